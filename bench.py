@@ -10,12 +10,19 @@ coordinates (forward, MSE, backward, gradient all-reduce when N > 1, Adam, plate
 scheduler) -- run.py:156-187.  Synthetic data (a two-tone signal on the linspace grid,
 weights random-init at seed 0); inputs resident in HBM before timing.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one process per GPU, RCCL)
 
-Prints ONE JSON line (rank 0).  `roofline` is for the SineLayer forward GEMM (north_star's
-"inner GEMM"; SIREN configs), timed with HIP events inside the timed region; `cpu_baseline` times the torch-CPU port of the same
-step (oracle/torch_cpu_step.py) on a bounded sample on rank 0 at N = 1.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the
+line: `value`, `ms_per_step`, and `roofline` for the SineLayer forward GEMM (north_star's "inner
+GEMM"; SIREN configs), timed with HIP events inside the timed region.  --dump-outputs DIR also
+writes what the last timed step left its caller (parameters, gradients, loss / lr history) as
+DIR/<name>.npy.  Everything that takes runs of its own is behind --full: the per-kind kernel
+breakdown (an untimed pass with every launch bracketed) and what follows from it (the other kinds'
+fractions, the HBM roofline of the width-256 stacks, the KAN roofline), the committed PMC traffic /
+attribution, `recon_snr` (the headline model's fit against the reference's run), `cpu_baseline`
+(the torch-CPU port of the same step, oracle/torch_cpu_step.py, on a bounded sample on rank 0 at
+N = 1) and `dist` (the exposed all-reduce time at N > 1).
 """
 from __future__ import annotations
 
@@ -192,24 +199,32 @@ def kan_work_per_row(widths):
     return by, fl
 
 
-def profiled_steps(eng, args, dev, dist, lib, _lib, records_per_step, dom_of):
+def profiled_steps(eng, args, dev, dist, lib, _lib, records_per_step, dom_of, static_dom=None):
     """Time args.steps steps with HIP events around only the dominant launch kind.
 
     Events around every launch cost a step 2-13% (measured: cfg4 2.35 -> 2.66 ms, cfg5 2.37 ->
     2.51, cfg2 27.6 -> 28.2), so the per-kind breakdown comes from a separate pass of up to 5
     steps with every kind bracketed (not timed); the kind dom_of(breakdown) picks is then the only
     one bracketed inside the timed region, which gives the roofline's per-launch duration live.
-    Returns (elapsed_s max over ranks, breakdown, breakdown_steps, dom, (dom_ms, dom_launches))."""
-    prof_steps = max(1, min(args.steps, 5))
-    _lib.check(lib.siren_profile_mask(0xFFFFFFFF), "profile_mask")
-    _lib.check(lib.siren_profile_enable(records_per_step * (prof_steps + 1)), "profile_enable")
-    for _ in range(prof_steps):
-        eng.step()
-    torch.cuda.synchronize(dev)
-    breakdown = _lib.profile_read()
-    dom = dom_of(breakdown, prof_steps)
-    _lib.check(lib.siren_profile_enable(records_per_step * (args.steps + 1)), "profile_enable")
-    _lib.check(lib.siren_profile_mask(1 << _lib.PROF_KINDS.index(dom)), "profile_mask")
+    Returns (elapsed_s max over ranks, breakdown, breakdown_steps, dom, (dom_ms, dom_launches)).
+
+    Without --full there is no separate pass: the breakdown is empty, and the timed region brackets
+    `static_dom`, the kind dom_of would pick where that does not depend on the breakdown (None: no
+    events at all; dom is then None and so is the roofline)."""
+    if args.full:
+        prof_steps = max(1, min(args.steps, 5))
+        _lib.check(lib.siren_profile_mask(0xFFFFFFFF), "profile_mask")
+        _lib.check(lib.siren_profile_enable(records_per_step * (prof_steps + 1)), "profile_enable")
+        for _ in range(prof_steps):
+            eng.step()
+        torch.cuda.synchronize(dev)
+        breakdown = _lib.profile_read()
+        dom = dom_of(breakdown, prof_steps)
+    else:
+        prof_steps, breakdown, dom = 0, {}, static_dom
+    if dom is not None:
+        _lib.check(lib.siren_profile_enable(records_per_step * (args.steps + 1)), "profile_enable")
+        _lib.check(lib.siren_profile_mask(1 << _lib.PROF_KINDS.index(dom)), "profile_mask")
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize(dev)
@@ -220,14 +235,48 @@ def profiled_steps(eng, args, dev, dist, lib, _lib, records_per_step, dom_of):
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    timed = _lib.profile_read()[dom]
-    _lib.check(lib.siren_profile_enable(0), "profile_disable")
-    _lib.check(lib.siren_profile_mask(0xFFFFFFFF), "profile_mask")
+    timed = (0.0, 0)
+    if dom is not None:
+        timed = _lib.profile_read()[dom]
+        _lib.check(lib.siren_profile_enable(0), "profile_disable")
+        _lib.check(lib.siren_profile_mask(0xFFFFFFFF), "profile_mask")
+        if not args.full:
+            breakdown = {dom: timed}
+            if not timed[1]:  # this stack has no launch of the pinned kind
+                dom = None
     if dist is not None:
         e = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
     return elapsed, breakdown, prof_steps, dom, timed
+
+
+DUMP_BUDGET = 60_000_000  # bytes of array data, all files of one --dump-outputs together (< 64 MB with headers)
+
+
+def dump_outputs(eng, out_dir: str) -> None:
+    """--dump-outputs: what a caller of eng.step() holds after the last timed step, as
+    out_dir/<name>.npy -- the flat fp32 parameter vector (the live weights behind
+    model.state_dict(), ParamLayout order), the flat gradient vector of that step, and
+    eng.history()'s loss (fp32) and lr (fp64) of every step applied so far.  The inputs are seeded
+    (weights: torch.manual_seed(0); coordinates and targets: closed-form on the grid), so two builds
+    run with the same arguments can be compared array for array.  An array over its share of
+    DUMP_BUDGET is written as a fixed seeded sample of its elements (ascending index order)."""
+    import numpy as np
+    n = eng.layout.n_params
+    losses, lrs = eng.history()  # synchronises
+    arrays = {"params": eng.params[:n].cpu().numpy(), "grads": eng.grads[:n].cpu().numpy(),
+              "loss_history": np.asarray(losses, np.float32), "lr_history": np.asarray(lrs, np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET
+    order = sorted(arrays, key=lambda k: arrays[k].nbytes)  # the small ones whole, the rest share what is left
+    for i, name in enumerate(order):
+        a = arrays[name]
+        keep = left // (len(order) - i) // a.itemsize
+        if a.size > keep:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def dp_report(eng, args, dev, dist, steps: int = 5) -> dict:
@@ -340,6 +389,8 @@ def run_kan(args, world, rank, dev, dist, lib, _lib):
     elapsed, prof, psteps, dom, (dom_ms, dom_n) = profiled_steps(
         eng, args, dev, dist, lib, _lib, 64 * eng.n_micro,
         lambda pr, n: max((k for k in bpr if pr[k][1]), key=lambda k: pr[k][0]))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs)
     kernels = {}
     for k, (ms, n) in prof.items():
         if n:
@@ -365,26 +416,29 @@ def run_kan(args, world, rank, dev, dist, lib, _lib):
                    "global_batch": n_total, "coords_per_gpu": per_gpu, "widths": widths,
                    "micro_batches_per_gpu": eng.n_micro, "parallelism": f"dp{world}",
                    "backend": args.backend if world > 1 else None},
-        # compute-bound once the expansions stay on chip: the fp32 dense peak for the dtype
-        "roofline": {"bound": "mfma", "kernel": dom, "achieved": kernels[dom]["tflops"], "peak": PEAK_F32_TFLOPS,
-                     "unit": "TFLOP/s", "frac": kernels[dom]["tflops"] / PEAK_F32_TFLOPS, "traffic": None,
-                     "peak_note": "fp32 dense (f32 MFMA = vector rate); the chunk products run on "
-                                  "v_mfma_f32_16x16x4_f32, the out = 1 head on VALU FMAs; GEMM flops only "
-                                  "(the B-spline recursion, recomputed in each of the three passes, is extra "
-                                  "VALU work)",
-                     "flops_per_row": fpr[dom], "rows_per_launch": rows,
-                     "hbm": {"achieved": kernels[dom]["gbs"], "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                             "frac": kernels[dom]["gbs"] / PEAK_HBM_GBS, "algorithmic_bytes_per_row": bpr[dom]}},
         "step_flop_frac": step_flops / (ms_per_step * 1e-3) / 1e12 / PEAK_F32_TFLOPS,
         "step_hbm_frac": step_bytes / (ms_per_step * 1e-3) / 1e9 / PEAK_HBM_GBS,
         "step_algorithmic_bytes": step_bytes, "step_gemm_flops": step_flops,
-        "kernels": kernels,
-        "kernels_source": f"{dom}: HIP events inside the timed region (the only kind bracketed there); "
-                          f"the other kinds: a separate untimed pass of {psteps} steps with every launch "
-                          f"bracketed",
         "final_loss": eng.last_loss(),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:  # the dominant kind is the breakdown's choice: the roofline needs that pass
+        result.update({
+            # compute-bound once the expansions stay on chip: the fp32 dense peak for the dtype
+            "roofline": {"bound": "mfma", "kernel": dom, "achieved": kernels[dom]["tflops"], "peak": PEAK_F32_TFLOPS,
+                         "unit": "TFLOP/s", "frac": kernels[dom]["tflops"] / PEAK_F32_TFLOPS, "traffic": None,
+                         "peak_note": "fp32 dense (f32 MFMA = vector rate); the chunk products run on "
+                                      "v_mfma_f32_16x16x4_f32, the out = 1 head on VALU FMAs; GEMM flops only "
+                                      "(the B-spline recursion, recomputed in each of the three passes, is extra "
+                                      "VALU work)",
+                         "flops_per_row": fpr[dom], "rows_per_launch": rows,
+                         "hbm": {"achieved": kernels[dom]["gbs"], "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                                 "frac": kernels[dom]["gbs"] / PEAK_HBM_GBS, "algorithmic_bytes_per_row": bpr[dom]}},
+            "kernels": kernels,
+            "kernels_source": f"{dom}: HIP events inside the timed region (the only kind bracketed there); "
+                              f"the other kinds: a separate untimed pass of {psteps} steps with every launch "
+                              f"bracketed",
+        })
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # A quarter of the SIREN sample (the B-spline expansion makes a CPU KAN step slow per
         # coordinate), at the box's CPU share only: at os.cpu_count() = 256 threads the KAN step
         # thrashes 40x (26 s a step, measured).
@@ -447,8 +501,13 @@ def main():
                     "(default: the whole per-GPU batch)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-recon-snr", action="store_true", help="skip the recon-SNR fit (cfg2, N = 1)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the per-kind "
+                    "kernel breakdown and the rooflines built on it, the committed PMC traffic, recon_snr, "
+                    "cpu_baseline, and the dist block at N > 1 (off: warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the "
+                    "last one left its caller (parameters, gradients, loss / lr history) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU port's timing")
+    ap.add_argument("--no-recon-snr", action="store_true", help="with --full: skip the recon-SNR fit (cfg2, N = 1)")
     ap.add_argument("--cpu-coords", type=int, default=65536)
     ap.add_argument("--cpu-steps", type=int, default=6)
     ap.add_argument("--set-option", action="append", default=[], metavar="K=V",
@@ -557,7 +616,10 @@ def main():
         return max((k for k in gemm_all if pr[k][1]), key=lambda k: pr[k][0])
 
     elapsed, prof, psteps, dom, (dom_ms, dom_n) = profiled_steps(
-        eng, args, dev, dist, lib, _lib, 64 * (2 * L + 8) * eng.n_micro, pick)
+        eng, args, dev, dist, lib, _lib, 64 * (2 * L + 8) * eng.n_micro, pick,
+        static_dom=None if bpr is not None else "inner_fwd")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs)
     loss = eng.last_loss()
 
     # one hidden-layer GEMM launch (fwd, dX or dW) covers one micro-batch of coordinates
@@ -574,15 +636,31 @@ def main():
         if k in kernels:
             kernels[k]["tflops"] = flops_gemm / (kernels[k]["avg_ms"] * 1e-3) / 1e12
     gemm_kinds = [k for k in gemm_all if k in kernels]
-    achieved = kernels[dom]["tflops"]
     inner_flops_step = 6.0 * per_gpu * H * H * L
-    gemm_ms_step = sum(kernels[k]["ms_per_step"] for k in gemm_kinds)
 
-    headline = args.config == "cfg2" and H == 1024 and L == 4 and per_gpu == 1 << 20 and eng.n_micro == 1
+    # the committed PMC passes were taken at the headline shape; reading them is --full's
+    headline = (args.full and dom is not None and args.config == "cfg2" and H == 1024 and L == 4
+                and per_gpu == 1 << 20 and eng.n_micro == 1)
     traffic, traffic_src = pmc_traffic(dom) if headline else (None, None)
     ms_per_step = elapsed / args.steps * 1e3
     value = (n_total if ranks == world else per_gpu) * args.steps / elapsed
     layers = L + 1
+    roofline = None  # no launch kind was bracketed (no --full: a stack whose kind the breakdown picks)
+    if dom is not None:
+        achieved = kernels[dom]["tflops"]
+        roofline = {"bound": "mfma", "kernel": dom,
+                    "kernel_choice": "pinned: the SineLayer forward GEMM (north_star's inner GEMM), "
+                                     "timed with HIP events over the timed region",
+                    "achieved": achieved, "peak": PEAK_BF16_TFLOPS,
+                    "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic,
+                    "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
+                    "flops_per_launch": flops_gemm,
+                    "hbm_gbs_at_traffic": (traffic / (kernels[dom]["avg_ms"] * 1e-3) / 1e9)
+                    if traffic else None,
+                    # the committed cycle attribution of this kernel (tools/pmc_attr.py): MFMA pipe
+                    # busy = SQ_INSTS_MFMA x 16 cycles / 1024 SIMDs over the dispatch's cycles
+                    # (GRBM_GUI_ACTIVE / 8), and the clock it ran at; frac = busy x clock / 2.4 GHz
+                    "pmc_attribution": pmc_attribution(dom) if headline else None}
     result = {
         "metric": METRIC, "value": value, "unit": "coord-samples/s", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
@@ -597,31 +675,22 @@ def main():
                    "micro_batches_per_gpu": eng.n_micro, "parallelism": f"dp{world}",
                    "backend": args.backend if world > 1 else None, "lib": args.lib,
                    "options": args.set_option or None},
-        "roofline": {"bound": "mfma", "kernel": dom,
-                     "kernel_choice": "pinned: the SineLayer forward GEMM (north_star's inner GEMM), "
-                                      "timed with HIP events over the timed region",
-                     "achieved": achieved, "peak": PEAK_BF16_TFLOPS,
-                     "unit": "TFLOP/s", "frac": achieved / PEAK_BF16_TFLOPS, "traffic": traffic,
-                     "traffic_unit": "bytes/launch", "traffic_source": traffic_src,
-                     "flops_per_launch": flops_gemm,
-                     "hbm_gbs_at_traffic": (traffic / (kernels[dom]["avg_ms"] * 1e-3) / 1e9)
-                     if traffic else None,
-                     # the committed cycle attribution of this kernel (tools/pmc_attr.py): MFMA pipe
-                     # busy = SQ_INSTS_MFMA x 16 cycles / 1024 SIMDs over the dispatch's cycles
-                     # (GRBM_GUI_ACTIVE / 8), and the clock it ran at; frac = busy x clock / 2.4 GHz
-                     "pmc_attribution": pmc_attribution(dom) if headline else None},
-        # every GEMM kind's spec-peak fraction (the dominant one is `roofline`); head_fwd does the
-        # forward GEMM's flops plus the head, loss gradient and head backward
-        "gemm_frac_by_kind": {k: kernels[k]["tflops"] / PEAK_BF16_TFLOPS for k in gemm_kinds},
+        "roofline": roofline,
         "step_mfma_frac": inner_flops_step / (ms_per_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS,
-        "gemm_mfma_frac": inner_flops_step / (gemm_ms_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS,
         "kernels": kernels,
-        "kernels_source": f"{dom}: HIP events inside the timed region (the only kind bracketed there); "
-                          f"the other kinds: a separate untimed pass of {psteps} steps with every launch "
-                          f"bracketed",
+        "kernels_source": f"{dom}: HIP events inside the timed region (the only kind bracketed there)"
+                          if dom is not None else "no kind bracketed (--full runs the per-kind pass)",
         "final_loss": loss,
         "fp16_overflow_steps": eng.guard_state()["overflows"],
     }
+    if args.full:
+        # every GEMM kind's spec-peak fraction (the dominant one is `roofline`); head_fwd does the
+        # forward GEMM's flops plus the head, loss gradient and head backward
+        gemm_ms_step = sum(kernels[k]["ms_per_step"] for k in gemm_kinds)
+        result["gemm_frac_by_kind"] = {k: kernels[k]["tflops"] / PEAK_BF16_TFLOPS for k in gemm_kinds}
+        result["gemm_mfma_frac"] = inner_flops_step / (gemm_ms_step * 1e-3) / 1e12 / PEAK_BF16_TFLOPS
+        result["kernels_source"] += (f"; the other kinds: a separate untimed pass of {psteps} steps with every "
+                                     f"launch bracketed")
     if ranks != world:
         # fill of the persistent GEMM grids at this shard: 256 x 256 tiles over the CUs
         tiles = (round_up(per_gpu // eng.n_micro, 256) // 256) * (H // 256)
@@ -634,6 +703,9 @@ def main():
             "waves": waves, "wave_tail_frac": (math.ceil(waves) - waves) / math.ceil(waves)}
         result["scaling"] = "strong" if args.strong else "weak"
     if bpr is not None:
+        result["config"]["stack"] = {"first": "sine", "hidden": layers_kind, "a_initial": A_INITIAL,
+                                     "reference": "run.py:466" if args.config == "live" else "run.py:30 defaults"}
+    if bpr is not None and args.full:
         # HBM roofline (width 256: 2 H^2 flop per row against >= 8 H bytes, far below the MFMA ridge)
         fused = prof["head_fwd"][1] > 0
         for k, b in bpr.items():
@@ -641,8 +713,6 @@ def main():
                 kernels[k]["bytes_per_step"] = b * per_gpu
                 kernels[k]["gbs"] = b * per_gpu / (kernels[k]["ms_per_step"] * 1e-3) / 1e9
         step_bytes = sum(bpr.values()) * per_gpu
-        result["config"]["stack"] = {"first": "sine", "hidden": layers_kind, "a_initial": A_INITIAL,
-                                     "reference": "run.py:466" if args.config == "live" else "run.py:30 defaults"}
         result["roofline"] = {
             "bound": "hbm", "kernel": dom, "kernel_choice": "the kind with the most time per step (HBM-bound stack)",
             "achieved": kernels[dom]["gbs"], "peak": PEAK_HBM_GBS, "unit": "GB/s",
@@ -654,11 +724,11 @@ def main():
         result["step_hbm_frac"] = step_bytes / (ms_per_step * 1e-3) / 1e9 / PEAK_HBM_GBS
         result["step_algorithmic_bytes"] = step_bytes
         result["bytes_per_row_by_kind"] = bpr
-    if dist is not None:
+    if args.full and dist is not None:
         result["dist"] = dp_report(eng, args, dev, dist)
-    if world == 1 and args.config == "cfg2" and not args.no_recon_snr:
+    if args.full and world == 1 and args.config == "cfg2" and not args.no_recon_snr:
         result["recon_snr"] = recon_snr(dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # BASELINE.md CPU plan: median of steps 2..k with torch.set_num_threads(os.cpu_count()).  On
         # the GPU box os.cpu_count() reports the whole host (256) while the job's CPU share is
         # OMP_NUM_THREADS (16), and 256 threads on that share thrash (6x slower, measured): the

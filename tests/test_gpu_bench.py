@@ -47,7 +47,7 @@ def test_torchrun_two_ranks_gloo():
     res = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                 "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
                 "--backend", "gloo", "--steps", "2", "--warmup", "1", "--coords", "65536", "--hidden", "256",
-                "--layers", "3", "--no-cpu-baseline"])
+                "--layers", "3", "--full", "--no-cpu-baseline"])
     _common(res, 2, "cfg2")
     assert res["config"]["global_batch"] == 2 * 65536 and res["config"]["backend"] == "gloo"
     assert "cpu_baseline" not in res and "recon_snr" not in res
@@ -62,10 +62,10 @@ def test_torchrun_two_ranks_gloo():
 
 
 def test_single_gpu_line_carries_recon_snr():
-    """The default line carries both halves of BASELINE's metric: coord-samples/s and, outside the
+    """The --full line carries both halves of BASELINE's metric: coord-samples/s and, outside the
     timed region, the recon SNR of the headline model's fit against the reference's run of it."""
     res = _run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--coords", "65536",
-                "--no-cpu-baseline"])
+                "--full", "--no-cpu-baseline"])
     r = res["recon_snr"]
     assert r is not None and r["fixture"].startswith("tests/golden/")
     assert abs(r["snr_target_db"] - r["reference_snr_target_db"]) < r["tolerance_db"], r
@@ -84,7 +84,8 @@ def test_torchrun_two_ranks_strong_scaling():
 
 
 def test_kan_config():
-    res = _run([sys.executable, "bench.py", "--config", "cfg5", "--steps", "2", "--warmup", "1", "--coords", "50000"])
+    res = _run([sys.executable, "bench.py", "--config", "cfg5", "--steps", "2", "--warmup", "1", "--coords", "50000",
+                "--full"])
     assert res["n_gpus"] == 1 and res["value"] > 0 and res["dtype"] == "fp32"
     assert res["config"]["widths"] == [1, 64, 64, 1] and res["roofline"]["bound"] == "mfma"
     assert 0 < res["roofline"]["frac"] < 1 and res["roofline"]["kernel"].startswith("kan_")
@@ -97,3 +98,29 @@ def test_single_gpu_configs(cfg, extra):
     _common(res, 1, cfg)
     assert res["config"]["in_features"] == 2
     assert res["config"]["layers"] == (6 if cfg == "cfg3" else 5)
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """Without --full the line is the timed steps' own: no breakdown pass, recon SNR, CPU baseline
+    or dist block; the roofline's kind is the only one in `kernels`.  --dump-outputs writes what
+    the last timed step left: the parameter and gradient vectors and one loss / lr per step run."""
+    import numpy as np
+    out = tmp_path / "dump"
+    res = _run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2", "--coords", "65536",
+                "--hidden", "256", "--layers", "3", "--dump-outputs", str(out)])
+    _common(res, 1, "cfg2")
+    assert res["steps"] == 3 and res["warmup"] == 2 and res["ms_per_step"] > 0
+    assert abs(res["value"] - 65536 / (res["ms_per_step"] * 1e-3)) <= 1e-9 * res["value"]
+    for k in ("recon_snr", "cpu_baseline", "dist", "gemm_frac_by_kind"):
+        assert k not in res, k
+    assert list(res["kernels"]) == ["inner_fwd"] and res["roofline"]["kernel"] == "inner_fwd"
+    assert res["kernels"]["inner_fwd"]["launches_per_step"] in (1, 2)  # 2 hidden layers, the last fused with the head
+    arrs = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+    assert sorted(arrs) == ["grads", "loss_history", "lr_history", "params"]
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64_000_000
+    n_params = 256 * 1 + 256 + 2 * (256 * 256 + 256) + 256 + 1  # the head bias's segment is padded to 64 floats
+    assert arrs["params"].size == arrs["grads"].size and n_params <= arrs["params"].size < n_params + 64
+    assert len(arrs["loss_history"]) == len(arrs["lr_history"]) == 5
+    assert float(arrs["loss_history"][-1]) == res["final_loss"]
+    assert np.isfinite(arrs["params"]).all() and np.isfinite(arrs["grads"]).all() and arrs["grads"].any()

@@ -250,3 +250,34 @@ def test_bench_bytes_per_row_live_stack():
     # forwards: sine 3e, sine 3e, snake 4e; dX into snake (i=3), sine (2), sine (1): 4e + 3e + 3e
     assert dflt["inner_fwd"] == 10 * e and dflt["bwd_dx"] == 10 * e and dflt["bwd_dw"] == 8 * e
     assert bench.STACKS["live"] == (0, 4) and bench.CONFIGS["live"][0] == 256 and bench.CONFIGS["live"][3] == 441_000
+
+
+def test_bench_dump_outputs_keeps_small_arrays_whole_and_samples_the_rest(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 / float64 .npy files within the byte budget; an array that fits
+    is written whole, a larger one as the same seeded sample of its elements every time."""
+    import sys
+    import types
+
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    n = 5000
+    g = torch.Generator().manual_seed(1)
+    eng = types.SimpleNamespace(
+        layout=types.SimpleNamespace(n_params=n), params=torch.randn(n + 64, generator=g),
+        grads=torch.randn(n + 64, generator=g),
+        history=lambda: (np.arange(3, dtype=np.float32), np.full(3, 1e-3, np.float64)))
+    bench.dump_outputs(eng, str(tmp_path / "whole"))
+    got = {f: np.load(tmp_path / "whole" / f) for f in os.listdir(tmp_path / "whole")}
+    assert sorted(got) == ["grads.npy", "loss_history.npy", "lr_history.npy", "params.npy"]
+    assert np.array_equal(got["params.npy"], eng.params[:n].numpy()) and got["params.npy"].dtype == np.float32
+    assert np.array_equal(got["grads.npy"], eng.grads[:n].numpy()) and got["lr_history.npy"].dtype == np.float64
+    assert bench.DUMP_BUDGET + 4 * 128 <= 64_000_000  # the data plus four .npy headers
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 36 + 2 * 4 * 1000)  # the histories, then 1000 floats each
+    for d in ("a", "b"):
+        bench.dump_outputs(eng, str(tmp_path / d))
+    a, b = (np.load(tmp_path / d / "params.npy") for d in ("a", "b"))
+    assert a.size == 1000 and np.array_equal(a, b) and np.isin(a, eng.params[:n].numpy()).all()
+    assert np.load(tmp_path / "a" / "grads.npy").size == 1000
+    assert np.array_equal(np.load(tmp_path / "a" / "loss_history.npy"), np.arange(3, dtype=np.float32))

@@ -1,6 +1,6 @@
 """KAN kernel ablation (measurement only, never the product): builds libsiren_hip variants with
 KAN_ABL = 1 (trivial basis stand-in), 2 (no chunk products), 3 (both) and runs
-`bench.py --config cfg5` on each in a child process, printing each variant's per-kind kernel
+`bench.py --full --config cfg5` on each in a child process, printing each variant's per-kind kernel
 times.  Separates the fused kernels' basis work, their MFMA products and their load / barrier
 skeleton.
 
@@ -28,7 +28,7 @@ import runpy, sys
 sys.path.insert(0, {root!r})
 from inr_for_audio_amd import _lib
 _lib.load({lib!r})
-sys.argv = ["bench.py", "--config", "cfg5", "--steps", "10", "--warmup", "3", "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--config", "cfg5", "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline"]
 runpy.run_path({bench!r}, run_name="__main__")
 """
 

@@ -1,4 +1,4 @@
-"""A/B of whole bench steps across builds of the library: `bench.py --config C` in a child process
+"""A/B of whole bench steps across builds of the library: `bench.py --full --config C` in a child process
 per (round, library), libraries alternating, per-kind kernel ms per step printed per run.
 
     python tools/lib_ab.py --config cfg5 --libs base=inr-for-audio_amd/libsiren_hip.so,x=inr-for-audio_amd/libsiren_x.so
@@ -21,7 +21,8 @@ from inr_for_audio_amd import _lib
 lib = _lib.load({lib!r})
 for opt, val in {opts!r}:
     _lib.check(lib.siren_set_option(opt, val), "set_option")
-sys.argv = ["bench.py", "--config", {cfg!r}, "--steps", "10", "--warmup", "3", "--no-cpu-baseline", "--no-recon-snr"]
+sys.argv = ["bench.py", "--config", {cfg!r}, "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline",
+            "--no-recon-snr"]
 runpy.run_path({bench!r}, run_name="__main__")
 """
 
