@@ -117,6 +117,12 @@ typedef struct siren_net {
   int32_t first_snake, pad1;
   const float* a0;                          /* [H] (first_snake)            */
   float head_omega, pad2;
+  /* run.py:141-144 rff.layers.GaussianEncoding(sigma, 1, rff_freq) in front of net.0 (appended in
+   * ABI 12; 0 = none): coords stay the raw [rows][1] coordinate (in_dim must be 1), rff_B is the
+   * encoding's b [rff_freq][1] fp32 (not trained) and W0 is [H][2 rff_freq] -- net.0 sees
+   * cat(cos(2 pi x b^T), sin(2 pi x b^T)), built inside the first layer's kernel.  1..256. */
+  int32_t rff_freq, pad3;
+  const float* rff_B;
 } siren_net;
 
 /* gradient destinations (fp32, accumulated into: zero them, or set zero_grads) */
@@ -139,7 +145,7 @@ typedef struct siren_batch {
   double n_total;        /* global coordinate count: MSE mean denominator    */
   int32_t splits;        /* split-K slices of the weight-gradient GEMM       */
   int32_t zero_grads;    /* 1: zero `grads.flat` before accumulating         */
-  const float* coords;   /* [rows][in]  */
+  const float* coords;   /* [rows][in]  (net.rff_freq > 0: the raw [rows][1] coordinate) */
   const float* target;   /* [rows]      */
   uint16_t* Y[SIREN_MAX_INNER + 1];  /* Y[0..L] fp16 [rows][H]: layer outputs          */
   uint16_t* C[SIREN_MAX_INNER + 1];  /* C[0..L] fp16 [rows][H]: cos(.) of a sine layer,
@@ -180,6 +186,12 @@ typedef struct siren_batch {
   siren_guard* guard;
   int32_t* tileq;            /* SIREN_TILEQ_INTS ints of tile-queue counters on the device of the
                                 activations (NULL: the forward GEMM's static tile walk) */
+  /* net.rff_freq > 0 (appended in ABI 12): enc = fp16 [rows][siren_rff_kpad(rff_freq)], the
+   * encoded coordinates the first layer's forward writes once for its weight gradient (NULL at
+   * inference: not written); rff_slab = siren_rff_slab_floats(rows, hidden, rff_freq) floats, the
+   * encoded layer's own split-K slab (train / backward) */
+  uint16_t* enc;
+  float* rff_slab;
 } siren_batch;
 
 /* Workspace sizing / tiling helpers.  siren_nt_tile: tile edge the NT GEMMs use for
@@ -306,6 +318,35 @@ int siren_inner_bwd_dx_act(const uint16_t* dZ, const uint16_t* WTh, const uint16
 int siren_first_bwd_dx(const uint16_t* dZ1, const uint16_t* WTh1, const uint16_t* C0, const float* t,
                        int32_t in_dim, float omega0, int32_t rows, int32_t hidden, const float* gscale,
                        float* part, void* stream);
+/* ---- Gaussian random-Fourier-feature encoding (run.py:141-144) --------------------------
+ * rff.layers.GaussianEncoding(sigma, input_size=1, encoded_size=F): b = randn(F, 1) * sigma,
+ * v -> cat(cos(2 pi v b^T), sin(2 pi v b^T), dim=-1), cosines first.  x [rows][1], B = b [F] fp32,
+ * F = rff_freq in 1..256 (else SIREN_ERR_CONFIG).  The phase x b is reduced exactly in
+ * revolutions in fp32 before the hardware cos / sin. */
+/* width of the fp16 enc buffers: 2 rff_freq padded to a multiple of 128 (0: rff_freq out of range) */
+int32_t siren_rff_kpad(int32_t rff_freq);
+/* floats of siren_batch.rff_slab / siren_rff_first_bwd's slab (0: unsupported shape) */
+int64_t siren_rff_slab_floats(int32_t rows, int32_t hidden, int32_t rff_freq);
+/* run.py:141-144 encoding(model_input): out = fp32 [rows][2 rff_freq] (the module API) */
+int siren_rff_encode(const float* x, const float* B, int32_t rff_freq, int64_t rows, float* out, void* stream);
+/* run.py:141-144 + models.py:114-115: the first SineLayer on the encoded coordinate in one launch --
+ * a0 = omega0 (enc(x) W0^T + b0) as an exact fp32 product (W0 [hidden][2 rff_freq]), Y0 = sin a0,
+ * C0 = cos a0 -> fp16; a != NULL: Linear + Snake(a) instead (first_linear=True, models.py:330-333,
+ * E0 required, omega0 unused); enc (nullable): receives enc(x) as fp16 [rows][siren_rff_kpad] */
+int siren_rff_first_fwd(const float* x, const float* B, int32_t rff_freq, const float* W0, const float* b0,
+                        float omega0, const float* a, int32_t rows, int32_t hidden, uint16_t* Y0, uint16_t* C0,
+                        uint16_t* E0, uint16_t* enc, void* stream);
+/* autograd of run.py:141-144's encoded first layer given the layer above: dZ0/omega0 = C0 (dZ1 W1)
+ * (x S, fp16, written to dZ0 [rows][hidden]; omega0 is applied in fp32 afterwards, it would
+ * overflow fp16), gW0 [hidden][2 rff_freq] += omega0 dZ0^T enc(x) / S split-K over the rows, gb0 +=
+ * omega0 colsum(dZ0) / S.  E0 != NULL: Linear + Snake first layer (C0 = dY/dz, omega0 unused,
+ * ga0 += colsum((dZ1 W1) E0) / S).  enc: fp16 [rows][siren_rff_kpad] scratch (computed here from
+ * x and B); part: [rows/128][2][hidden], red_tmp: [4][64][hidden], slab: siren_rff_slab_floats.
+ * Rows whose dZ1 is zero (pad rows: g = 0) contribute exactly nothing. */
+int siren_rff_first_bwd(const uint16_t* dZ1, const uint16_t* WTh1, const uint16_t* C0, const uint16_t* E0,
+                        const float* x, const float* B, int32_t rff_freq, float omega0, int32_t rows,
+                        int32_t hidden, const float* gscale, uint16_t* dZ0, uint16_t* enc, float* part,
+                        float* red_tmp, float* slab, float* gW0, float* gb0, float* ga0, void* stream);
 /* autograd addmm dW: slab[s] = partial dZ^T Y over coordinate slice s, tile edge 128/256
  * (0 = siren_dw_tile(rows, hidden)); siren_dw_reduce must get the same tile. */
 int siren_inner_bwd_dw(const uint16_t* Y, const uint16_t* dZ, int32_t rows, int32_t hidden,

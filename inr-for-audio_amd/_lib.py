@@ -57,6 +57,7 @@ class SirenNet(ctypes.Structure):
         ("w_head", _p), ("b_head", _p),
         ("act", _i32 * MAX_INNER), ("a", _p * MAX_INNER),
         ("first_snake", _i32), ("pad1", _i32), ("a0", _p), ("head_omega", ctypes.c_float), ("pad2", ctypes.c_float),
+        ("rff_freq", _i32), ("pad3", _i32), ("rff_B", _p),
     ]
 
 
@@ -81,6 +82,7 @@ class SirenBatch(ctypes.Structure):
         ("E", _p * (MAX_INNER + 1)),
         ("grad_ready", _p * (MAX_INNER + 2)),
         ("loss_mode", _i32), ("head_scale_prev", _i32), ("guard", _p), ("tileq", _p),
+        ("enc", _p), ("rff_slab", _p),
     ]
 
 
@@ -142,6 +144,13 @@ _SIGS = {
     "siren_inner_bwd_dx": (ctypes.c_int, [_p, _p, _p, ctypes.c_float, _i32, _i32, _p, _p, _p, _p]),
     "siren_first_bwd_dx": (ctypes.c_int, [_p, _p, _p, _p, _i32, ctypes.c_float, _i32, _i32, _p, _p,
                                           _p]),
+    "siren_rff_kpad": (_i32, [_i32]),
+    "siren_rff_slab_floats": (_i64, [_i32, _i32, _i32]),
+    "siren_rff_encode": (ctypes.c_int, [_p, _p, _i32, _i64, _p, _p]),
+    "siren_rff_first_fwd": (ctypes.c_int, [_p, _p, _i32, _p, _p, ctypes.c_float, _p, _i32, _i32, _p, _p, _p, _p,
+                                           _p]),
+    "siren_rff_first_bwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i32, ctypes.c_float, _i32, _i32, _p, _p, _p,
+                                           _p, _p, _p, _p, _p, _p, _p]),
     "siren_inner_bwd_dw": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "siren_dw_reduce": (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _i32, _p, _p]),
     "siren_nt_tile": (_i32, [_i32, _i32]),

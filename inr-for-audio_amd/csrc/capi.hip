@@ -80,6 +80,11 @@ int check_net(const siren_net* n) {
   }
   if (n->first_snake && !n->a0) return SIREN_ERR_NULL;
   if (!(n->head_omega >= 0.f)) return SIREN_ERR_CONFIG;
+  // run.py:141-144: the encoding is built for the 1-D waveform coordinate only
+  if (n->rff_freq != 0) {
+    if (n->rff_freq < 1 || n->rff_freq > kRffMaxFreq || n->in_dim != 1) return SIREN_ERR_CONFIG;
+    if (!n->rff_B) return SIREN_ERR_NULL;
+  }
   return SIREN_OK;
 }
 
@@ -107,6 +112,7 @@ int check_batch(const siren_net* n, const siren_batch* b, bool train) {
         !b->slab || !b->gmax_part || !b->gscale)
       return SIREN_ERR_NULL;
     if (b->splits < 1 || b->n_total <= 0) return SIREN_ERR_CONFIG;
+    if (n->rff_freq > 0 && (!b->enc || !b->rff_slab)) return SIREN_ERR_NULL;
   }
   if (b->loss_mode < 0 || b->loss_mode > 1) return SIREN_ERR_CONFIG;
   return SIREN_OK;
@@ -149,9 +155,15 @@ bool head_fused(const siren_net* n, const siren_batch* b, hipStream_t s) {
 // fused NT_FWD_HB (training; gfac = the loss gradient factor, b->gscale already set)
 hipError_t run_forward(const siren_net* n, siren_batch* b, hipStream_t s, bool hb = false, float gfac = 0.f) {
   const int R = b->rows, H = n->hidden, L = n->n_inner;
-  SIREN_PROF(SIREN_PROF_FIRST_FWD, s, first_fwd(b->coords, n->in_dim, n->W0, n->b0, n->omega0, R, H, B(b->Y[0]),
-                                                B(b->C[0]), s, n->first_snake ? n->a0 : nullptr,
-                                                n->first_snake ? B(b->E[0]) : nullptr));
+  if (n->rff_freq > 0) {  // run.py:141-144: net.0 on the encoded coordinate, one launch (rff.hip)
+    SIREN_PROF(SIREN_PROF_FIRST_FWD, s, rff_first_fwd(b->coords, n->rff_B, n->rff_freq, n->W0, n->b0, n->omega0, R, H,
+                                                      B(b->Y[0]), B(b->C[0]), n->first_snake ? n->a0 : nullptr,
+                                                      n->first_snake ? B(b->E[0]) : nullptr, B(b->enc), s));
+  } else {
+    SIREN_PROF(SIREN_PROF_FIRST_FWD, s, first_fwd(b->coords, n->in_dim, n->W0, n->b0, n->omega0, R, H, B(b->Y[0]),
+                                                  B(b->C[0]), s, n->first_snake ? n->a0 : nullptr,
+                                                  n->first_snake ? B(b->E[0]) : nullptr));
+  }
   // the run of plain forward layers is ONE profiling record (back-to-back launches: one event
   // pair per run instead of per launch, so the per-launch dispatch latency inside the bracket
   // is paid once; bench.py divides by the launch count)
@@ -283,6 +295,27 @@ static int check_grads(const siren_net* net, const siren_grads* gr) {
   return SIREN_OK;
 }
 
+// run.py:141-144's encoded first layer once NT_DX / NT_DX_SNAKE left dZ0 / omega0 (x S) in dZ0 and
+// the [prow][1 or 2][H] partials of db0 (and da0), x 1/S, in part: db0 (x omega0 for the sine
+// layer), da0, and dW0 = omega0 dZ0^T enc / S split-K over the rows (rff.hip)
+static hipError_t rff_first_grads(bool fs, float omega0, int F, int R, int H, int prow, const h16* enc,
+                                  const h16* dZ0, const float* gscale, const float* part, float* red_tmp,
+                                  float* slab, float* gW0, float* gb0, float* ga0, hipStream_t s) {
+  float* db = slab + rff_slab_floats(R, H, F) - H;
+  ColSegs sg = {};
+  if (fs) {
+    seg_add(sg, part, gb0);
+    seg_add(sg, part + H, ga0);
+    SIREN_PROF(SIREN_PROF_REDUCE, s, col_reduce_multi(sg, 2 * (int64_t)H, prow, H, 1, red_tmp, s));
+  } else {
+    seg_add(sg, part, db);
+    SIREN_PROF(SIREN_PROF_REDUCE, s, col_reduce_multi(sg, H, prow, H, 0, red_tmp, s));
+  }
+  SIREN_PROF(SIREN_PROF_BWD_DW, s, rff_dw0(enc, dZ0, F, R, H, fs ? 1.0f : omega0, gscale, slab, fs ? nullptr : db,
+                                            gW0, gb0, s));
+  return hipSuccess;
+}
+
 // autograd of models.py:388-394 given dLoss/dout in batch->g (rows >= n_valid are zero).  hb: the
 // forward's NT_FWD_HB already wrote dZ_L and the [R/256][2][H] partials of db_L and dw_head
 static int run_backward(const siren_net* net, const siren_grads* gr, siren_batch* b, hipStream_t s,
@@ -350,6 +383,18 @@ static int run_backward(const siren_net* net, const siren_grads* gr, siren_batch
       if (snake) seg_add(sg, b->col_part + H, gr->a[i - 1]);
       SIREN_PROF(SIREN_PROF_REDUCE, s, col_reduce_multi(sg, rs, prow, H, 1, b->red_tmp, s));
       cur ^= 1;
+    } else if (net->rff_freq > 0) {
+      // encoded first layer: the hidden-layer dX epilogue with omega 1 stores C0 (dZ1 W1) S; omega0
+      // (22000 by default: it would overflow fp16 at this S) enters in fp32 in rff_first_grads
+      const bool fs = net->first_snake != 0;
+      p.omega = 1.0f;
+      p.Cprev = B(b->C[0]);
+      p.Eprev = B(b->E[0]);
+      p.dZ = B(b->dZ[cur ^ 1]);
+      SIREN_PROF(SIREN_PROF_BWD_DX0, s, gemm_nt(fs ? NT_DX_SNAKE : NT_DX, false, p, s));
+      SIREN_TRY(rff_first_grads(fs, net->omega0, net->rff_freq, R, H, prow, B(b->enc), B(b->dZ[cur ^ 1]), b->gscale,
+                                b->col_part, b->red_tmp, b->rff_slab, gr->W0, gr->b0, gr->a0, s));
+      SIREN_TRY(mark_ready(b, L, s));
     } else {
       const bool fs = net->first_snake != 0;
       p.omega = fs ? 1.0f : net->omega0;
@@ -646,6 +691,55 @@ int siren_first_bwd_dx(const uint16_t* dZ1, const uint16_t* WTh1, const uint16_t
   p.omega = omega0; p.Cprev = B(C0); p.t = t; p.in_dim = in_dim; p.colsum_part = part;
   p.gscale = gscale;
   return (int)gemm_nt(NT_DX0, false, p, S(stream));
+}
+
+// ---- Gaussian random-Fourier-feature encoding (run.py:141-144) ------------------------------
+static bool rff_freq_ok(int32_t f) { return f >= 1 && f <= kRffMaxFreq; }
+
+int32_t siren_rff_kpad(int32_t rff_freq) { return rff_freq_ok(rff_freq) ? rff_kpad(rff_freq) : 0; }
+
+int64_t siren_rff_slab_floats(int32_t rows, int32_t hidden, int32_t rff_freq) {
+  if (!rff_freq_ok(rff_freq) || !hidden_ok(hidden) || rows <= 0 || rows % SIREN_ROW_TILE) return 0;
+  return rff_slab_floats(rows, hidden, rff_freq);
+}
+
+int siren_rff_encode(const float* x, const float* Bf, int32_t rff_freq, int64_t rows, float* out, void* stream) {
+  if (!rff_freq_ok(rff_freq)) return SIREN_ERR_CONFIG;
+  if (!x || !Bf || !out) return SIREN_ERR_NULL;
+  if (rows < 0) return SIREN_ERR_SHAPE;
+  return (int)rff_encode(x, Bf, rff_freq, rows, out, S(stream));
+}
+
+int siren_rff_first_fwd(const float* x, const float* Bf, int32_t rff_freq, const float* W0, const float* b0,
+                        float omega0, const float* a, int32_t rows, int32_t hidden, uint16_t* Y0, uint16_t* C0,
+                        uint16_t* E0, uint16_t* enc, void* stream) {
+  if (!rff_freq_ok(rff_freq)) return SIREN_ERR_CONFIG;
+  if (!x || !Bf || !W0 || !b0 || !Y0 || !C0 || (a && !E0)) return SIREN_ERR_NULL;
+  if (!hidden_ok(hidden) || rows <= 0 || rows % SIREN_ROW_TILE) return SIREN_ERR_SHAPE;
+  return (int)rff_first_fwd(x, Bf, rff_freq, W0, b0, omega0, rows, hidden, B(Y0), B(C0), a, a ? B(E0) : nullptr,
+                            B(enc), S(stream));
+}
+
+int siren_rff_first_bwd(const uint16_t* dZ1, const uint16_t* WTh1, const uint16_t* C0, const uint16_t* E0,
+                        const float* x, const float* Bf, int32_t rff_freq, float omega0, int32_t rows,
+                        int32_t hidden, const float* gscale, uint16_t* dZ0, uint16_t* enc, float* part,
+                        float* red_tmp, float* slab, float* gW0, float* gb0, float* ga0, void* stream) {
+  if (!rff_freq_ok(rff_freq)) return SIREN_ERR_CONFIG;
+  if (!dZ1 || !WTh1 || !C0 || !x || !Bf || !dZ0 || !enc || !part || !red_tmp || !slab || !gW0 || !gb0 ||
+      (E0 && !ga0))
+    return SIREN_ERR_NULL;
+  if (!hidden_ok(hidden) || rows <= 0 || rows % SIREN_ROW_TILE) return SIREN_ERR_SHAPE;
+  hipStream_t s = S(stream);
+  const bool fs = E0 != nullptr;
+  SIREN_TRY(rff_encode16(x, Bf, rff_freq, rows, B(enc), s));
+  NtParams p = {};
+  p.X = B(dZ1); p.W = B(WTh1); p.M = rows; p.N = hidden; p.K = hidden;
+  p.tile = nt_choose_tile(rows, hidden);
+  p.omega = 1.0f; p.Cprev = B(C0); p.Eprev = B(E0); p.dZ = B(dZ0); p.colsum_part = part;
+  p.gscale = gscale;
+  SIREN_TRY(gemm_nt(fs ? NT_DX_SNAKE : NT_DX, false, p, s));
+  return (int)rff_first_grads(fs, omega0, rff_freq, rows, hidden, rows / p.tile, B(enc), B(dZ0), gscale, part,
+                              red_tmp, slab, gW0, gb0, ga0, s);
 }
 
 int siren_inner_bwd_dw(const uint16_t* Y, const uint16_t* dZ, int32_t rows, int32_t hidden,

@@ -185,6 +185,21 @@ hipError_t fp32_act_bwd(int act, const float* x, int64_t rows, int cols, const f
 hipError_t fp32_linear_bwd(const float* x, int64_t rows, int in, int out, const float* W, float omega, float* gpre,
                            float* gx, float* gW, float* gb, float* slab, int splits, float* tmp, hipStream_t s);
 
+// Gaussian random-Fourier-feature encoded first layer (rff.hip; run.py:141-144): x [R][1], Bf [F],
+// enc = [cos(2 pi x Bf) | sin(2 pi x Bf)], W0 [H][2F].  enc buffers are fp16 [R][rff_kpad(F)]
+constexpr int kRffMaxFreq = 256;
+int rff_kpad(int F);                          // 2F padded to the weight-gradient GEMM's 128-column tile
+int rff_splits(int R, int H, int F);          // split-K slices of the dW0 GEMM
+int64_t rff_slab_floats(int R, int H, int F);  // [splits + 1][H][kpad] + [H]
+hipError_t rff_encode(const float* x, const float* Bf, int F, int64_t rows, float* out, hipStream_t s);
+hipError_t rff_encode16(const float* x, const float* Bf, int F, int R, h16* enc, hipStream_t s);
+// a0 / E0 non-null: Linear + Snake first layer; enc nullable (inference)
+hipError_t rff_first_fwd(const float* x, const float* Bf, int F, const float* W0, const float* b0, float omega0, int R,
+                         int H, h16* Y0, h16* C0, const float* a0, h16* E0, h16* enc, hipStream_t s);
+// gW0 [H][2F] += scale (dZ0^T enc) / S and (db non-null) gb0 += scale db; slab: rff_slab_floats
+hipError_t rff_dw0(const h16* enc, const h16* dZ0, int F, int R, int H, float scale, const float* gscale,
+                   float* slab, const float* db, float* gW0, float* gb0, hipStream_t s);
+
 // KAN (kan.hip): fp32, grid_size 5, spline_order 3 (9 A-columns per input)
 // fused layer kernels (the bases are recomputed in LDS; A and dA never reach HBM)
 hipError_t kan_fwd_fused(const float* X, const float* grid, const float* W, int64_t N, int in, int out, float* Y,

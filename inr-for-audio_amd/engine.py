@@ -47,17 +47,18 @@ class NetSpec:
     acts: tuple = ()   # siren_act per inner layer (empty: all sine)
     first_snake: bool = False   # first_linear=True: net.0 is Linear + Snake
     head_omega: float = 0.0     # last_linear=False: final SineLayer(H, 1, head_omega)
+    rff_freq: int = 0           # run.py:141-144 GaussianEncoding in front of net.0 (W0 is [H][2 rff_freq])
 
     def act(self, i: int) -> int:
         return self.acts[i] if self.acts else _lib.ACT_SINE
 
 
-def net_spec(model) -> NetSpec:
+def net_spec(model, encoding=None) -> NetSpec:
     """Validate that `model` is a SirenWithSnakeTanh configuration the HIP path implements."""
     spec = getattr(model, "hip_spec", None)
     if spec is None:
         raise TypeError("expected inr_for_audio_amd.models.SirenWithSnakeTanh")
-    return spec()
+    return spec() if encoding is None else spec(encoding)
 
 
 class ParamLayout:
@@ -161,6 +162,12 @@ class Workspace:
             self.splits = 1
             self.dZ = [None, None]
             self.col_part = self.col_part2 = self.red_tmp = self.slab = None
+        # the encoded first layer's own buffers (training only): enc(x) as fp16 for its weight
+        # gradient, and that GEMM's split-K slab -- col_part / slab keep their in_dim = 1 sizes
+        self.enc = self.rff_slab = None
+        if train and spec.rff_freq:
+            self.enc = torch.zeros(R, int(lib.siren_rff_kpad(spec.rff_freq)), dtype=h, device=device)
+            self.rff_slab = e(int(lib.siren_rff_slab_floats(R, H, spec.rff_freq)))
 
     def batch(self, coords: torch.Tensor, target, n_valid: int, n_total: float,
               zero_grads: bool = False, guard: torch.Tensor | None = None, loss_mode: int = 0) -> SirenBatch:
@@ -182,10 +189,11 @@ class Workspace:
         b.col_part, b.col_part2 = ptr(self.col_part), ptr(self.col_part2)
         b.red_tmp, b.slab = ptr(self.red_tmp), ptr(self.slab)
         b.tileq = ptr(self.tileq)
+        b.enc, b.rff_slab = ptr(self.enc), ptr(self.rff_slab)
         return b
 
 
-def make_net(spec: NetSpec, W0, b0, bs, Whs, WThs, w_head, b_head, snake_a=None, a0=None) -> SirenNet:
+def make_net(spec: NetSpec, W0, b0, bs, Whs, WThs, w_head, b_head, snake_a=None, a0=None, rff_B=None) -> SirenNet:
     n = SirenNet()
     n.in_dim, n.hidden, n.n_inner = spec.in_dim, spec.hidden, spec.n_inner
     n.omega0, n.omega = spec.omega0, spec.omega
@@ -199,6 +207,10 @@ def make_net(spec: NetSpec, W0, b0, bs, Whs, WThs, w_head, b_head, snake_a=None,
     n.first_snake = int(spec.first_snake)
     n.a0 = ptr(a0)
     n.head_omega = float(spec.head_omega)
+    if spec.rff_freq:
+        if rff_B is None or rff_B.numel() != spec.rff_freq:
+            raise ValueError(f"rff_freq={spec.rff_freq} needs the encoding's b [{spec.rff_freq}][1]")
+        n.rff_freq, n.rff_B = int(spec.rff_freq), ptr(rff_B)
     return n
 
 
@@ -265,7 +277,10 @@ class SirenEngine:
     def __init__(self, model, coords: torch.Tensor, target: torch.Tensor, *, lr: float = 1e-3,
                  min_lr: float = 1e-6, factor: float = 0.8, patience: int = 200,
                  n_total: int | None = None, micro_batch: int = 1 << 20, hist_cap: int = 20000,
-                 splits: int | None = None, device=None, loss_mode: str = "mse"):
+                 splits: int | None = None, device=None, loss_mode: str = "mse", encoding=None):
+        """`encoding` (encoding.GaussianEncoding, run.py:141-144): `coords` stay the raw [N][1]
+        coordinates and model.in_features must be 2 * encoded_size -- the first layer's kernel
+        builds the encoded input itself (training and infer())."""
         lib = _lib.load()
         self.lib = lib
         if loss_mode not in LOSS_MODES:
@@ -274,7 +289,8 @@ class SirenEngine:
         if self.device.type != "cuda":
             raise RuntimeError("SirenEngine runs on the GPU only (HIP kernels; no CPU fallback)")
         self.model = model
-        self.spec = spec = net_spec(model)
+        self.encoding = encoding
+        self.spec = spec = net_spec(model, encoding)
         self.layout = lay = ParamLayout(model, model.hip_padding())
         dev = self.device
 
@@ -294,6 +310,16 @@ class SirenEngine:
         self.exp_avg = torch.zeros_like(self.params)
         self.exp_avg_sq = torch.zeros_like(self.params)
 
+        # the encoding's b (not trained): a device copy, rank 0's in a process group (each rank
+        # draws its own otherwise), written back so that every rank's module holds the one in use
+        self.rff_B = None
+        if encoding is not None:
+            self.rff_B = encoding.b.detach().to(dev, torch.float32).reshape(-1).contiguous().clone()
+            if d is not None:
+                d.broadcast(self.rff_B, src=0)
+                with torch.no_grad():
+                    encoding.b.copy_(self.rff_B.reshape(encoding.b.shape))
+
         L, H = spec.n_inner, spec.hidden
         self.ix = ix = model.param_index()
         pv = lambda i: lay.view(self.params, i)  # noqa: E731
@@ -302,7 +328,7 @@ class SirenEngine:
         self.WTh = [torch.empty(H, H, dtype=STORE16, device=dev) for _ in range(L)]
         self.net = make_net(spec, pv(ix["W0"]), pv(ix["b0"]), [pv(k) for k in ix["b"]], self.Wh, self.WTh,
                             pv(ix["wh"]), pv(ix["bh"]), [None if k is None else pv(k) for k in ix["a"]],
-                            None if ix["a0"] is None else pv(ix["a0"]))
+                            None if ix["a0"] is None else pv(ix["a0"]), rff_B=self.rff_B)
         self.grad_struct = make_grads(spec, lay, self.grads, ix)
         self._Wp = (ctypes.c_void_p * L)(*[ptr(w) for w in self.W])
         self._Whp = (ctypes.c_void_p * L)(*[ptr(w) for w in self.Wh])

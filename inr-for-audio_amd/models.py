@@ -124,8 +124,10 @@ class SirenWithSnakeTanh(nn.Module):
                                  omega_0=hidden_omega_0))
         self.net = nn.Sequential(*net)
 
-    def hip_spec(self):
-        """NetSpec of the fused path; raises for configurations it does not cover."""
+    def hip_spec(self, encoding=None):
+        """NetSpec of the fused path; raises for configurations it does not cover.  `encoding`
+        (encoding.GaussianEncoding, run.py:141-144): the network takes the encoded coordinate, so
+        in_features must be 2 * encoded_size and the raw coordinate is 1-D."""
         from .engine import NetSpec
         if self.out_features != 1:
             raise NotImplementedError("HIP path: out_features must be 1 (run.py:95,112)")
@@ -133,16 +135,23 @@ class SirenWithSnakeTanh(nn.Module):
         if n_inner < 1:
             raise NotImplementedError("HIP path: at least one hidden layer (num_sine + num_snake + "
                                       "num_tanh >= 1)")
-        if self.in_features not in (1, 2):
+        in_dim, rff_freq = self.in_features, 0
+        if encoding is not None:
+            rff_freq = int(encoding.encoded_size)
+            if self.in_features != 2 * rff_freq:
+                raise ValueError(f"in_features={self.in_features} must be 2 * encoded_size = {2 * rff_freq} "
+                                 "(run.py:81-82)")
+            in_dim = 1
+        elif self.in_features not in (1, 2):
             raise NotImplementedError("HIP path: in_features must be 1 or 2")
         H = self.hip_width()
         if n_inner > _lib.MAX_INNER:
             raise NotImplementedError(f"HIP path: num_sine + num_snake + num_tanh <= {_lib.MAX_INNER}")
         acts = (_lib.ACT_SINE,) * self.num_sine + (_lib.ACT_SNAKE,) * self.num_snake + \
             (_lib.ACT_TANH,) * self.num_tanh
-        return NetSpec(self.in_features, H, n_inner, float(self.first_omega_0),
+        return NetSpec(in_dim, H, n_inner, float(self.first_omega_0),
                        float(self.hidden_omega_0), acts, bool(self.first_linear),
-                       0.0 if self.last_linear else float(self.hidden_omega_0))
+                       0.0 if self.last_linear else float(self.hidden_omega_0), rff_freq)
 
     def hip_width(self) -> int:
         """The hidden width the kernels run at: hidden_features itself when it is 128, 256, 512,

@@ -3,8 +3,10 @@
 Differences from the reference are limited to what the hot-path scope excludes: no plots
 (matplotlib figures), no loss-landscape, no STFT / auraloss-SNR loss terms (alpha must be 0 --
 at alpha=0 the reference's STFT term contributes exactly zero; loss_mode 'mse'
-and 'mae' (L1Loss, run.py:161-163) are fused on device, 'snr' needs auraloss), no
-random-Fourier-feature encoding.  ``multichannel=True`` (keyword-only) fits the (time,
+and 'mae' (L1Loss, run.py:161-163) are fused on device, 'snr' needs auraloss).  ``num_freq=F``
+puts the Gaussian random-Fourier-feature encoding of run.py:141-144 in front of the waveform MLP
+(encoding.GaussianEncoding; its b is saved in the checkpoint, which the reference forgets).
+``multichannel=True`` (keyword-only) fits the (time,
 channel) grid of MultiWaveformFitting (utils.py:186-231; the reference's call site,
 run.py:59-63, is commented out, with mode == 'lp' selecting its FIR decimation) -- BASELINE
 cfg3's data path; its output.wav is written as a (samples, channels) file.  arch='kan' fits KAN([1, H, H, 1]) (SURVEY §8 f4,
@@ -27,11 +29,15 @@ import numpy as np
 import scipy.io.wavfile as wavfile
 import torch
 
+from .encoding import GaussianEncoding
 from .engine import KanEngine, SirenEngine
 from .kan import KAN
 from .models import SirenWithSnakeTanh
 from .utils import (MDCTFitting, MultiWaveformFitting, WaveformFitting, calculate_snr, get_coord,
                     load_mono_like_librosa, reported_snr)
+
+
+RFF_KEY = "rff_b"  # checkpoint key of the GaussianEncoding's b (an addition: run.py:359-362 saves none)
 
 
 def save_parameters(experiment_folder, **kwargs):
@@ -92,8 +98,10 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         raise NotImplementedError("arch='kan' is fitted with loss_mode='mse'")
     if multichannel and (method != "wave" or arch != "mlp" or bwe):
         raise NotImplementedError("multichannel fits the waveform MLP (run.py:59-63) without bwe")
-    if num_freq is not None:
-        raise NotImplementedError("random Fourier features (rff) are out of scope")
+    if num_freq is not None and (method != "wave" or arch != "mlp" or multichannel):
+        # the reference's own code cannot run these: b is [num_freq][1] against 2-D coordinates
+        # (run.py:142-143), and KAN is built with input width 1 (run.py:93)
+        raise NotImplementedError("num_freq encodes the 1-D waveform coordinate of the MLP (run.py:141-144)")
     if visualization:
         raise NotImplementedError("loss-landscape visualization is out of scope")
 
@@ -120,6 +128,9 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         ground_truth = torch.from_numpy(np.ascontiguousarray(pixels))
         input_dimension = 2
 
+    if num_freq is not None:  # run.py:81-82
+        input_dimension = num_freq * 2
+
     if seed is not None:
         torch.manual_seed(seed)
     if arch == "kan":  # run.py:92-93
@@ -135,9 +146,19 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         ckpt = torch.load(prev_ckpt_path, map_location="cpu", weights_only=True)
         model.load_state_dict(ckpt["model_state_dict"])
 
+    # run.py:141-144: the encoding is drawn after the model (sigma 10.0).  The reference forgets
+    # to save its b, so a resumed run there fits against a fresh one; here the checkpoint carries
+    # it under RFF_KEY and prev_ckpt_path reuses it (a checkpoint without the key draws afresh)
+    encoding = None
+    if num_freq is not None:
+        saved_b = None if ckpt is None else ckpt.get(RFF_KEY)
+        encoding = GaussianEncoding(b=saved_b) if saved_b is not None else GaussianEncoding(10.0, 1, num_freq)
+        if encoding.encoded_size != num_freq:
+            raise ValueError(f"checkpoint encoding has {encoding.encoded_size} frequencies, num_freq={num_freq}")
+
     dev = torch.device(device or "cuda")
     Engine = KanEngine if arch == "kan" else SirenEngine
-    kw = {} if arch == "kan" else {"loss_mode": loss_mode}
+    kw = {} if arch == "kan" else {"loss_mode": loss_mode, "encoding": encoding}
     engine = Engine(model, model_input, ground_truth, lr=learning_rate, min_lr=min_learning_rate,
                     patience=patience, micro_batch=micro_batch, hist_cap=total_steps, device=dev, **kw)
     if ckpt is not None:
@@ -205,6 +226,8 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
 
         checkpoint = {"model_state_dict": {k: v.detach().cpu().clone() for k, v in model.state_dict().items()},
                       "optimizer_state_dict": engine.adam_state_dict()}
+        if encoding is not None:
+            checkpoint[RFF_KEY] = encoding.b.detach().cpu().clone()
         torch.save(checkpoint, ckpt_path)
 
         n_gpus = torch.distributed.get_world_size() if not single else 1
