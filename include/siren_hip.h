@@ -52,8 +52,8 @@ int siren_abi_version(void);
  * stale or foreign library is refused instead of trusted by file time */
 const char* siren_build_id(void);
 /* sizeof of the ABI structs, for binding checks: 0 siren_net, 1 siren_grads, 2 siren_batch,
- * 3 siren_opt_state, 4 siren_kan_net, 5 siren_kan_grads, 6 siren_kan_batch, 7 siren_guard
- * (-1: unknown) */
+ * 3 siren_opt_state, 4 siren_kan_net, 5 siren_kan_grads, 6 siren_kan_batch, 7 siren_guard,
+ * 8 siren_spectral (-1: unknown) */
 int64_t siren_struct_size(int32_t which);
 const char* siren_status_string(int status);
 
@@ -172,7 +172,8 @@ typedef struct siren_batch {
    * [L]: the first layer (W0, b0); [L+1]: the head (w_head, b_head) and `sse`. */
   void* grad_ready[SIREN_MAX_INNER + 2];
   /* run.py:161-169 loss_mode: 0 = MSELoss (sse = sum err^2, g = 2 err / n_total), 1 = L1Loss
-   * ('mae': sse slot = sum |err|, g = sign(err) / n_total) */
+   * ('mae': sse slot = sum |err|, g = sign(err) / n_total), 2 = the SNR loss ('snr', run.py:126,
+   * :165): siren_train_step_spectral only (siren_train_step has no workspace for it: SIREN_ERR_NULL) */
   int32_t loss_mode;
   /* ABI 11: 1 = gmax_part holds the max|g| partials of a previous siren_train_step /
    * siren_backward on this workspace (same rows).  A Snake last layer then runs fused with the
@@ -347,6 +348,62 @@ int siren_rff_first_bwd(const uint16_t* dZ1, const uint16_t* WTh1, const uint16_
                         const float* x, const float* B, int32_t rff_freq, float omega0, int32_t rows,
                         int32_t hidden, const float* gscale, uint16_t* dZ0, uint16_t* enc, float* part,
                         float* red_tmp, float* slab, float* gW0, float* gb0, float* ga0, void* stream);
+/* ---- STFT and SNR losses (run.py:126-128 auraloss.freq.STFTLoss() / auraloss.time.SNRLoss(),
+ * evaluated at run.py:160-169) ------------------------------------------------------------------
+ * Restated from the published auraloss 0.4.0 defaults; x = model output, y = target, both one
+ * sequence of n samples:
+ *   X = stft(x, n_fft 1024, hop 256, periodic Hann, center, reflect): T = 1 + n / 256 frames, 513 bins
+ *   x_mag = sqrt(max(re^2 + im^2, 1e-8));  L_stft = |y_mag - x_mag|_F / |y_mag|_F + mean|log x_mag - log y_mag|
+ *   L_snr = -10 log10(sum yc^2 / (sum (xc - yc)^2 + 1e-8) + 1e-8), xc / yc = x / y minus their means
+ * The transform is an exact-fp32 MFMA GEMM against windowed cos / -sin tables.  `basis` holds two
+ * fragment-native copies of the table v[c][k][bin] (c 0: w_k cos(2 pi k bin / 1024), 1: -w_k sin(.);
+ * bin < 528, zero past 512): floats [0, 2*1024*528) as [c][k / 16][bin][k % 16], then the same
+ * number as [c][bin / 16][k][bin % 16].  `ws` is one fp32 workspace; siren_stft_ws_offset locates
+ * its pieces.  n > 512 (reflect padding is undefined below; else SIREN_ERR_SHAPE), n <= 2^30. */
+/* run.py:160 frames of an n-sample signal (0: n <= 512) */
+int64_t siren_stft_frames(int64_t n);
+int64_t siren_stft_basis_floats(void);
+/* run.py:128 the transform's tables, computed in fp64 and rounded once -- `basis_host` is a HOST
+ * buffer of siren_stft_basis_floats() floats (the only host pointer of this ABI; copy it to the device) */
+int siren_stft_basis_fill(float* basis_host);
+/* floats of siren_spectral.stft_ws / `ws` below for n samples in a batch of `rows` rows (-1: bad shape) */
+int64_t siren_stft_workspace_floats(int32_t n, int32_t rows);
+/* float offset of a piece of the workspace (-1: unknown): 0 re [T][528], 1 im [T][528], 2 y_mag
+ * [T][528], 3 log y_mag [T][528], 4 dF [T][1024], 5 the scalars [32]: {S1, sum|dlog|, Sy, L_stft,
+ * 1/(sqrt S1 sqrt Sy), 1/(T 513), mean x, mean y, sum yc^2, sum r^2, L_snr, SNR gradient factor,
+ * point loss, mixed loss} */
+int64_t siren_stft_ws_offset(int32_t n, int32_t rows, int32_t which);
+/* run.py:160 STFT magnitude side: target 0 -- re / im of x and the per-block partials of S1 and
+ * sum|dlog| against the stored target; target 1 -- y_mag, log y_mag and Sy of the target (once) */
+int siren_stft_forward(const float* x, int32_t n, int32_t rows, const float* basis, float* ws, int32_t target,
+                       void* stream);
+/* run.py:160 the finished STFT scalars from siren_stft_forward's partials; loss[0] = L_stft (device) */
+int siren_stft_loss(int32_t n, int32_t rows, float* ws, float* loss, void* stream);
+/* autograd of run.py:160 after siren_stft_forward + siren_stft_loss: g_stft [n] = dL_stft/dx (the
+ * transposed GEMM, then a fixed-order gather over frames and reflected images: no atomics) */
+int siren_stft_loss_bwd(int32_t n, int32_t rows, const float* basis, float* ws, float* g_stft, void* stream);
+/* run.py:126, :165 SNRLoss and its gradient: loss[0] = L_snr, g [n] = dL_snr/dx (both device) */
+int siren_snr_loss(const float* x, const float* y, int32_t n, int32_t rows, float* ws, float* loss, float* g,
+                   void* stream);
+
+/* run.py:158-185 with the reference's remaining loss options (run.py:126-128, :160-169):
+ * loss = (1 - alpha) {MSE | L1 | SNR (batch.loss_mode 0 | 1 | 2)} + alpha L_stft.  The loss is global
+ * -- every output sample feeds every gradient -- so the step runs the last layer and the head
+ * unfused, the loss kernels above on batch.out, and the backward from the mixed g (left in batch.g,
+ * zero on pad rows) exactly as siren_backward runs it; grads.sse[0] receives the FINISHED mixed loss
+ * (pass n_total = 1 to siren_apply_update).  The batch must hold the whole signal (n_total ==
+ * n_valid, else SIREN_ERR_CONFIG); alpha in [0, 1]; alpha != 0 needs n_valid > 512.  With alpha 0
+ * and loss_mode 0 / 1 it is siren_train_step.  (A struct and an entry point of their own: siren_batch
+ * and siren_train_step keep their ABI 12 layout and behaviour.) */
+typedef struct siren_spectral {
+  double alpha;              /* weight of the STFT term */
+  const float* stft_basis;   /* siren_stft_basis_floats() floats from siren_stft_basis_fill (alpha != 0) */
+  float* stft_ws;            /* siren_stft_workspace_floats(n_valid, rows) floats; with alpha != 0 its target
+                                side set once by siren_stft_forward(target, ..., 1) */
+} siren_spectral;
+int siren_train_step_spectral(const siren_net* net, const siren_grads* grads, siren_batch* batch,
+                              const siren_spectral* loss, void* stream);
+
 /* autograd addmm dW: slab[s] = partial dZ^T Y over coordinate slice s, tile edge 128/256
  * (0 = siren_dw_tile(rows, hidden)); siren_dw_reduce must get the same tile. */
 int siren_inner_bwd_dw(const uint16_t* Y, const uint16_t* dZ, int32_t rows, int32_t hidden,
@@ -457,7 +514,9 @@ enum siren_prof_kind {
   /* the last hidden layer fused with the head, the loss gradient and the head backward
    * (siren_train_step with SIREN_OPT_HEAD_FUSE; counted apart from INNER_FWD) */
   SIREN_PROF_HEAD_FWD = 12,
-  SIREN_PROF_NKINDS = 13
+  /* the STFT / SNR loss kernels and the loss mix (siren_train_step_spectral) */
+  SIREN_PROF_LOSS = 13,
+  SIREN_PROF_NKINDS = 14
 };
 /* tuning knobs for in-process A/B measurement (process-global; 0 = automatic):
  * SIREN_OPT_NT_TILE / SIREN_OPT_TN_TILE = 128 or 256 forces the GEMM tile edge;

@@ -86,6 +86,11 @@ class SirenBatch(ctypes.Structure):
     ]
 
 
+class SirenSpectral(ctypes.Structure):
+    """siren_spectral: the STFT term's weight and the loss workspace (run.py:126-128, :160-169)."""
+    _fields_ = [("alpha", ctypes.c_double), ("stft_basis", _p), ("stft_ws", _p)]
+
+
 KAN_MAX_LAYERS = 8
 
 
@@ -123,6 +128,8 @@ _SIGS = {
     "siren_forward": (ctypes.c_int, [ctypes.POINTER(SirenNet), ctypes.POINTER(SirenBatch), _p]),
     "siren_train_step": (ctypes.c_int, [ctypes.POINTER(SirenNet), ctypes.POINTER(SirenGrads),
                                         ctypes.POINTER(SirenBatch), _p]),
+    "siren_train_step_spectral": (ctypes.c_int, [ctypes.POINTER(SirenNet), ctypes.POINTER(SirenGrads),
+                                                 ctypes.POINTER(SirenBatch), ctypes.POINTER(SirenSpectral), _p]),
     "siren_backward": (ctypes.c_int, [ctypes.POINTER(SirenNet), ctypes.POINTER(SirenGrads),
                                       ctypes.POINTER(SirenBatch), _p]),
     "siren_apply_update": (ctypes.c_int, [ctypes.POINTER(SirenNet), _p, _p, _p, _p, _i64,
@@ -151,6 +158,15 @@ _SIGS = {
                                            _p]),
     "siren_rff_first_bwd": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _i32, ctypes.c_float, _i32, _i32, _p, _p, _p,
                                            _p, _p, _p, _p, _p, _p, _p]),
+    "siren_stft_frames": (_i64, [_i64]),
+    "siren_stft_basis_floats": (_i64, []),
+    "siren_stft_basis_fill": (ctypes.c_int, [_p]),
+    "siren_stft_workspace_floats": (_i64, [_i32, _i32]),
+    "siren_stft_ws_offset": (_i64, [_i32, _i32, _i32]),
+    "siren_stft_forward": (ctypes.c_int, [_p, _i32, _i32, _p, _p, _i32, _p]),
+    "siren_stft_loss": (ctypes.c_int, [_i32, _i32, _p, _p, _p]),
+    "siren_stft_loss_bwd": (ctypes.c_int, [_i32, _i32, _p, _p, _p, _p]),
+    "siren_snr_loss": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _p, _p, _p]),
     "siren_inner_bwd_dw": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "siren_dw_reduce": (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _i32, _p, _p]),
     "siren_nt_tile": (_i32, [_i32, _i32]),
@@ -185,10 +201,11 @@ _SIGS = {
                                           ctypes.POINTER(_i64)]),
 }
 
-STRUCTS = [SirenNet, SirenGrads, SirenBatch, SirenOptState, SirenKanNet, SirenKanGrads, SirenKanBatch, SirenGuard]
+STRUCTS = [SirenNet, SirenGrads, SirenBatch, SirenOptState, SirenKanNet, SirenKanGrads, SirenKanBatch, SirenGuard,
+           SirenSpectral]
 
 PROF_KINDS = ["first_fwd", "inner_fwd", "head", "bwd_dw", "bwd_dx", "bwd_dx0", "reduce", "update",
-              "kan_fwd", "kan_dw", "kan_dx", "kan_misc", "head_fwd"]
+              "kan_fwd", "kan_dw", "kan_dx", "kan_misc", "head_fwd", "loss"]
 
 
 def profile_read() -> dict:

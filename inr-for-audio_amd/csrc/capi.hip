@@ -96,7 +96,15 @@ float act_bound(const siren_net* n, int i) {
   return n->act[i] == SIREN_ACT_SINE ? n->omega : (n->act[i] == SIREN_ACT_SNAKE ? 2.0f : 1.0f);
 }
 
-int check_batch(const siren_net* n, const siren_batch* b, bool train) {
+// run.py:160-169: a batch with an STFT term or the SNR loss takes the unfused step with the loss
+// kernels of stft.hip between the forward and the backward
+constexpr int kStftMaxN = 1 << 30;
+bool spectral(const siren_batch* b, const siren_spectral* sp) { return (sp && sp->alpha != 0.0) || b->loss_mode == 2; }
+
+// loss_step: the call evaluates the loss (siren_train_step*), so loss_mode 2 / alpha need their workspace;
+// siren_backward takes dLoss/dout as given and ignores both
+int check_batch(const siren_net* n, const siren_batch* b, bool train, const siren_spectral* sp = nullptr,
+                bool loss_step = false) {
   if (!b) return SIREN_ERR_NULL;
   if (b->rows <= 0 || b->rows % SIREN_ROW_TILE || b->n_valid < 0 || b->n_valid > b->rows)
     return SIREN_ERR_SHAPE;
@@ -114,7 +122,15 @@ int check_batch(const siren_net* n, const siren_batch* b, bool train) {
     if (b->splits < 1 || b->n_total <= 0) return SIREN_ERR_CONFIG;
     if (n->rff_freq > 0 && (!b->enc || !b->rff_slab)) return SIREN_ERR_NULL;
   }
-  if (b->loss_mode < 0 || b->loss_mode > 1) return SIREN_ERR_CONFIG;
+  if (b->loss_mode < 0 || b->loss_mode > 2) return SIREN_ERR_CONFIG;
+  if (sp && !(sp->alpha >= 0.0 && sp->alpha <= 1.0)) return SIREN_ERR_CONFIG;
+  if (loss_step && spectral(b, sp)) {
+    // run.py:160-169: the STFT / SNR losses see the whole signal in one workspace
+    if (!sp || !sp->stft_ws || (sp->alpha != 0.0 && !sp->stft_basis)) return SIREN_ERR_NULL;
+    if (b->n_total != (double)b->n_valid) return SIREN_ERR_CONFIG;
+    if (b->n_valid < 1 || b->n_valid > kStftMaxN || (sp->alpha != 0.0 && stft_frames(b->n_valid) < 1))
+      return SIREN_ERR_SHAPE;
+  }
   return SIREN_OK;
 }
 
@@ -235,6 +251,7 @@ int64_t siren_struct_size(int32_t which) {
     case 5: return sizeof(siren_kan_grads);
     case 6: return sizeof(siren_kan_batch);
     case 7: return sizeof(siren_guard);
+    case 8: return sizeof(siren_spectral);
   }
   return -1;
 }
@@ -416,10 +433,46 @@ static int run_backward(const siren_net* net, const siren_grads* gr, siren_batch
   return SIREN_OK;
 }
 
-int siren_train_step(const siren_net* net, const siren_grads* gr, siren_batch* b, void* stream) {
+// run.py:158-185 with an STFT term (alpha) or the SNR loss (run.py:126-128, :160-169).  The loss is
+// global -- every output sample feeds every gradient through 1024-point frames and the sums over the
+// whole signal -- so it cannot live in the fused last layer's epilogue: unfused forward and head_loss
+// (out, and the L1 / MSE sum), the loss kernels (stft.hip), then the backward from the mixed
+// g = dLoss/dout exactly as siren_backward runs it.  gr->sse[0] receives the finished mixed loss.
+static int run_spectral_step(const siren_net* net, const siren_grads* gr, siren_batch* b,
+                             const siren_spectral* sp, float gfac, hipStream_t s) {
+  const int R = b->rows, H = net->hidden, n = b->n_valid, nsum = (R + 255) / 256;
+  const int nparts = H / nt_choose_tile(R, H);
+  const bool stft = sp->alpha != 0.0;
+  const StftWs w = stft_ws_map(sp->stft_ws, n, R);
+  SIREN_TRY(run_forward(net, b, s));
+  // out (through the final sine of last_linear=False) and the |err| / err^2 partials; its g is replaced
+  SIREN_PROF(SIREN_PROF_HEAD, s, head_loss(b->head_part, nparts, R, net->b_head, b->target, n, gfac, b->out, b->g,
+                                           b->sse_part, b->gsum_part, b->gmax_part, s, net->head_omega,
+                                           b->loss_mode == 1 ? 1 : 0));
+  if (b->loss_mode == 2) SIREN_PROF(SIREN_PROF_LOSS, s, snr_sums(b->out, b->target, n, w, s));
+  if (stft) SIREN_PROF(SIREN_PROF_LOSS, s, stft_forward(b->out, n, sp->stft_basis, w, false, s));
+  SIREN_PROF(SIREN_PROF_LOSS, s, loss_finish(w, n, b->sse_part, nsum, b->loss_mode, sp->alpha, b->n_total, stft,
+                                             gr->sse, s));
+  if (stft) SIREN_PROF(SIREN_PROF_LOSS, s, stft_backward(sp->stft_basis, w, s));
+  SIREN_PROF(SIREN_PROF_LOSS, s, loss_mix(b->out, b->target, n, R, w, b->loss_mode, sp->alpha, gfac, b->g, s));
+  // from here on siren_backward's sequence; batch->g keeps dLoss/dout, the chain through a final
+  // sine (last_linear=False) goes to a copy
+  siren_batch bb = *b;
+  if (net->head_omega > 0.f) {
+    SIREN_TRY(hipMemcpyAsync(w.gchain, b->g, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, s));
+    SIREN_TRY(head_sine_chain(b->head_part, nparts, R, net->b_head, net->head_omega, w.gchain, s));
+    bb.g = w.gchain;
+  }
+  SIREN_TRY(sum_to(bb.g, R, gr->b_head, 1, s));
+  SIREN_TRY(gmax_partials(bb.g, R, b->gmax_part, s));
+  return run_backward(net, gr, &bb, s);
+}
+
+static int train_step(const siren_net* net, const siren_grads* gr, siren_batch* b, const siren_spectral* sp,
+                      void* stream) {
   int st = check_net(net);
   if (st) return st;
-  if ((st = check_batch(net, b, true))) return st;
+  if ((st = check_batch(net, b, true, sp, true))) return st;
   if ((st = check_grads(net, gr))) return st;
   if (!gr->sse) return SIREN_ERR_NULL;
   hipStream_t s = S(stream);
@@ -429,6 +482,7 @@ int siren_train_step(const siren_net* net, const siren_grads* gr, siren_batch* b
 
   // mean backward: MSELoss 2 err / N, L1Loss sign(err) / N
   const float gfac = (float)((b->loss_mode == 1 ? 1.0 : 2.0) / b->n_total);
+  if (spectral(b, sp)) return run_spectral_step(net, gr, b, sp, gfac, s);
   const bool hb = head_fused(net, b, s);
   if (hb) {
     // the fused head needs the backward scale S before the forward.  Sine / Tanh last layer
@@ -459,6 +513,16 @@ int siren_train_step(const siren_net* net, const siren_grads* gr, siren_batch* b
                                            gr->sse + 1));
   // ---- backward (autograd of run.py:185) ----
   return run_backward(net, gr, b, s, hb);
+}
+
+int siren_train_step(const siren_net* net, const siren_grads* gr, siren_batch* b, void* stream) {
+  return train_step(net, gr, b, nullptr, stream);
+}
+
+int siren_train_step_spectral(const siren_net* net, const siren_grads* gr, siren_batch* b,
+                              const siren_spectral* loss, void* stream) {
+  if (!loss) return SIREN_ERR_NULL;
+  return train_step(net, gr, b, loss, stream);
 }
 
 int siren_backward(const siren_net* net, const siren_grads* gr, siren_batch* b, void* stream) {
@@ -740,6 +804,71 @@ int siren_rff_first_bwd(const uint16_t* dZ1, const uint16_t* WTh1, const uint16_
   SIREN_TRY(gemm_nt(fs ? NT_DX_SNAKE : NT_DX, false, p, s));
   return (int)rff_first_grads(fs, omega0, rff_freq, rows, hidden, rows / p.tile, B(enc), B(dZ0), gscale, part,
                               red_tmp, slab, gW0, gb0, ga0, s);
+}
+
+// ---- STFT and SNR losses (run.py:126-128, :160-169) -----------------------------------------
+// n samples in a batch of `rows` rows; `stft`: the transform needs n > 512
+static int stft_shape(int32_t n, int32_t rows, bool stft) {
+  if (n < 1 || n > kStftMaxN || rows < n || (stft && stft_frames(n) < 1)) return SIREN_ERR_SHAPE;
+  return SIREN_OK;
+}
+
+int64_t siren_stft_frames(int64_t n) { return n >= 0 && n <= kStftMaxN ? stft_frames(n) : 0; }
+
+int64_t siren_stft_basis_floats(void) { return stft_basis_floats(); }
+
+int siren_stft_basis_fill(float* basis_host) {
+  if (!basis_host) return SIREN_ERR_NULL;
+  stft_basis_fill(basis_host);
+  return SIREN_OK;
+}
+
+int64_t siren_stft_workspace_floats(int32_t n, int32_t rows) {
+  return stft_shape(n, rows, false) ? -1 : stft_ws_floats(n, rows);
+}
+
+int64_t siren_stft_ws_offset(int32_t n, int32_t rows, int32_t which) {
+  if (stft_shape(n, rows, false)) return -1;
+  const StftWs w = stft_ws_map(nullptr, n, rows);
+  const float* const p[6] = {w.re, w.im, w.ymag, w.ylog, w.dF, w.scal};
+  return which >= 0 && which < 6 ? (int64_t)((uintptr_t)p[which] / sizeof(float)) : -1;
+}
+
+int siren_stft_forward(const float* x, int32_t n, int32_t rows, const float* basis, float* ws, int32_t target,
+                       void* stream) {
+  if (!x || !basis || !ws) return SIREN_ERR_NULL;
+  if (target < 0 || target > 1) return SIREN_ERR_CONFIG;
+  int st = stft_shape(n, rows, true);
+  if (st) return st;
+  return (int)stft_forward(x, n, basis, stft_ws_map(ws, n, rows), target != 0, S(stream));
+}
+
+int siren_stft_loss(int32_t n, int32_t rows, float* ws, float* loss, void* stream) {
+  if (!ws || !loss) return SIREN_ERR_NULL;
+  int st = stft_shape(n, rows, true);
+  if (st) return st;
+  return (int)loss_finish(stft_ws_map(ws, n, rows), n, nullptr, 0, -1, 1.0, 1.0, true, loss, S(stream));
+}
+
+int siren_stft_loss_bwd(int32_t n, int32_t rows, const float* basis, float* ws, float* g_stft, void* stream) {
+  if (!basis || !ws || !g_stft) return SIREN_ERR_NULL;
+  int st = stft_shape(n, rows, true);
+  if (st) return st;
+  const StftWs w = stft_ws_map(ws, n, rows);
+  SIREN_TRY(stft_backward(basis, w, S(stream)));
+  return (int)stft_gather(n, w, g_stft, S(stream));
+}
+
+int siren_snr_loss(const float* x, const float* y, int32_t n, int32_t rows, float* ws, float* loss, float* g,
+                   void* stream) {
+  if (!x || !y || !ws || !loss || !g) return SIREN_ERR_NULL;
+  int st = stft_shape(n, rows, false);
+  if (st) return st;
+  hipStream_t s = S(stream);
+  const StftWs w = stft_ws_map(ws, n, rows);
+  SIREN_TRY(snr_sums(x, y, n, w, s));
+  SIREN_TRY(loss_finish(w, n, nullptr, 0, 2, 0.0, (double)n, false, loss, s));
+  return (int)loss_mix(x, y, n, n, w, 2, 0.0, 0.f, g, s);
 }
 
 int siren_inner_bwd_dw(const uint16_t* Y, const uint16_t* dZ, int32_t rows, int32_t hidden,

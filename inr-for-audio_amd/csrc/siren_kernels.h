@@ -200,6 +200,37 @@ hipError_t rff_first_fwd(const float* x, const float* Bf, int F, const float* W0
 hipError_t rff_dw0(const h16* enc, const h16* dZ0, int F, int R, int H, float scale, const float* gscale,
                    float* slab, const float* db, float* gW0, float* gb0, hipStream_t s);
 
+// STFT / SNR losses and the loss mix (stft.hip; run.py:126-128, :160-169).  One caller-owned fp32
+// workspace of stft_ws_floats(n, rows) floats, carved up by stft_ws_map
+constexpr int kStftFft = 1024, kStftHop = 256, kStftBins = 513, kStftBinsPad = 528;
+struct StftWs {
+  float *re, *im;       // [T][528] transform of the model output
+  float *ymag, *ylog;   // [T][528] target magnitudes and their logs (constant: stft_forward(target))
+  float* dF;            // [T][1024] gradient of the frames
+  float* part;          // [8][npart] per-block partial sums
+  float* scal;          // [32] finished scalars (stft.hip SC_*)
+  float* gchain;        // [rows] dLoss/d(head linear output) of a last_linear=False step
+  int T, npart;
+};
+int64_t stft_frames(int64_t n);   // 1 + n / 256 (0: n <= 512, reflect padding undefined)
+int64_t stft_basis_floats();
+void stft_basis_fill(float* host);  // both tables, fp64 on the host rounded once
+int64_t stft_ws_floats(int n, int rows);
+StftWs stft_ws_map(float* ws, int n, int rows);
+// target: ymag, ylog and scal[Sy]; else re, im and the partials of S1 and sum|dlog|
+hipError_t stft_forward(const float* x, int n, const float* basis, const StftWs& w, bool target, hipStream_t s);
+// partials of the means, then of sum yc^2 and sum (xc - yc)^2
+hipError_t snr_sums(const float* x, const float* y, int n, const StftWs& w, hipStream_t s);
+// the finished scalars; loss_mode 0 / 1: point loss = sum(sse_part) / n_total, 2: L_snr, -1: none
+// (loss = L_stft); stft: the partials of stft_forward are reduced; loss_out (nullable) <- the mixed loss
+hipError_t loss_finish(const StftWs& w, int n, const float* sse_part, int nsum, int loss_mode, double alpha,
+                       double n_total, bool stft, float* loss_out, hipStream_t s);
+hipError_t stft_backward(const float* basis, const StftWs& w, hipStream_t s);   // -> w.dF
+hipError_t stft_gather(int n, const StftWs& w, float* g_stft, hipStream_t s);  // dF -> dL_stft/dx [n]
+// g[rows] = (1 - alpha) g_point + alpha gather(dF), 0 on pad rows
+hipError_t loss_mix(const float* out, const float* y, int n, int rows, const StftWs& w, int loss_mode, double alpha,
+                    float gfac, float* g, hipStream_t s);
+
 // KAN (kan.hip): fp32, grid_size 5, spline_order 3 (9 A-columns per input)
 // fused layer kernels (the bases are recomputed in LDS; A and dA never reach HBM)
 hipError_t kan_fwd_fused(const float* X, const float* grid, const float* W, int64_t N, int in, int out, float* Y,

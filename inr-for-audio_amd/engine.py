@@ -239,7 +239,16 @@ def cast_shadows(spec, Ws, Whs, WThs, stream):
               "siren_cast_weight")
 
 
-LOSS_MODES = {"mse": 0, "mae": 1}   # run.py:161-169 (MSELoss / L1Loss)
+LOSS_MODES = {"mse": 0, "mae": 1, "snr": 2}   # run.py:161-169 (MSELoss / L1Loss / auraloss SNRLoss)
+
+
+def stft_basis(device) -> torch.Tensor:
+    """The STFT loss's windowed cos / -sin tables (include/siren_hip.h "STFT and SNR losses"): computed
+    by the library in fp64 on the host, rounded to fp32 once, copied to `device`."""
+    lib = _lib.load()
+    host = torch.empty(int(lib.siren_stft_basis_floats()), dtype=torch.float32)
+    check(lib.siren_stft_basis_fill(host.data_ptr()), "siren_stft_basis_fill")
+    return host.to(device)
 
 
 def new_guard(device) -> torch.Tensor:
@@ -277,14 +286,37 @@ class SirenEngine:
     def __init__(self, model, coords: torch.Tensor, target: torch.Tensor, *, lr: float = 1e-3,
                  min_lr: float = 1e-6, factor: float = 0.8, patience: int = 200,
                  n_total: int | None = None, micro_batch: int = 1 << 20, hist_cap: int = 20000,
-                 splits: int | None = None, device=None, loss_mode: str = "mse", encoding=None):
+                 splits: int | None = None, device=None, loss_mode: str = "mse", encoding=None,
+                 alpha: float = 0.0):
         """`encoding` (encoding.GaussianEncoding, run.py:141-144): `coords` stay the raw [N][1]
         coordinates and model.in_features must be 2 * encoded_size -- the first layer's kernel
-        builds the encoded input itself (training and infer())."""
+        builds the encoded input itself (training and infer()).
+
+        `alpha` and loss_mode='snr' (run.py:126-128, :160-169): loss = (1 - alpha) {MSE | L1 | SNR} +
+        alpha L_stft, the two auraloss terms restated from their published definitions (csrc/stft.hip).
+        Both see the flattened signal as a whole, so such an engine takes one micro-batch on one rank
+        and more than 512 samples when alpha > 0; its last layer runs unfused."""
         lib = _lib.load()
         self.lib = lib
         if loss_mode not in LOSS_MODES:
             raise NotImplementedError(f"loss_mode={loss_mode!r}: the HIP path has {sorted(LOSS_MODES)}")
+        self.alpha = float(alpha)
+        if not 0.0 <= self.alpha <= 1.0:
+            raise ValueError(f"alpha={alpha!r} must be in [0, 1] (run.py:161-169 mixes (1 - alpha) and alpha)")
+        self.spectral = self.alpha != 0.0 or loss_mode == "snr"
+        if self.spectral:
+            n_sig = int(target.numel())
+            if _dist() is not None:
+                raise NotImplementedError("the STFT / SNR losses need the whole signal on one rank (frames and the "
+                                          "sums cross shard boundaries): no process group of more than one rank")
+            if n_total is not None and int(n_total) != n_sig:
+                raise NotImplementedError("the STFT / SNR losses need the whole signal (n_total == len(target))")
+            if n_sig > round_up(int(micro_batch), 2 * ROW_TILE):
+                raise NotImplementedError(f"the STFT / SNR losses need the whole signal in one micro-batch: "
+                                          f"{n_sig} samples > micro_batch={micro_batch}")
+            if self.alpha != 0.0 and n_sig <= 512:
+                raise ValueError(f"the STFT loss needs more than 512 samples (reflect padding of a 1024-point "
+                                 f"frame is undefined for {n_sig}; torch.stft refuses it too)")
         self.device = torch.device(device or "cuda")
         if self.device.type != "cuda":
             raise RuntimeError("SirenEngine runs on the GPU only (HIP kernels; no CPU fallback)")
@@ -387,7 +419,25 @@ class SirenEngine:
         self.graph = None
         if d is not None:
             self._setup_buckets()
+        self.stft_basis = self.stft_ws = None
+        if self.spectral:
+            self._setup_spectral()
         self._refresh_shadows()
+
+    def _setup_spectral(self):
+        """The STFT / SNR loss workspace of the (single) batch, the transform's tables and -- computed
+        once, they never change -- the target's magnitudes, their logs and Sy."""
+        lib, b, n, dev = self.lib, self.batches[0], self.n_local, self.device
+        assert self.n_micro == 1 and n == self.n_total
+        self.stft_ws = torch.zeros(int(lib.siren_stft_workspace_floats(n, self.rows)), dtype=torch.float32,
+                                   device=dev)
+        self.spectral_struct = sp = _lib.SirenSpectral()
+        sp.alpha, sp.stft_ws = self.alpha, ptr(self.stft_ws)
+        if self.alpha != 0.0:
+            self.stft_basis = stft_basis(dev)
+            sp.stft_basis = ptr(self.stft_basis)
+            check(lib.siren_stft_forward(ptr(self.target), n, self.rows, ptr(self.stft_basis), ptr(self.stft_ws), 1,
+                                         self._stream()), "siren_stft_forward")
 
     def _setup_buckets(self):
         """One bucket per layer (contiguous in the flat layout): the head (+ the SSE tail slot),
@@ -422,6 +472,11 @@ class SirenEngine:
     def _launch_grads(self):
         s = self._stream()
         for b in self.batches:
+            if self.spectral:   # run.py:160-169: the STFT / SNR step (one batch: the whole signal)
+                check(self.lib.siren_train_step_spectral(ctypes.byref(self.net), ctypes.byref(self.grad_struct),
+                                                         ctypes.byref(b), ctypes.byref(self.spectral_struct), s),
+                      "siren_train_step_spectral")
+                continue
             check(self.lib.siren_train_step(ctypes.byref(self.net), ctypes.byref(self.grad_struct),
                                             ctypes.byref(b), s), "siren_train_step")
         # every micro-batch's gmax_part now holds its launch's max|g| partials: from the next step on
@@ -436,7 +491,9 @@ class SirenEngine:
         check(self.lib.siren_apply_update(
             ctypes.byref(self.net), ptr(self.params), ptr(self.grads), ptr(self.exp_avg),
             ptr(self.exp_avg_sq), self.layout.n_params, self._Wp, self._Whp, self._WThp,
-            ptr(self.state), self.grads.data_ptr() + 4 * self.layout.sse_offset, float(self.n_total),
+            ptr(self.state), self.grads.data_ptr() + 4 * self.layout.sse_offset,
+            # an STFT / SNR step leaves the finished mixed loss in the sse slot, not a sum over N
+            1.0 if self.spectral else float(self.n_total),
             ptr(self.loss_hist), ptr(self.lr_hist), self.hist_cap, ptr(self.guard), self._stream()),
             "siren_apply_update")
 
@@ -632,8 +689,11 @@ class KanEngine(SirenEngine):
     def __init__(self, model, coords: torch.Tensor, target: torch.Tensor, *, lr: float = 1e-3,
                  min_lr: float = 1e-6, factor: float = 0.8, patience: int = 200,
                  n_total: int | None = None, micro_batch: int = 1 << 20, hist_cap: int = 20000,
-                 splits: int | None = None, device=None):
+                 splits: int | None = None, device=None, loss_mode: str = "mse", alpha: float = 0.0):
         from .kan import make_kan_grads
+        if loss_mode != "mse" or alpha != 0.0:
+            raise NotImplementedError("KanEngine is fitted with MSELoss only (no loss_mode 'mae' / 'snr', no STFT "
+                                      "term: alpha must be 0)")
         lib = _lib.load()
         self.lib = lib
         self.device = dev = torch.device(device or "cuda")

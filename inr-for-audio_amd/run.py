@@ -1,9 +1,13 @@
 """``train()`` with the reference's keyword API (run.py:30-400) on the HIP engine.
 
 Differences from the reference are limited to what the hot-path scope excludes: no plots
-(matplotlib figures), no loss-landscape, no STFT / auraloss-SNR loss terms (alpha must be 0 --
-at alpha=0 the reference's STFT term contributes exactly zero; loss_mode 'mse'
-and 'mae' (L1Loss, run.py:161-163) are fused on device, 'snr' needs auraloss).  ``num_freq=F``
+(matplotlib figures), no loss-landscape.  loss_mode 'mse' and 'mae' (L1Loss, run.py:161-163) at
+alpha=0 are fused on device (at alpha=0 the reference's STFT term contributes exactly zero, SURVEY
+§8 a8).  The reference's other loss options -- ``alpha > 0`` (auraloss.freq.STFTLoss, run.py:128,
+:160) and ``loss_mode='snr'`` (auraloss.time.SNRLoss, run.py:126, :165) -- are refused unless
+``restated_losses=True``: auraloss is not a dependency of this project, so those two terms are
+restated from their published 0.4.0 definitions (csrc/stft.hip) and parity is to that formula, not to
+an installed module; the switch makes that substitution explicit.  ``num_freq=F``
 puts the Gaussian random-Fourier-feature encoding of run.py:141-144 in front of the waveform MLP
 (encoding.GaussianEncoding; its b is saved in the checkpoint, which the reference forgets).
 ``multichannel=True`` (keyword-only) fits the (time,
@@ -78,12 +82,17 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
           last_linear=True, hidden_omega=30, a_initial=0.5, total_steps=20000, learning_rate=1e-3,
           min_learning_rate=1e-6, alpha=0.0, prev_ckpt_path=None, visualization=False, *,
           filename=None, data_dir="data", seed=None, micro_batch=1 << 20, use_graph=True,
-          device=None, verbose=False, multichannel=False, patience=200):
+          device=None, verbose=False, multichannel=False, patience=200, restated_losses=False):
     """Fit one clip; returns the checkpoint path (run.py:400).  Extra keyword-only knobs:
     ``filename`` (default ``{data_dir}/{inst}.wav`` as run.py:33), ``seed`` (torch.manual_seed
     before model construction), ``micro_batch`` (rows per fused micro-batch), ``use_graph``
     (replay each step as a HIP graph), ``device``, ``multichannel`` (the (t, ch) grid of
-    MultiWaveformFitting, run.py:59-63), ``patience`` (ReduceLROnPlateau, run.py:117's 200)."""
+    MultiWaveformFitting, run.py:59-63), ``patience`` (ReduceLROnPlateau, run.py:117's 200),
+    ``restated_losses`` (opt-in: fit with ``alpha > 0`` and / or ``loss_mode='snr'`` using this
+    project's restatement of auraloss's STFTLoss / SNRLoss defaults -- run.py:126-128, :160-169 --
+    instead of raising; parity is to the published formula, not to an installed auraloss.  For
+    method 'wave' and 'mdct' of the MLP, the whole signal in one micro-batch on one GPU; with 'snr'
+    the loss is negative, so the dB history is NaN as in the reference, run.py:180)."""
     if method not in ("wave", "mdct"):
         raise ValueError("specify the correct fitting method as wave or mdct (run.py:77-78)")
     if method == "mdct" and bwe:
@@ -92,8 +101,12 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         raise NotImplementedError(f"arch={arch!r}: the reference builds 'kan' or the MLP (run.py:92-96)")
     if arch == "kan" and method == "mdct":
         raise NotImplementedError("arch='kan' takes 1-D coordinates (run.py:92 builds KAN([1, H, H, 1]))")
-    if loss_mode not in ("mse", "mae") or alpha != 0.0:
-        raise NotImplementedError("HIP path implements loss_mode 'mse' / 'mae' with alpha=0 (run.py:161-169)")
+    spectral = loss_mode == "snr" or alpha != 0.0
+    if loss_mode not in ("mse", "mae", "snr") or (spectral and not restated_losses):
+        raise NotImplementedError("HIP path implements loss_mode 'mse' / 'mae' with alpha=0 (run.py:161-169); "
+                                  "restated_losses=True fits 'snr' and alpha > 0 with the restated auraloss terms")
+    if spectral and (multichannel or arch != "mlp"):
+        raise NotImplementedError("restated_losses fits the waveform / MDCT MLP (no multichannel, no arch='kan')")
     if arch == "kan" and loss_mode != "mse":
         raise NotImplementedError("arch='kan' is fitted with loss_mode='mse'")
     if multichannel and (method != "wave" or arch != "mlp" or bwe):
@@ -158,7 +171,7 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
 
     dev = torch.device(device or "cuda")
     Engine = KanEngine if arch == "kan" else SirenEngine
-    kw = {} if arch == "kan" else {"loss_mode": loss_mode, "encoding": encoding}
+    kw = {} if arch == "kan" else {"loss_mode": loss_mode, "encoding": encoding, "alpha": alpha}
     engine = Engine(model, model_input, ground_truth, lr=learning_rate, min_lr=min_learning_rate,
                     patience=patience, micro_batch=micro_batch, hist_cap=total_steps, device=dev, **kw)
     if ckpt is not None:
@@ -184,7 +197,8 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     total_time = (end_time - start_time) / 60
 
     raw_losses, raw_lrs = engine.history()
-    losses = 10 * np.log10(raw_losses.astype(np.float64) + 1e-10)   # run.py:180
+    with np.errstate(invalid="ignore"):  # 'snr': a negative loss gives NaN, as in the reference
+        losses = 10 * np.log10(raw_losses.astype(np.float64) + 1e-10)   # run.py:180
     lrs = 10 * np.log10(raw_lrs)                                     # run.py:190
     best_iter = int(np.argmin(raw_losses)) if len(raw_losses) else -1
 
