@@ -67,6 +67,35 @@ bool hidden_ok(int h) {
   return (h >= 128 && h % 128 == 0 && h <= 1024 && 256 % (h / 4) == 0) || (h > 1024 && h % 1024 == 0 && h <= SIREN_MAX_HIDDEN);
 }
 
+// a hidden-layer launch's shape: a kernel width and whole row tiles (the fused last layer: of 256 rows)
+bool rows_hidden_ok(int rows, int hidden, int row_mult = SIREN_ROW_TILE) {
+  return hidden_ok(hidden) && rows > 0 && rows % row_mult == 0;
+}
+
+// the square hidden-layer GEMM X [rows][hidden] x W [hidden][hidden]^T; the caller adds its mode's fields
+NtParams hidden_gemm(const h16* X, const h16* W, int rows, int hidden) {
+  NtParams p = {};
+  p.X = X;
+  p.W = W;
+  p.M = rows; p.N = hidden; p.K = hidden;
+  p.tile = nt_choose_tile(rows, hidden);
+  return p;
+}
+
+// 256-row bands: the sse / gsum / max|g| partials of head_loss and gmax_partials, one per band
+inline int bands(int rows) { return (rows + 255) / 256; }
+// head partials per row: one per tile column of the last layer's GEMM
+inline int head_parts(int rows, int hidden) { return hidden / nt_choose_tile(rows, hidden); }
+// mean backward: MSELoss 2 err / N, L1Loss sign(err) / N
+inline float loss_gfac(int loss_mode, double n_total) { return (float)((loss_mode == 1 ? 1.0 : 2.0) / n_total); }
+
+// the first micro-batch of a step clears the flat gradient vector (SIREN and KAN structs alike)
+template <class Grads, class Batch>
+hipError_t zero_grads(const Grads* gr, const Batch* b, hipStream_t s) {
+  if (!b->zero_grads || !gr->flat) return hipSuccess;
+  return hipMemsetAsync(gr->flat, 0, gr->flat_len * sizeof(float), s);
+}
+
 int check_net(const siren_net* n) {
   if (!n) return SIREN_ERR_NULL;
   if (n->in_dim < 1 || n->in_dim > 2) return SIREN_ERR_CONFIG;
@@ -94,6 +123,11 @@ float act_omega(const siren_net* n, int i) { return n->act[i] == SIREN_ACT_SINE 
 // bound of |dY/dz| of inner layer i (grad_scale headroom): omega, 2 (Snake), 1 (Tanh)
 float act_bound(const siren_net* n, int i) {
   return n->act[i] == SIREN_ACT_SINE ? n->omega : (n->act[i] == SIREN_ACT_SNAKE ? 2.0f : 1.0f);
+}
+// the backward storage scale of the last inner layer from the max|g| partials in b->gmax_part
+hipError_t last_grad_scale(const siren_net* n, const siren_batch* b, hipStream_t s) {
+  return grad_scale(b->gmax_part, bands(b->rows), n->w_head, n->hidden, act_bound(n, n->n_inner - 1), b->gscale, s,
+                    (const GuardState*)b->guard);
 }
 
 // run.py:160-169: a batch with an STFT term or the SNR loss takes the unfused step with the loss
@@ -189,11 +223,7 @@ hipError_t run_forward(const siren_net* n, siren_batch* b, hipStream_t s, bool h
     run = 0;
   };
   for (int i = 0; i < L; ++i) {
-    NtParams p = {};
-    p.X = B(b->Y[i]);
-    p.W = B(n->Wh[i]);
-    p.M = R; p.N = H; p.K = H;
-    p.tile = nt_choose_tile(R, H);
+    NtParams p = hidden_gemm(B(b->Y[i]), B(n->Wh[i]), R, H);
     p.omega = n->omega;
     p.bias = n->b[i];
     p.Y = B(b->Y[i + 1]);
@@ -295,8 +325,7 @@ int siren_forward(const siren_net* net, siren_batch* batch, void* stream) {
   hipStream_t s = S(stream);
   SIREN_TRY(run_forward(net, batch, s));
   // out = sum of head partials + bias (g/sse unused at inference: n_valid = 0 path)
-  SIREN_TRY(head_loss(batch->head_part, net->hidden / nt_choose_tile(batch->rows, net->hidden),
-                      batch->rows, net->b_head, batch->out,
+  SIREN_TRY(head_loss(batch->head_part, head_parts(batch->rows, net->hidden), batch->rows, net->b_head, batch->out,
                       0, 0.f, batch->out, batch->g, batch->sse_part, batch->gsum_part, nullptr, s,
                       net->head_omega));
   return SIREN_OK;
@@ -351,9 +380,7 @@ static int run_backward(const siren_net* net, const siren_grads* gr, siren_batch
   } else {
     const bool snake_last = net->act[L - 1] == SIREN_ACT_SNAKE;
     float* da_last = b->col_part + (int64_t)(R / 128) * H;  // second H-wide slab of col_part
-    SIREN_PROF(SIREN_PROF_HEAD, s, grad_scale(b->gmax_part, (R + 255) / 256, net->w_head, H,
-                                              act_bound(net, L - 1), b->gscale, s,
-                                              (const GuardState*)b->guard));
+    SIREN_PROF(SIREN_PROF_HEAD, s, last_grad_scale(net, b, s));
     SIREN_PROF(SIREN_PROF_HEAD, s, head_bwd(B(b->C[L]), B(b->Y[L]), b->g, net->w_head, act_omega(net, L - 1),
                                             R, H, b->gscale, B(b->dZ[0]), b->col_part, b->col_part2,
                                             snake_last ? B(b->E[L]) : nullptr, snake_last ? da_last : nullptr, s));
@@ -379,39 +406,33 @@ static int run_backward(const siren_net* net, const siren_grads* gr, siren_batch
                                                        b->gscale, s));
     SIREN_TRY(mark_ready(b, i, s));  // W_i now; b_i and a_i were reduced one stage earlier
 
-    NtParams p = {};
-    p.X = B(b->dZ[cur]);
-    p.W = B(net->WTh[i]);
-    p.M = R; p.N = H; p.K = H;
-    p.tile = ntile;
+    NtParams p = hidden_gemm(B(b->dZ[cur]), B(net->WTh[i]), R, H);
     p.colsum_part = b->col_part;
     p.gscale = b->gscale;
     p.tileq = b->tileq;  // used only with SIREN_OPT_NT_QUEUE 2
-    if (i > 0) {
-      const bool snake = net->act[i - 1] == SIREN_ACT_SNAKE;
-      p.omega = act_omega(net, i - 1);
+    if (i > 0 || net->rff_freq > 0) {
+      // dX into the layer below with the hidden-layer epilogue: inner layer i - 1, or (i == 0) the
+      // encoded first layer, where omega 1 stores C0 (dZ1 W1) S; omega0 (22000 by default: it would
+      // overflow fp16 at this S) enters in fp32 in rff_first_grads
+      const bool snake = i > 0 ? net->act[i - 1] == SIREN_ACT_SNAKE : net->first_snake != 0;
+      p.omega = i > 0 ? act_omega(net, i - 1) : 1.0f;
       p.Cprev = B(b->C[i]);
       p.Eprev = B(b->E[i]);
       p.dZ = B(b->dZ[cur ^ 1]);
-      SIREN_PROF(SIREN_PROF_BWD_DX, s, gemm_nt(snake ? NT_DX_SNAKE : NT_DX, false, p, s));
-      const int64_t rs = (int64_t)(snake ? 2 : 1) * H;
-      ColSegs sg = {};
-      seg_add(sg, b->col_part, gr->b[i - 1]);
-      if (snake) seg_add(sg, b->col_part + H, gr->a[i - 1]);
-      SIREN_PROF(SIREN_PROF_REDUCE, s, col_reduce_multi(sg, rs, prow, H, 1, b->red_tmp, s));
-      cur ^= 1;
-    } else if (net->rff_freq > 0) {
-      // encoded first layer: the hidden-layer dX epilogue with omega 1 stores C0 (dZ1 W1) S; omega0
-      // (22000 by default: it would overflow fp16 at this S) enters in fp32 in rff_first_grads
-      const bool fs = net->first_snake != 0;
-      p.omega = 1.0f;
-      p.Cprev = B(b->C[0]);
-      p.Eprev = B(b->E[0]);
-      p.dZ = B(b->dZ[cur ^ 1]);
-      SIREN_PROF(SIREN_PROF_BWD_DX0, s, gemm_nt(fs ? NT_DX_SNAKE : NT_DX, false, p, s));
-      SIREN_TRY(rff_first_grads(fs, net->omega0, net->rff_freq, R, H, prow, B(b->enc), B(b->dZ[cur ^ 1]), b->gscale,
-                                b->col_part, b->red_tmp, b->rff_slab, gr->W0, gr->b0, gr->a0, s));
-      SIREN_TRY(mark_ready(b, L, s));
+      SIREN_PROF(i > 0 ? SIREN_PROF_BWD_DX : SIREN_PROF_BWD_DX0, s,
+                 gemm_nt(snake ? NT_DX_SNAKE : NT_DX, false, p, s));
+      if (i > 0) {
+        const int64_t rs = (int64_t)(snake ? 2 : 1) * H;
+        ColSegs sg = {};
+        seg_add(sg, b->col_part, gr->b[i - 1]);
+        if (snake) seg_add(sg, b->col_part + H, gr->a[i - 1]);
+        SIREN_PROF(SIREN_PROF_REDUCE, s, col_reduce_multi(sg, rs, prow, H, 1, b->red_tmp, s));
+        cur ^= 1;
+      } else {
+        SIREN_TRY(rff_first_grads(snake, net->omega0, net->rff_freq, R, H, prow, B(b->enc), B(b->dZ[cur ^ 1]),
+                                  b->gscale, b->col_part, b->red_tmp, b->rff_slab, gr->W0, gr->b0, gr->a0, s));
+        SIREN_TRY(mark_ready(b, L, s));
+      }
     } else {
       const bool fs = net->first_snake != 0;
       p.omega = fs ? 1.0f : net->omega0;
@@ -433,6 +454,18 @@ static int run_backward(const siren_net* net, const siren_grads* gr, siren_batch
   return SIREN_OK;
 }
 
+// the backward from dLoss/dout in b->g, changed in place when last_linear=False chains it through
+// the final sin (head_part is the forward's)
+static int backward_from_g(const siren_net* net, const siren_grads* gr, siren_batch* b, hipStream_t s) {
+  const int R = b->rows;
+  if (net->head_omega > 0.f)
+    SIREN_TRY(head_sine_chain(b->head_part, head_parts(R, net->hidden), R, net->b_head, net->head_omega, b->g, s));
+  // bias of the head: sum of g; max |g| partials for the backward storage scale
+  SIREN_TRY(sum_to(b->g, R, gr->b_head, 1, s));
+  SIREN_TRY(gmax_partials(b->g, R, b->gmax_part, s));
+  return run_backward(net, gr, b, s);
+}
+
 // run.py:158-185 with an STFT term (alpha) or the SNR loss (run.py:126-128, :160-169).  The loss is
 // global -- every output sample feeds every gradient through 1024-point frames and the sums over the
 // whole signal -- so it cannot live in the fused last layer's epilogue: unfused forward and head_loss
@@ -440,18 +473,17 @@ static int run_backward(const siren_net* net, const siren_grads* gr, siren_batch
 // g = dLoss/dout exactly as siren_backward runs it.  gr->sse[0] receives the finished mixed loss.
 static int run_spectral_step(const siren_net* net, const siren_grads* gr, siren_batch* b,
                              const siren_spectral* sp, float gfac, hipStream_t s) {
-  const int R = b->rows, H = net->hidden, n = b->n_valid, nsum = (R + 255) / 256;
-  const int nparts = H / nt_choose_tile(R, H);
+  const int R = b->rows, n = b->n_valid;
   const bool stft = sp->alpha != 0.0;
   const StftWs w = stft_ws_map(sp->stft_ws, n, R);
   SIREN_TRY(run_forward(net, b, s));
   // out (through the final sine of last_linear=False) and the |err| / err^2 partials; its g is replaced
-  SIREN_PROF(SIREN_PROF_HEAD, s, head_loss(b->head_part, nparts, R, net->b_head, b->target, n, gfac, b->out, b->g,
-                                           b->sse_part, b->gsum_part, b->gmax_part, s, net->head_omega,
+  SIREN_PROF(SIREN_PROF_HEAD, s, head_loss(b->head_part, head_parts(R, net->hidden), R, net->b_head, b->target, n, gfac,
+                                           b->out, b->g, b->sse_part, b->gsum_part, b->gmax_part, s, net->head_omega,
                                            b->loss_mode == 1 ? 1 : 0));
   if (b->loss_mode == 2) SIREN_PROF(SIREN_PROF_LOSS, s, snr_sums(b->out, b->target, n, w, s));
   if (stft) SIREN_PROF(SIREN_PROF_LOSS, s, stft_forward(b->out, n, sp->stft_basis, w, false, s));
-  SIREN_PROF(SIREN_PROF_LOSS, s, loss_finish(w, n, b->sse_part, nsum, b->loss_mode, sp->alpha, b->n_total, stft,
+  SIREN_PROF(SIREN_PROF_LOSS, s, loss_finish(w, n, b->sse_part, bands(R), b->loss_mode, sp->alpha, b->n_total, stft,
                                              gr->sse, s));
   if (stft) SIREN_PROF(SIREN_PROF_LOSS, s, stft_backward(sp->stft_basis, w, s));
   SIREN_PROF(SIREN_PROF_LOSS, s, loss_mix(b->out, b->target, n, R, w, b->loss_mode, sp->alpha, gfac, b->g, s));
@@ -460,12 +492,9 @@ static int run_spectral_step(const siren_net* net, const siren_grads* gr, siren_
   siren_batch bb = *b;
   if (net->head_omega > 0.f) {
     SIREN_TRY(hipMemcpyAsync(w.gchain, b->g, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, s));
-    SIREN_TRY(head_sine_chain(b->head_part, nparts, R, net->b_head, net->head_omega, w.gchain, s));
     bb.g = w.gchain;
   }
-  SIREN_TRY(sum_to(bb.g, R, gr->b_head, 1, s));
-  SIREN_TRY(gmax_partials(bb.g, R, b->gmax_part, s));
-  return run_backward(net, gr, &bb, s);
+  return backward_from_g(net, gr, &bb, s);
 }
 
 static int train_step(const siren_net* net, const siren_grads* gr, siren_batch* b, const siren_spectral* sp,
@@ -478,10 +507,8 @@ static int train_step(const siren_net* net, const siren_grads* gr, siren_batch* 
   hipStream_t s = S(stream);
   const int R = b->rows, H = net->hidden;
 
-  if (b->zero_grads && gr->flat) SIREN_TRY(hipMemsetAsync(gr->flat, 0, gr->flat_len * sizeof(float), s));
-
-  // mean backward: MSELoss 2 err / N, L1Loss sign(err) / N
-  const float gfac = (float)((b->loss_mode == 1 ? 1.0 : 2.0) / b->n_total);
+  SIREN_TRY(zero_grads(gr, b, s));
+  const float gfac = loss_gfac(b->loss_mode, b->n_total);
   if (spectral(b, sp)) return run_spectral_step(net, gr, b, sp, gfac, s);
   const bool hb = head_fused(net, b, s);
   if (hb) {
@@ -489,13 +516,12 @@ static int train_step(const siren_net* net, const siren_grads* gr, siren_batch* 
     // (|Y_L| <= 1): from the bound of max|g| (elementwise.hip grad_scale_bound) instead of the
     // step's max|g|.  Snake: from the previous launch's max|g| partials in gmax_part (grad_scale,
     // the unfused path's own scale rule on last step's g)
-    const int L = net->n_inner, nv = b->n_valid, nyp = (nv + 255) / 256;
+    const int L = net->n_inner, nv = b->n_valid;
     if (net->act[L - 1] == SIREN_ACT_SNAKE) {
-      SIREN_PROF(SIREN_PROF_HEAD, s, grad_scale(b->gmax_part, (R + 255) / 256, net->w_head, H, act_bound(net, L - 1),
-                                                b->gscale, s, (const GuardState*)b->guard));
+      SIREN_PROF(SIREN_PROF_HEAD, s, last_grad_scale(net, b, s));
     } else {
       if (nv > 0) SIREN_PROF(SIREN_PROF_HEAD, s, gmax_partials(b->target, nv, b->gmax_part, s));
-      SIREN_PROF(SIREN_PROF_HEAD, s, grad_scale_bound(b->gmax_part, nyp, net->w_head, net->b_head, H, gfac,
+      SIREN_PROF(SIREN_PROF_HEAD, s, grad_scale_bound(b->gmax_part, bands(nv), net->w_head, net->b_head, H, gfac,
                                                       net->head_omega, b->loss_mode, act_bound(net, L - 1),
                                                       b->gscale, s, (const GuardState*)b->guard));
     }
@@ -503,13 +529,12 @@ static int train_step(const siren_net* net, const siren_grads* gr, siren_batch* 
   // ---- forward (models.py:388-394) + MSE / L1 (run.py:161-169) ----
   SIREN_TRY(run_forward(net, b, s, hb, gfac));
   if (!hb)
-    SIREN_PROF(SIREN_PROF_HEAD, s, head_loss(b->head_part, H / nt_choose_tile(R, H), R, net->b_head,
+    SIREN_PROF(SIREN_PROF_HEAD, s, head_loss(b->head_part, head_parts(R, H), R, net->b_head,
                                              b->target, b->n_valid, gfac, b->out, b->g, b->sse_part,
                                              b->gsum_part, b->gmax_part, s, net->head_omega, b->loss_mode));
-  const int nsum = (R + 255) / 256;
   // sse[1]: the fused hand-off's stall flag rides the gradient all-reduce with the sse (siren_grads.sse)
   const int* stall = (hb && b->guard) ? &((const GuardState*)b->guard)->stalls : nullptr;
-  SIREN_PROF(SIREN_PROF_REDUCE, s, sum_to2(b->sse_part, gr->sse, b->gsum_part, gr->b_head, nsum, 1, s, stall,
+  SIREN_PROF(SIREN_PROF_REDUCE, s, sum_to2(b->sse_part, gr->sse, b->gsum_part, gr->b_head, bands(R), 1, s, stall,
                                            gr->sse + 1));
   // ---- backward (autograd of run.py:185) ----
   return run_backward(net, gr, b, s, hb);
@@ -530,16 +555,8 @@ int siren_backward(const siren_net* net, const siren_grads* gr, siren_batch* b, 
   if (st) return st;
   if ((st = check_batch(net, b, true))) return st;
   if ((st = check_grads(net, gr))) return st;
-  hipStream_t s = S(stream);
-  if (b->zero_grads && gr->flat) SIREN_TRY(hipMemsetAsync(gr->flat, 0, gr->flat_len * sizeof(float), s));
-  // last_linear=False: chain dLoss/dout through the final sin (head_part is the forward's)
-  if (net->head_omega > 0.f)
-    SIREN_TRY(head_sine_chain(b->head_part, net->hidden / nt_choose_tile(b->rows, net->hidden), b->rows,
-                              net->b_head, net->head_omega, b->g, s));
-  // bias of the head: sum of g; max |g| partials for the backward storage scale
-  SIREN_TRY(sum_to(b->g, b->rows, gr->b_head, 1, s));
-  SIREN_TRY(gmax_partials(b->g, b->rows, b->gmax_part, s));
-  return run_backward(net, gr, b, s);
+  SIREN_TRY(zero_grads(gr, b, S(stream)));
+  return backward_from_g(net, gr, b, S(stream));
 }
 
 int siren_apply_update(const siren_net* net, float* params, const float* grads_flat, float* exp_avg,
@@ -598,15 +615,10 @@ int siren_first_fwd(const float* t, int32_t in_dim, const float* W0, const float
 int siren_inner_fwd(const uint16_t* X, const uint16_t* Wh, const float* b, float omega, int32_t rows,
                     int32_t hidden, uint16_t* Y, uint16_t* C, const float* head_w, float* head_part,
                     int32_t* tileq, void* stream) {
-  if (!X || !Wh || !b || !Y || !C) return SIREN_ERR_NULL;
-  if (!hidden_ok(hidden) || rows <= 0 || rows % SIREN_ROW_TILE) return SIREN_ERR_SHAPE;
-  if (head_w && !head_part) return SIREN_ERR_NULL;
-  NtParams p = {};
-  p.X = B(X); p.W = B(Wh); p.M = rows; p.N = hidden; p.K = hidden;
-  p.tile = nt_choose_tile(rows, hidden);
-  p.omega = omega; p.bias = b; p.Y = B(Y); p.C = B(C);
-  p.head_w = head_w; p.head_part = head_part; p.tileq = tileq;
-  return (int)gemm_nt(NT_FWD, head_w != nullptr, p, S(stream));
+  // the sine layer of siren_inner_fwd_act: its act test passes, the Snake test does not apply, and a
+  // and E are the fields this wrapper left zero, so statuses, their order and the launch are the same
+  return siren_inner_fwd_act(X, Wh, b, SIREN_ACT_SINE, omega, nullptr, rows, hidden, Y, C, nullptr, head_w, head_part,
+                             tileq, stream);
 }
 
 int siren_head_loss(const float* head_part, int32_t nparts, int32_t rows, const float* b_head,
@@ -615,7 +627,7 @@ int siren_head_loss(const float* head_part, int32_t nparts, int32_t rows, const 
   if (!head_part || !b_head || !out || !g || !sse_part || !gsum_part) return SIREN_ERR_NULL;
   if (n_valid > 0 && !y) return SIREN_ERR_NULL;
   if (rows <= 0 || nparts < 1 || n_valid > rows || n_total <= 0) return SIREN_ERR_SHAPE;
-  return (int)head_loss(head_part, nparts, rows, b_head, y, n_valid, (float)(2.0 / n_total), out, g,
+  return (int)head_loss(head_part, nparts, rows, b_head, y, n_valid, loss_gfac(0, n_total), out, g,
                         sse_part, gsum_part, gmax_part, S(stream));
 }
 
@@ -631,7 +643,7 @@ int siren_head_bwd(const uint16_t* C, const uint16_t* Y, const float* g, const f
                    float* db_part, float* dwh_part, const uint16_t* E, float* da_part, void* stream) {
   if (!C || !Y || !g || !w_head || !dZ || !db_part || !dwh_part) return SIREN_ERR_NULL;
   if (E && !da_part) return SIREN_ERR_NULL;
-  if (!hidden_ok(hidden) || rows <= 0 || rows % SIREN_ROW_TILE) return SIREN_ERR_SHAPE;
+  if (!rows_hidden_ok(rows, hidden)) return SIREN_ERR_SHAPE;
   return (int)head_bwd(B(C), B(Y), g, w_head, omega, rows, hidden, gscale, B(dZ), db_part, dwh_part,
                        B(E), da_part, S(stream));
 }
@@ -641,21 +653,12 @@ int siren_head_fused_fwd(const uint16_t* X, const uint16_t* Wh, const float* b, 
                          int32_t n_valid, double n_total, int32_t loss_mode, const float* gscale, float* head_part,
                          float* out, float* g, float* sse_part, float* gsum_part, uint16_t* dZ, float* part,
                          void* stream) {
-  if (!X || !Wh || !b || !w_head || !b_head || !gscale || !head_part || !out || !g || !sse_part || !gsum_part ||
-      !dZ || !part || (n_valid > 0 && !y))
-    return SIREN_ERR_NULL;
-  if (!hidden_ok(hidden) || rows <= 0 || rows % 256 || n_valid < 0 || n_valid > rows || !(n_total > 0))
-    return SIREN_ERR_SHAPE;
-  if (loss_mode < 0 || loss_mode > 1 || !(head_omega >= 0.f)) return SIREN_ERR_CONFIG;
-  if (!gemm_nt_head_fusable(rows, hidden, S(stream))) return SIREN_ERR_CONFIG;
-  NtParams p = {};
-  p.X = B(X); p.W = B(Wh); p.M = rows; p.N = hidden; p.K = hidden;
-  p.tile = nt_choose_tile(rows, hidden);
-  p.omega = omega; p.bias = b; p.head_w = w_head; p.head_part = head_part;
-  p.target = y; p.b_head = b_head; p.out = out; p.g = g; p.sse_part = sse_part; p.gsum_part = gsum_part;
-  p.n_valid = n_valid; p.loss_mode = loss_mode; p.gfac = (float)((loss_mode == 1 ? 1.0 : 2.0) / n_total);
-  p.head_omega = head_omega; p.gscale = gscale; p.dZ = B(dZ); p.colsum_part = part;
-  return (int)gemm_nt(NT_FWD_HB, true, p, S(stream));
+  // the sine last layer of siren_head_fused_fwd_act: the Snake clause of its NULL test and its act
+  // test never fire, hb_mode(SINE) is NT_FWD_HB (gemm_nt_head_fusable's default mode), and a, E and
+  // gmax_part are the fields this wrapper left zero, so statuses, their order and the launch are the same
+  return siren_head_fused_fwd_act(X, Wh, b, SIREN_ACT_SINE, omega, nullptr, rows, hidden, w_head, b_head, head_omega, y,
+                                  n_valid, n_total, loss_mode, gscale, head_part, out, g, sse_part, gsum_part, nullptr,
+                                  dZ, part, nullptr, stream);
 }
 
 int siren_head_fused_fwd_act(const uint16_t* X, const uint16_t* Wh, const float* b, int32_t act, float omega,
@@ -667,18 +670,15 @@ int siren_head_fused_fwd_act(const uint16_t* X, const uint16_t* Wh, const float*
   if (!X || !Wh || !b || !w_head || !b_head || !gscale || !head_part || !out || !g || !sse_part || !gsum_part ||
       !dZ || !part || (n_valid > 0 && !y) || (act == SIREN_ACT_SNAKE && (!a || !E)))
     return SIREN_ERR_NULL;
-  if (!hidden_ok(hidden) || rows <= 0 || rows % 256 || n_valid < 0 || n_valid > rows || !(n_total > 0))
-    return SIREN_ERR_SHAPE;
+  if (!rows_hidden_ok(rows, hidden, 256) || n_valid < 0 || n_valid > rows || !(n_total > 0)) return SIREN_ERR_SHAPE;
   if (act < SIREN_ACT_SINE || act > SIREN_ACT_TANH || loss_mode < 0 || loss_mode > 1 || !(head_omega >= 0.f))
     return SIREN_ERR_CONFIG;
   if (!gemm_nt_head_fusable(rows, hidden, S(stream), hb_mode(act))) return SIREN_ERR_CONFIG;
-  NtParams p = {};
-  p.X = B(X); p.W = B(Wh); p.M = rows; p.N = hidden; p.K = hidden;
-  p.tile = nt_choose_tile(rows, hidden);
+  NtParams p = hidden_gemm(B(X), B(Wh), rows, hidden);
   p.omega = omega; p.bias = b; p.act_a = a; p.head_w = w_head; p.head_part = head_part;
   p.target = y; p.b_head = b_head; p.out = out; p.g = g; p.sse_part = sse_part; p.gsum_part = gsum_part;
   p.gmax_part = gmax_part;
-  p.n_valid = n_valid; p.loss_mode = loss_mode; p.gfac = (float)((loss_mode == 1 ? 1.0 : 2.0) / n_total);
+  p.n_valid = n_valid; p.loss_mode = loss_mode; p.gfac = loss_gfac(loss_mode, n_total);
   p.head_omega = head_omega; p.gscale = gscale; p.dZ = B(dZ); p.colsum_part = part; p.E = B(E);
   return (int)gemm_nt(hb_mode(act), true, p, S(stream));
 }
@@ -691,9 +691,8 @@ int siren_grad_scale_bound(const float* y, int32_t n_valid, float* ymax_part, co
   if (loss_mode < 0 || loss_mode > 1) return SIREN_ERR_CONFIG;
   hipStream_t s = S(stream);
   if (n_valid > 0) SIREN_TRY(gmax_partials(y, n_valid, ymax_part, s));
-  return (int)grad_scale_bound(ymax_part, (n_valid + 255) / 256, w_head, b_head, hidden,
-                               (float)((loss_mode == 1 ? 1.0 : 2.0) / n_total), head_omega, loss_mode, act_bound,
-                               gscale, s);
+  return (int)grad_scale_bound(ymax_part, bands(n_valid), w_head, b_head, hidden, loss_gfac(loss_mode, n_total),
+                               head_omega, loss_mode, act_bound, gscale, s);
 }
 
 int siren_inner_fwd_act(const uint16_t* X, const uint16_t* Wh, const float* b, int32_t act,
@@ -703,11 +702,9 @@ int siren_inner_fwd_act(const uint16_t* X, const uint16_t* Wh, const float* b, i
   if (!X || !Wh || !b || !Y || !C) return SIREN_ERR_NULL;
   if (act < SIREN_ACT_SINE || act > SIREN_ACT_TANH) return SIREN_ERR_CONFIG;
   if (act == SIREN_ACT_SNAKE && (!a || !E)) return SIREN_ERR_NULL;
-  if (!hidden_ok(hidden) || rows <= 0 || rows % SIREN_ROW_TILE) return SIREN_ERR_SHAPE;
+  if (!rows_hidden_ok(rows, hidden)) return SIREN_ERR_SHAPE;
   if (head_w && !head_part) return SIREN_ERR_NULL;
-  NtParams p = {};
-  p.X = B(X); p.W = B(Wh); p.M = rows; p.N = hidden; p.K = hidden;
-  p.tile = nt_choose_tile(rows, hidden);
+  NtParams p = hidden_gemm(B(X), B(Wh), rows, hidden);
   p.omega = omega; p.bias = b; p.Y = B(Y); p.C = B(C); p.E = B(E); p.act_a = a;
   p.head_w = head_w; p.head_part = head_part; p.tileq = tileq;
   return (int)gemm_nt(fwd_mode(act), head_w != nullptr, p, S(stream));
@@ -720,10 +717,8 @@ int siren_inner_bwd_dx_act(const uint16_t* dZ, const uint16_t* WTh, const uint16
   if (!dZ || !WTh || !Cprev || !dZprev || !part) return SIREN_ERR_NULL;
   if (act_prev < SIREN_ACT_SINE || act_prev > SIREN_ACT_TANH) return SIREN_ERR_CONFIG;
   if (act_prev == SIREN_ACT_SNAKE && !Eprev) return SIREN_ERR_NULL;
-  if (!hidden_ok(hidden) || rows <= 0 || rows % SIREN_ROW_TILE) return SIREN_ERR_SHAPE;
-  NtParams p = {};
-  p.X = B(dZ); p.W = B(WTh); p.M = rows; p.N = hidden; p.K = hidden;
-  p.tile = nt_choose_tile(rows, hidden);
+  if (!rows_hidden_ok(rows, hidden)) return SIREN_ERR_SHAPE;
+  NtParams p = hidden_gemm(B(dZ), B(WTh), rows, hidden);
   p.omega = act_prev == SIREN_ACT_SINE ? omega_prev : 1.0f;
   p.Cprev = B(Cprev); p.Eprev = B(Eprev); p.dZ = B(dZprev); p.colsum_part = part;
   p.gscale = gscale;
@@ -733,14 +728,11 @@ int siren_inner_bwd_dx_act(const uint16_t* dZ, const uint16_t* WTh, const uint16
 int siren_inner_bwd_dx(const uint16_t* dZ, const uint16_t* WTh, const uint16_t* Cprev, float omega_prev,
                        int32_t rows, int32_t hidden, const float* gscale, uint16_t* dZprev,
                        float* db_part, void* stream) {
-  if (!dZ || !WTh || !Cprev || !dZprev || !db_part) return SIREN_ERR_NULL;
-  if (!hidden_ok(hidden) || rows <= 0 || rows % SIREN_ROW_TILE) return SIREN_ERR_SHAPE;
-  NtParams p = {};
-  p.X = B(dZ); p.W = B(WTh); p.M = rows; p.N = hidden; p.K = hidden;
-  p.tile = nt_choose_tile(rows, hidden);
-  p.omega = omega_prev; p.Cprev = B(Cprev); p.dZ = B(dZprev); p.colsum_part = db_part;
-  p.gscale = gscale;
-  return (int)gemm_nt(NT_DX, false, p, S(stream));
+  // a sine layer below in siren_inner_bwd_dx_act: its act test passes, the Snake test does not apply,
+  // omega is omega_prev, the mode NT_DX and Eprev the field this wrapper left zero, so statuses, their
+  // order and the launch are the same
+  return siren_inner_bwd_dx_act(dZ, WTh, Cprev, nullptr, SIREN_ACT_SINE, omega_prev, rows, hidden, gscale, dZprev,
+                                db_part, stream);
 }
 
 int siren_first_bwd_dx(const uint16_t* dZ1, const uint16_t* WTh1, const uint16_t* C0, const float* t,
@@ -748,10 +740,8 @@ int siren_first_bwd_dx(const uint16_t* dZ1, const uint16_t* WTh1, const uint16_t
                        float* part, void* stream) {
   if (!dZ1 || !WTh1 || !C0 || !t || !part) return SIREN_ERR_NULL;
   if (in_dim < 1 || in_dim > 2) return SIREN_ERR_CONFIG;
-  if (!hidden_ok(hidden) || rows <= 0 || rows % SIREN_ROW_TILE) return SIREN_ERR_SHAPE;
-  NtParams p = {};
-  p.X = B(dZ1); p.W = B(WTh1); p.M = rows; p.N = hidden; p.K = hidden;
-  p.tile = nt_choose_tile(rows, hidden);
+  if (!rows_hidden_ok(rows, hidden)) return SIREN_ERR_SHAPE;
+  NtParams p = hidden_gemm(B(dZ1), B(WTh1), rows, hidden);
   p.omega = omega0; p.Cprev = B(C0); p.t = t; p.in_dim = in_dim; p.colsum_part = part;
   p.gscale = gscale;
   return (int)gemm_nt(NT_DX0, false, p, S(stream));
@@ -763,7 +753,7 @@ static bool rff_freq_ok(int32_t f) { return f >= 1 && f <= kRffMaxFreq; }
 int32_t siren_rff_kpad(int32_t rff_freq) { return rff_freq_ok(rff_freq) ? rff_kpad(rff_freq) : 0; }
 
 int64_t siren_rff_slab_floats(int32_t rows, int32_t hidden, int32_t rff_freq) {
-  if (!rff_freq_ok(rff_freq) || !hidden_ok(hidden) || rows <= 0 || rows % SIREN_ROW_TILE) return 0;
+  if (!rff_freq_ok(rff_freq) || !rows_hidden_ok(rows, hidden)) return 0;
   return rff_slab_floats(rows, hidden, rff_freq);
 }
 
@@ -779,7 +769,7 @@ int siren_rff_first_fwd(const float* x, const float* Bf, int32_t rff_freq, const
                         uint16_t* E0, uint16_t* enc, void* stream) {
   if (!rff_freq_ok(rff_freq)) return SIREN_ERR_CONFIG;
   if (!x || !Bf || !W0 || !b0 || !Y0 || !C0 || (a && !E0)) return SIREN_ERR_NULL;
-  if (!hidden_ok(hidden) || rows <= 0 || rows % SIREN_ROW_TILE) return SIREN_ERR_SHAPE;
+  if (!rows_hidden_ok(rows, hidden)) return SIREN_ERR_SHAPE;
   return (int)rff_first_fwd(x, Bf, rff_freq, W0, b0, omega0, rows, hidden, B(Y0), B(C0), a, a ? B(E0) : nullptr,
                             B(enc), S(stream));
 }
@@ -792,13 +782,11 @@ int siren_rff_first_bwd(const uint16_t* dZ1, const uint16_t* WTh1, const uint16_
   if (!dZ1 || !WTh1 || !C0 || !x || !Bf || !dZ0 || !enc || !part || !red_tmp || !slab || !gW0 || !gb0 ||
       (E0 && !ga0))
     return SIREN_ERR_NULL;
-  if (!hidden_ok(hidden) || rows <= 0 || rows % SIREN_ROW_TILE) return SIREN_ERR_SHAPE;
+  if (!rows_hidden_ok(rows, hidden)) return SIREN_ERR_SHAPE;
   hipStream_t s = S(stream);
   const bool fs = E0 != nullptr;
   SIREN_TRY(rff_encode16(x, Bf, rff_freq, rows, B(enc), s));
-  NtParams p = {};
-  p.X = B(dZ1); p.W = B(WTh1); p.M = rows; p.N = hidden; p.K = hidden;
-  p.tile = nt_choose_tile(rows, hidden);
+  NtParams p = hidden_gemm(B(dZ1), B(WTh1), rows, hidden);
   p.omega = 1.0f; p.Cprev = B(C0); p.Eprev = B(E0); p.dZ = B(dZ0); p.colsum_part = part;
   p.gscale = gscale;
   SIREN_TRY(gemm_nt(fs ? NT_DX_SNAKE : NT_DX, false, p, s));
@@ -874,7 +862,7 @@ int siren_snr_loss(const float* x, const float* y, int32_t n, int32_t rows, floa
 int siren_inner_bwd_dw(const uint16_t* Y, const uint16_t* dZ, int32_t rows, int32_t hidden,
                        int32_t splits, int32_t tile, float* slab, void* stream) {
   if (!Y || !dZ || !slab) return SIREN_ERR_NULL;
-  if (!hidden_ok(hidden) || rows <= 0 || rows % 64 || splits < 1) return SIREN_ERR_SHAPE;
+  if (!rows_hidden_ok(rows, hidden, 64) || splits < 1) return SIREN_ERR_SHAPE;
   if (tile != 0 && tile != 128 && tile != 256) return SIREN_ERR_CONFIG;
   TnParams p = {};
   p.Y = B(Y); p.dZ = B(dZ); p.R = rows; p.Hin = hidden; p.Hout = hidden; p.splits = splits;
@@ -1198,13 +1186,13 @@ int siren_kan_train_step(const siren_kan_net* net, const siren_kan_grads* gr, si
   hipStream_t s = S(stream);
   const int64_t R = b->rows;
   const KanWs w = kan_layout(net, R, b->splits, b->ws);
-  if (b->zero_grads && gr->flat) SIREN_TRY(hipMemsetAsync(gr->flat, 0, gr->flat_len * sizeof(float), s));
+  SIREN_TRY(zero_grads(gr, b, s));
   SIREN_TRY(hipMemsetAsync(w.zero, 0, sizeof(float), s));
   const int L = net->n_layers;
   // a last layer of width in <= 64 after a hidden layer runs its forward, the MSE gradient and its
   // backward in one pass (kan_head_train); otherwise forward, head_loss, backward
   const bool head_train = L > 1 && net->width[L - 1] <= 64;
-  const float gfac = (float)(2.0 / b->n_total);
+  const float gfac = loss_gfac(0, b->n_total);
   const float* G = b->g;
   int cur = 0, l_top = L - 1;
   if (head_train) {
@@ -1245,7 +1233,7 @@ int siren_kan_backward(const siren_kan_net* net, const siren_kan_grads* gr, sire
     if (!gr->base_w[l] || !gr->spline_w[l] || !gr->scaler[l]) return SIREN_ERR_NULL;
   hipStream_t s = S(stream);
   const KanWs w = kan_layout(net, b->rows, b->splits, b->ws);
-  if (b->zero_grads && gr->flat) SIREN_TRY(hipMemsetAsync(gr->flat, 0, gr->flat_len * sizeof(float), s));
+  SIREN_TRY(zero_grads(gr, b, s));
   SIREN_TRY(kan_run_backward(net, gr, b, w, s, b->g, net->n_layers - 1, 0, grad_coords));
   return SIREN_OK;
 }

@@ -13,6 +13,9 @@ forward, MSELoss, backward, Adam, ReduceLROnPlateau.  The engine owns
 * the optimizer / scheduler state as a device struct, so a step needs no host sync and
   can be captured in a HIP graph.
 
+FitEngine holds the flat vectors, the optimizer state and the step / graph / checkpoint methods;
+SirenEngine and KanEngine (the KAN variant, fp32 throughout) each add their net, workspace and launches.
+
 Data parallel: one process per GPU (torchrun), rank r owns the contiguous coordinate slice
 [r*N/G, (r+1)*N/G); the MSE gradient uses the GLOBAL N and the flat gradient vector (whose
 tail slot carries the summed squared error) is all-reduced once per step.
@@ -271,17 +274,221 @@ def shard_range(n_total: int, rank: int, world: int) -> tuple[int, int]:
     return n_total * rank // world, n_total * (rank + 1) // world
 
 
-class SirenEngine:
+def _opt_state_tensor(lr, min_lr, factor, patience, dev) -> torch.Tensor:
+    """siren_opt_state for torch.optim.Adam(lr) + ReduceLROnPlateau(min, factor, patience,
+    min_lr) with torch's defaults (run.py:116-117), as device bytes."""
+    st = SirenOptState()
+    st.lr, st.best, st.step = float(lr), math.inf, 0.0
+    st.num_bad, st.last_epoch = 0, 0
+    st.min_lr, st.factor, st.threshold, st.eps_lr = float(min_lr), float(factor), 1e-4, 1e-8
+    st.patience = int(patience)
+    st.beta1, st.beta2, st.eps = 0.9, 0.999, 1e-8
+    return torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(dev)
+
+
+class FitEngine:
+    """What SirenEngine and KanEngine share: the flat parameter / gradient / Adam vectors the model's
+    parameters are re-pointed at, the device optimizer + scheduler state with its loss / lr history,
+    this rank's coordinate shard, and the step, graph-capture, history and checkpoint methods.  An
+    engine adds its net and gradient structs, its workspace and batches, _launch_grads (every
+    micro-batch's gradients into `grads`, the summed loss into its tail slot), _launch_update (Adam +
+    ReduceLROnPlateau on the flat vectors) and infer."""
+
+    _buckets = None  # [(event index, lo, hi)] in completion order (SirenEngine, DP only)
+    # bench.py's exposed-communication measurement only: False skips the gradient all-reduce (the
+    # ranks' parameters then drift apart -- timing passes after the measured run, never training)
+    comm_enabled = True
+    guard = None  # the fp16 backward range guard (SirenEngine; KAN is fp32 throughout)
+
+    def __init__(self, device):
+        self.lib = _lib.load()
+        self.device = torch.device(device or "cuda")
+        if self.device.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} runs on the GPU only (HIP kernels; no CPU fallback)")
+        self.steps_done = 0
+        self.graph = None
+
+    def _setup_flat(self, model, pad=None):
+        """Flat fp32 parameter storage; module parameters become views into it (the model's own
+        blocks of the padded tensors when `pad` widens them).  Rank 0's values in a process group."""
+        self.layout = lay = ParamLayout(model, pad)
+        dev = self.device
+        self.params = torch.zeros(lay.flat_len, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            lay.fill_pads(self.params)
+            for i, (_, p) in enumerate(model.named_parameters()):
+                lay.true_view(self.params, i).copy_(p.detach().to(dev, torch.float32))
+        d = _dist()
+        if d is not None:
+            d.broadcast(self.params, src=0)
+        for i, (_, p) in enumerate(model.named_parameters()):
+            p.data = lay.true_view(self.params, i)
+        self.grads = torch.zeros_like(self.params)
+        self.exp_avg = torch.zeros_like(self.params)
+        self.exp_avg_sq = torch.zeros_like(self.params)
+
+    def _setup_opt(self, lr, min_lr, factor, patience, hist_cap):
+        """Optimizer + scheduler state (torch defaults of run.py:116-117) and the loss / lr history."""
+        dev = self.device
+        self.state = _opt_state_tensor(lr, min_lr, factor, patience, dev)
+        self.hist_cap = int(hist_cap)
+        self.loss_hist = torch.zeros(max(self.hist_cap, 1), dtype=torch.float32, device=dev)
+        self.lr_hist = torch.zeros(max(self.hist_cap, 1), dtype=torch.float64, device=dev)
+
+    def _shard(self, coords, target, in_dim, n_total):
+        """This rank's contiguous shard of the data as fp32 ([n][in_dim], [n]); sets n_total (the
+        global N of the loss) and n_local.  A caller that passes n_total has sharded already."""
+        coords = coords.reshape(-1, in_dim).to(torch.float32)
+        target = target.reshape(-1).to(torch.float32)
+        self.n_total = coords.shape[0] if n_total is None else int(n_total)
+        d = _dist()
+        if n_total is None and d is not None:
+            lo, hi = shard_range(self.n_total, d.get_rank(), d.get_world_size())
+            coords, target = coords[lo:hi], target[lo:hi]
+        self.n_local = coords.shape[0]
+        return coords, target
+
+    def _stream(self) -> int:
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _check_capture(self):
+        """capture_graph's hook for a launch configuration that the first step changes."""
+
+    # ------------------------------------------------------------------ public API
+    def step(self):
+        """One optimizer step over the full batch (all micro-batches, all ranks)."""
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._launch_grads()
+            d = _dist() if self.comm_enabled else None
+            if d is not None and self._buckets is not None:
+                # bucket k goes out as soon as the backward recorded grad_ready[k]
+                works = []
+                with torch.cuda.stream(self._comm):
+                    for k, lo, hi in self._buckets:
+                        self._comm.wait_event(self._events[k])
+                        works.append(d.all_reduce(self.grads[lo:hi], async_op=True))
+                for w in works:
+                    w.wait()
+                torch.cuda.current_stream(self.device).wait_stream(self._comm)
+            elif d is not None:
+                d.all_reduce(self.grads)
+            self._launch_update()
+        self.steps_done += 1
+
+    def capture_graph(self, warmup: int = 0):
+        """Capture one whole step as a HIP graph (single-process only).  The graph replays the
+        launch configuration of the capture (SirenEngine._check_capture)."""
+        if _dist() is not None:
+            raise RuntimeError("graph capture is for the single-GPU path")
+        for _ in range(warmup):
+            self.step()
+        self._check_capture()
+        torch.cuda.synchronize(self.device)
+        g = torch.cuda.CUDAGraph()
+        s = torch.cuda.Stream(self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(g, stream=s):
+                self._launch_grads()
+                self._launch_update()
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        self.graph = g
+        return g
+
+    def opt_state(self) -> SirenOptState:
+        return SirenOptState.from_buffer_copy(bytes(self.state.cpu().numpy().tobytes()))
+
+    def steps_applied(self) -> int:
+        """Optimizer steps taken by this engine (scheduler steps of this run); step() calls
+        minus the ones the fp16 range guard rejected and recomputed (synchronises).  Raises
+        SirenError if a fused last layer's hand-off timed out since the last clear_stalls()."""
+        self.guard_state()
+        return int(self.opt_state().last_epoch)
+
+    def guard_state(self) -> dict:
+        """{'headroom', 'overflows', 'clean', 'stalls'} of the fp16 backward range guard
+        (synchronises).  Raises SirenError when `stalls` is non-zero: a fused last layer's band
+        hand-off gave up waiting for a partner (include/siren_hip.h siren_guard), so that step's
+        loss and gradients were void and its update was skipped -- parameters and optimizer state
+        are those of before it.  clear_stalls() re-arms the guard."""
+        if self.guard is None:
+            return {"headroom": None, "overflows": 0, "clean": 0, "stalls": 0}
+        g = self.guard.cpu().tolist()
+        if g[5]:
+            raise _lib.SirenError(
+                f"fused last layer: {g[5]} hand-off wait(s) timed out (a band partner never published its "
+                "head partial -- CUs held by other work?); the step was voided and not applied. "
+                "Call clear_stalls() to train on, or set SIREN_OPT_HEAD_FUSE 0")
+        return {"headroom": g[1], "overflows": g[3], "clean": g[2], "stalls": g[5]}
+
+    def clear_stalls(self) -> None:
+        """Zero the guard's hand-off stall counter (after guard_state() raised)."""
+        self.guard[5] = 0
+
+    def run(self, steps: int) -> None:
+        """`steps` optimizer steps: step() calls, plus one more for each step the fp16 range
+        guard rejected (checked once at the end -- no per-step host synchronisation)."""
+        start = self.steps_applied()
+        for _ in range(steps):
+            self.step()
+        while self.steps_applied() - start < steps:
+            self.step()
+
+    def history(self):
+        """(losses, lrs) of the optimizer steps applied so far (host copies)."""
+        k = min(self.steps_applied(), self.hist_cap)
+        return self.loss_hist[:k].cpu().numpy(), self.lr_hist[:k].cpu().numpy()
+
+    def last_loss(self) -> float:
+        k = min(self.steps_applied(), self.hist_cap) - 1
+        return float(self.loss_hist[k].item()) if k >= 0 else float("nan")
+
+    def grad_views(self):
+        """The gradient of every parameter, in the model's own shapes (named_parameters order)."""
+        return [self.layout.true_view(self.grads, i) for i in range(len(self.layout.names))]
+
+    def adam_state_dict(self):
+        """torch.optim.Adam-compatible state_dict (run.py:359-362 checkpoint format)."""
+        st = self.opt_state()
+        state = {}
+        for i in range(len(self.layout.names)):
+            state[i] = {
+                "step": torch.tensor(float(st.step)),
+                "exp_avg": self.layout.true_view(self.exp_avg, i).detach().cpu().clone(),
+                "exp_avg_sq": self.layout.true_view(self.exp_avg_sq, i).detach().cpu().clone(),
+            }
+        group = {"lr": float(st.lr), "betas": (st.beta1, st.beta2), "eps": st.eps, "weight_decay": 0,
+                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
+                 "differentiable": False, "fused": None, "decoupled_weight_decay": False,
+                 "params": list(range(len(self.layout.names)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_adam_state_dict(self, sd):
+        """Resume from a reference checkpoint's optimizer_state_dict (run.py:104-105)."""
+        with torch.no_grad():
+            step = 0.0
+            for i in range(len(self.layout.names)):
+                s = sd["state"].get(i)
+                if s is None:
+                    continue
+                shp = self.layout.true_shapes[i]
+                self.layout.true_view(self.exp_avg, i).copy_(s["exp_avg"].reshape(shp))
+                self.layout.true_view(self.exp_avg_sq, i).copy_(s["exp_avg_sq"].reshape(shp))
+                step = float(s["step"])
+            st = self.opt_state()
+            st.step = step
+            st.lr = float(sd["param_groups"][0]["lr"])
+            self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(self.device))
+
+
+class SirenEngine(FitEngine):
     """Full-batch SIREN fit on one GPU (or one DP rank): run.py:108-190 minus the plots.
 
     Data parallel (torch.distributed initialised, world > 1): the gradients are all-reduced in
     per-layer buckets on a communication stream, each as soon as the backward has finalised it
     (siren_batch.grad_ready events), so RCCL runs under the remaining backward GEMMs."""
-
-    _buckets = None  # [(event index, lo, hi)] in completion order (DP only)
-    # bench.py's exposed-communication measurement only: False skips the gradient all-reduce (the
-    # ranks' parameters then drift apart -- timing passes after the measured run, never training)
-    comm_enabled = True
 
     def __init__(self, model, coords: torch.Tensor, target: torch.Tensor, *, lr: float = 1e-3,
                  min_lr: float = 1e-6, factor: float = 0.8, patience: int = 200,
@@ -296,8 +503,6 @@ class SirenEngine:
         alpha L_stft, the two auraloss terms restated from their published definitions (csrc/stft.hip).
         Both see the flattened signal as a whole, so such an engine takes one micro-batch on one rank
         and more than 512 samples when alpha > 0; its last layer runs unfused."""
-        lib = _lib.load()
-        self.lib = lib
         if loss_mode not in LOSS_MODES:
             raise NotImplementedError(f"loss_mode={loss_mode!r}: the HIP path has {sorted(LOSS_MODES)}")
         self.alpha = float(alpha)
@@ -317,30 +522,12 @@ class SirenEngine:
             if self.alpha != 0.0 and n_sig <= 512:
                 raise ValueError(f"the STFT loss needs more than 512 samples (reflect padding of a 1024-point "
                                  f"frame is undefined for {n_sig}; torch.stft refuses it too)")
-        self.device = torch.device(device or "cuda")
-        if self.device.type != "cuda":
-            raise RuntimeError("SirenEngine runs on the GPU only (HIP kernels; no CPU fallback)")
+        super().__init__(device)
         self.model = model
         self.encoding = encoding
         self.spec = spec = net_spec(model, encoding)
-        self.layout = lay = ParamLayout(model, model.hip_padding())
-        dev = self.device
-
-        # flat fp32 parameter storage; module parameters become views into it (the model's own
-        # blocks of the padded tensors when the hidden width is padded)
-        self.params = torch.zeros(lay.flat_len, dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            lay.fill_pads(self.params)
-            for i, (_, p) in enumerate(model.named_parameters()):
-                lay.true_view(self.params, i).copy_(p.detach().to(dev, torch.float32))
-        d = _dist()
-        if d is not None:
-            d.broadcast(self.params, src=0)
-        for i, (_, p) in enumerate(model.named_parameters()):
-            p.data = lay.true_view(self.params, i)
-        self.grads = torch.zeros_like(self.params)
-        self.exp_avg = torch.zeros_like(self.params)
-        self.exp_avg_sq = torch.zeros_like(self.params)
+        self._setup_flat(model, model.hip_padding())
+        lay, dev, d = self.layout, self.device, _dist()
 
         # the encoding's b (not trained): a device copy, rank 0's in a process group (each rank
         # draws its own otherwise), written back so that every rank's module holds the one in use
@@ -365,29 +552,11 @@ class SirenEngine:
         self._Wp = (ctypes.c_void_p * L)(*[ptr(w) for w in self.W])
         self._Whp = (ctypes.c_void_p * L)(*[ptr(w) for w in self.Wh])
         self._WThp = (ctypes.c_void_p * L)(*[ptr(w) for w in self.WTh])
-
-        # optimizer + scheduler state (torch defaults of run.py:116-117)
-        st = SirenOptState()
-        st.lr, st.best, st.step = float(lr), math.inf, 0.0
-        st.num_bad, st.last_epoch = 0, 0
-        st.min_lr, st.factor, st.threshold, st.eps_lr = float(min_lr), float(factor), 1e-4, 1e-8
-        st.patience = int(patience)
-        st.beta1, st.beta2, st.eps = 0.9, 0.999, 1e-8
-        self.state = torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(dev)
-        self.hist_cap = int(hist_cap)
-        self.loss_hist = torch.zeros(max(self.hist_cap, 1), dtype=torch.float32, device=dev)
-        self.lr_hist = torch.zeros(max(self.hist_cap, 1), dtype=torch.float64, device=dev)
+        self._setup_opt(lr, min_lr, factor, patience, hist_cap)
 
         # data: this rank's contiguous shard, padded per micro-batch
-        coords = coords.reshape(-1, spec.in_dim).to(torch.float32)
-        target = target.reshape(-1).to(torch.float32)
-        n_global = coords.shape[0] if n_total is None else int(n_total)
-        rank, world = (d.get_rank(), d.get_world_size()) if d is not None else (0, 1)
-        if n_total is None and world > 1:
-            lo, hi = shard_range(n_global, rank, world)
-            coords, target = coords[lo:hi], target[lo:hi]
-        self.n_total = n_global
-        self.n_local = n = coords.shape[0]
+        coords, target = self._shard(coords, target, spec.in_dim, n_total)
+        n, n_global = self.n_local, self.n_total
         # rows padded to 256 (pad rows carry g = 0): the 256x256 GEMM tiles need M % 256 == 0,
         # the 128-row minimum of the C-ABI would drop a 3.6 M-row shard to the 128x128 kernels
         mb = min(round_up(int(micro_batch), 2 * ROW_TILE), round_up(max(n, 1), 2 * ROW_TILE))
@@ -415,8 +584,6 @@ class SirenEngine:
                               guard=self.guard, loss_mode=LOSS_MODES[loss_mode])
             b.gmax_part = ptr(self._gmax[k])
             self.batches.append(b)
-        self.steps_done = 0
-        self.graph = None
         if d is not None:
             self._setup_buckets()
         self.stft_basis = self.stft_ws = None
@@ -463,9 +630,6 @@ class SirenEngine:
         self._buckets = order
 
     # ------------------------------------------------------------------ internals
-    def _stream(self) -> int:
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def _refresh_shadows(self):
         cast_shadows(self.spec, self.W, self.Wh, self.WTh, self._stream())
 
@@ -497,108 +661,15 @@ class SirenEngine:
             ptr(self.loss_hist), ptr(self.lr_hist), self.hist_cap, ptr(self.guard), self._stream()),
             "siren_apply_update")
 
-    # ------------------------------------------------------------------ public API
-    def step(self):
-        """One optimizer step over the full batch (all micro-batches, all ranks)."""
-        if self.graph is not None:
-            self.graph.replay()
-        else:
-            self._launch_grads()
-            d = _dist() if self.comm_enabled else None
-            if d is not None and self._buckets is not None:
-                # bucket k goes out as soon as the backward recorded grad_ready[k]
-                works = []
-                with torch.cuda.stream(self._comm):
-                    for k, lo, hi in self._buckets:
-                        self._comm.wait_event(self._events[k])
-                        works.append(d.all_reduce(self.grads[lo:hi], async_op=True))
-                for w in works:
-                    w.wait()
-                torch.cuda.current_stream(self.device).wait_stream(self._comm)
-            elif d is not None:
-                d.all_reduce(self.grads)
-            self._launch_update()
-        self.steps_done += 1
-
-    def capture_graph(self, warmup: int = 0):
-        """Capture one whole step as a HIP graph (single-process only).
-
-        The graph replays the launch configuration of the capture.  A stack whose last inner layer
-        is a Snake runs that layer fused with the head only once a step has run (its backward scale
-        comes from the previous launch's max|g|), so capturing before any step records the unfused
-        launches for the whole run: run one step first (warmup >= 1, or step() as run.train does);
-        this case warns."""
-        if _dist() is not None:
-            raise RuntimeError("graph capture is for the single-GPU path")
-        for _ in range(warmup):
-            self.step()
+    def _check_capture(self):
+        """A stack whose last inner layer is a Snake runs that layer fused with the head only once
+        a step has run (its backward scale comes from the previous launch's max|g|), so capturing
+        before any step records the unfused launches for the whole run: run one step first
+        (capture_graph's warmup >= 1, or step() as run.train does); this case warns."""
         if self.steps_done == 0 and self.spec.act(self.spec.n_inner - 1) == _lib.ACT_SNAKE:
             import warnings
             warnings.warn("capture_graph before any step: the Snake last layer is captured unfused "
-                          "(run one step first to capture the fused launch)", RuntimeWarning, stacklevel=2)
-        torch.cuda.synchronize(self.device)
-        g = torch.cuda.CUDAGraph()
-        s = torch.cuda.Stream(self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            with torch.cuda.graph(g, stream=s):
-                self._launch_grads()
-                self._launch_update()
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        self.graph = g
-        return g
-
-    def opt_state(self) -> SirenOptState:
-        return SirenOptState.from_buffer_copy(bytes(self.state.cpu().numpy().tobytes()))
-
-    def steps_applied(self) -> int:
-        """Optimizer steps taken by this engine (scheduler steps of this run); step() calls
-        minus the ones the fp16 range guard rejected and recomputed (synchronises).  Raises
-        SirenError if a fused last layer's hand-off timed out since the last clear_stalls()."""
-        self.guard_state()
-        return int(self.opt_state().last_epoch)
-
-    def guard_state(self) -> dict:
-        """{'headroom', 'overflows', 'clean', 'stalls'} of the fp16 backward range guard
-        (synchronises).  Raises SirenError when `stalls` is non-zero: a fused last layer's band
-        hand-off gave up waiting for a partner (include/siren_hip.h siren_guard), so that step's
-        loss and gradients were void and its update was skipped -- parameters and optimizer state
-        are those of before it.  clear_stalls() re-arms the guard."""
-        if getattr(self, "guard", None) is None:
-            return {"headroom": None, "overflows": 0, "clean": 0, "stalls": 0}
-        g = self.guard.cpu().tolist()
-        if g[5]:
-            raise _lib.SirenError(
-                f"fused last layer: {g[5]} hand-off wait(s) timed out (a band partner never published its "
-                "head partial -- CUs held by other work?); the step was voided and not applied. "
-                "Call clear_stalls() to train on, or set SIREN_OPT_HEAD_FUSE 0")
-        return {"headroom": g[1], "overflows": g[3], "clean": g[2], "stalls": g[5]}
-
-    def clear_stalls(self) -> None:
-        """Zero the guard's hand-off stall counter (after guard_state() raised)."""
-        self.guard[5] = 0
-
-    def run(self, steps: int) -> None:
-        """`steps` optimizer steps: step() calls, plus one more for each step the fp16 range
-        guard rejected (checked once at the end -- no per-step host synchronisation)."""
-        start = self.steps_applied()
-        for _ in range(steps):
-            self.step()
-        while self.steps_applied() - start < steps:
-            self.step()
-
-    def history(self):
-        """(losses, lrs) of the optimizer steps applied so far (host copies)."""
-        k = min(self.steps_applied(), self.hist_cap)
-        return self.loss_hist[:k].cpu().numpy(), self.lr_hist[:k].cpu().numpy()
-
-    def last_loss(self) -> float:
-        k = min(self.steps_applied(), self.hist_cap) - 1
-        return float(self.loss_hist[k].item()) if k >= 0 else float("nan")
-
-    def grad_views(self):
-        """The gradient of every parameter, in the model's own shapes (named_parameters order)."""
-        return [self.layout.true_view(self.grads, i) for i in range(len(self.layout.names))]
+                          "(run one step first to capture the fused launch)", RuntimeWarning, stacklevel=3)
 
     @torch.no_grad()
     def infer(self, coords: torch.Tensor, chunk: int | None = None) -> torch.Tensor:
@@ -609,39 +680,6 @@ class SirenEngine:
         ws = self.ws if round_up(chunk, ROW_TILE) == self.rows else None
         return forward_net(self.spec, self.net, coords.reshape(-1, self.spec.in_dim), self.device,
                            chunk, shadows_ready=True, ws=ws)
-
-    def adam_state_dict(self):
-        """torch.optim.Adam-compatible state_dict (run.py:359-362 checkpoint format)."""
-        st = self.opt_state()
-        state = {}
-        for i in range(len(self.layout.names)):
-            state[i] = {
-                "step": torch.tensor(float(st.step)),
-                "exp_avg": self.layout.true_view(self.exp_avg, i).detach().cpu().clone(),
-                "exp_avg_sq": self.layout.true_view(self.exp_avg_sq, i).detach().cpu().clone(),
-            }
-        group = {"lr": float(st.lr), "betas": (st.beta1, st.beta2), "eps": st.eps, "weight_decay": 0,
-                 "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
-                 "differentiable": False, "fused": None, "decoupled_weight_decay": False,
-                 "params": list(range(len(self.layout.names)))}
-        return {"state": state, "param_groups": [group]}
-
-    def load_adam_state_dict(self, sd):
-        """Resume from a reference checkpoint's optimizer_state_dict (run.py:104-105)."""
-        with torch.no_grad():
-            step = 0.0
-            for i in range(len(self.layout.names)):
-                s = sd["state"].get(i)
-                if s is None:
-                    continue
-                shp = self.layout.true_shapes[i]
-                self.layout.true_view(self.exp_avg, i).copy_(s["exp_avg"].reshape(shp))
-                self.layout.true_view(self.exp_avg_sq, i).copy_(s["exp_avg_sq"].reshape(shp))
-                step = float(s["step"])
-            st = self.opt_state()
-            st.step = step
-            st.lr = float(sd["param_groups"][0]["lr"])
-            self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(self.device))
 
 
 def forward_net(spec: NetSpec, net: SirenNet, coords: torch.Tensor, device, chunk: int,
@@ -668,23 +706,11 @@ def forward_net(spec: NetSpec, net: SirenNet, coords: torch.Tensor, device, chun
     return out
 
 
-def _opt_state_tensor(lr, min_lr, factor, patience, dev) -> torch.Tensor:
-    """siren_opt_state for torch.optim.Adam(lr) + ReduceLROnPlateau(min, factor, patience,
-    min_lr) with torch's defaults (run.py:116-117), as device bytes."""
-    st = SirenOptState()
-    st.lr, st.best, st.step = float(lr), math.inf, 0.0
-    st.num_bad, st.last_epoch = 0, 0
-    st.min_lr, st.factor, st.threshold, st.eps_lr = float(min_lr), float(factor), 1e-4, 1e-8
-    st.patience = int(patience)
-    st.beta1, st.beta2, st.eps = 0.9, 0.999, 1e-8
-    return torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(dev)
-
-
-class KanEngine(SirenEngine):
+class KanEngine(FitEngine):
     """Full-batch fit of the KAN variant (run.py:92-93 arch='kan') on the HIP
     path: siren_kan_train_step per micro-batch, gradient all-reduce across DP ranks, then the
-    same flat Adam + ReduceLROnPlateau kernels as the SIREN path.  Shares the optimizer,
-    history, checkpoint and graph-capture methods of SirenEngine."""
+    same flat Adam + ReduceLROnPlateau kernels as the SIREN path.  The optimizer, history,
+    checkpoint and graph-capture methods are FitEngine's; fp32 throughout, so no range guard."""
 
     def __init__(self, model, coords: torch.Tensor, target: torch.Tensor, *, lr: float = 1e-3,
                  min_lr: float = 1e-6, factor: float = 0.8, patience: int = 200,
@@ -694,47 +720,21 @@ class KanEngine(SirenEngine):
         if loss_mode != "mse" or alpha != 0.0:
             raise NotImplementedError("KanEngine is fitted with MSELoss only (no loss_mode 'mae' / 'snr', no STFT "
                                       "term: alpha must be 0)")
-        lib = _lib.load()
-        self.lib = lib
-        self.device = dev = torch.device(device or "cuda")
-        if dev.type != "cuda":
-            raise RuntimeError("KanEngine runs on the GPU only (HIP kernels; no CPU fallback)")
+        super().__init__(device)
+        lib, dev = self.lib, self.device
         model.hip_check()
         self.model = model.to(dev)
-        self.spec = None
-        self.layout = lay = ParamLayout(model)
-        self.params = torch.zeros(lay.flat_len, dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            for i, (_, p) in enumerate(model.named_parameters()):
-                lay.view(self.params, i).copy_(p.detach().to(dev, torch.float32))
-        d = _dist()
-        if d is not None:
-            d.broadcast(self.params, src=0)
-        for i, (_, p) in enumerate(model.named_parameters()):
-            p.data = lay.view(self.params, i)
-        self.grads = torch.zeros_like(self.params)
-        self.exp_avg = torch.zeros_like(self.params)
-        self.exp_avg_sq = torch.zeros_like(self.params)
+        self._setup_flat(model)
+        lay = self.layout
         views = [lay.view(self.params, i) for i in range(len(lay.names))]
         gviews = [lay.view(self.grads, i) for i in range(len(lay.names))]
         self.net = model.make_net(views)
         self.grad_struct = make_kan_grads(model, gviews, self.grads.data_ptr() + 4 * lay.sse_offset,
                                           self.grads, lay.flat_len)
-        self.state = _opt_state_tensor(lr, min_lr, factor, patience, dev)
-        self.hist_cap = int(hist_cap)
-        self.loss_hist = torch.zeros(max(self.hist_cap, 1), dtype=torch.float32, device=dev)
-        self.lr_hist = torch.zeros(max(self.hist_cap, 1), dtype=torch.float64, device=dev)
+        self._setup_opt(lr, min_lr, factor, patience, hist_cap)
 
-        in_dim = model.widths[0]
-        coords = coords.reshape(-1, in_dim).to(torch.float32)
-        target = target.reshape(-1).to(torch.float32)
-        n_global = coords.shape[0] if n_total is None else int(n_total)
-        rank, world = (d.get_rank(), d.get_world_size()) if d is not None else (0, 1)
-        if n_total is None and world > 1:
-            lo, hi = shard_range(n_global, rank, world)
-            coords, target = coords[lo:hi], target[lo:hi]
-        self.n_total = n_global
-        self.n_local = n = coords.shape[0]
+        coords, target = self._shard(coords, target, model.widths[0], n_total)
+        n, n_global = self.n_local, self.n_total
         self.rows = mb = max(1, min(int(micro_batch), n))
         self.n_micro = max(1, -(-n // mb))
         self.coords = coords.to(dev).contiguous()
@@ -756,11 +756,6 @@ class KanEngine(SirenEngine):
             b.coords, b.target = self.coords[lo:hi].data_ptr(), self.target[lo:hi].data_ptr()
             b.out, b.g, b.ws = ptr(self.out), ptr(self.g), ptr(self.ws)
             self.batches.append(b)
-        self.steps_done = 0
-        self.graph = None
-
-    def _refresh_shadows(self):
-        pass
 
     def _launch_grads(self):
         s = self._stream()

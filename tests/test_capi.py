@@ -105,6 +105,25 @@ def test_validation_without_device(lib):
     assert lib.siren_grad_scale_bound(None, 10, None, 1, 1, 256, 10.0, f(0), 0, f(30), 1, None) == 1002
     assert lib.siren_grad_scale_bound(1, -1, 1, 1, 1, 256, 10.0, f(0), 0, f(30), 1, None) == 1001
     assert lib.siren_grad_scale_bound(1, 10, 1, 1, 1, 256, 10.0, f(0), 3, f(30), 1, None) == 1003
+    # the plain wrappers are their _act counterparts at SINE: the same answers in the same order
+    SINE, SNAKE = 0, 1
+    FA = lambda act, a=None, rows=1024, hw=None, hp=None: lib.siren_inner_fwd_act(  # noqa: E731
+        1, 1, 1, act, f(30), a, rows, 256, 1, 1, None, hw, hp, None, None)
+    assert FA(3) == 1003
+    assert FA(SNAKE) == 1002                                                # a Snake needs its a
+    assert FA(SINE, rows=100) == 1001
+    assert FA(SINE, hw=1) == 1002                                           # head_w without head_part
+    F0 = lambda rows=1024, hw=None: lib.siren_inner_fwd(  # noqa: E731
+        1, 1, 1, f(30), rows, 256, 1, 1, hw, None, None, None)
+    assert F0(rows=100) == 1001
+    assert F0(hw=1) == 1002
+    assert lib.siren_inner_bwd_dx(1, 1, None, f(30), 1024, 256, 1, 1, 1, None) == 1002
+    assert lib.siren_inner_bwd_dx(1, 1, 1, f(30), 100, 256, 1, 1, 1, None) == 1001
+    DA = lambda act, e: lib.siren_inner_bwd_dx_act(1, 1, 1, e, act, f(30), 1024, 256, 1, 1, 1, None)  # noqa: E731
+    assert DA(3, 1) == 1003
+    assert DA(SNAKE, None) == 1002                                          # a Snake needs its Eprev
+    # CONFIG is tested before SHAPE
+    assert lib.siren_first_bwd_dx(1, 1, 1, 1, 3, f(30), 100, 256, 1, 1, None) == 1003
     b = SirenBatch()
     b.loss_mode = 7                                                          # not MSE / L1
     net.hidden = 256

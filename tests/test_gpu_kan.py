@@ -114,6 +114,27 @@ def test_kan_fit_tracks_reference(dev):
     assert np.array_equal(lrs, np.array(tr["lr"]))
 
 
+def test_kan_capture_graph_before_any_step(dev):
+    """KanEngine.capture_graph() with no step before it: the replayed steps are the eager ones bit for
+    bit (kan.hip has no atomics).  The eager engine runs first, so every kernel is loaded at capture.
+    Both models start from one state dict: KAN's least-squares init (torch.linalg.lstsq on the CPU) is
+    not bit-reproducible under one seed, so a second _kan() may differ in the last bit."""
+    from inr_for_audio_amd.engine import KanEngine
+    t, y = _data(2000)
+    ma, mb = _kan([1, 32, 32, 1]), _kan([1, 32, 32, 1])
+    mb.load_state_dict(ma.state_dict())
+    a = KanEngine(ma, torch.from_numpy(t), torch.from_numpy(y), device=dev)
+    for _ in range(4):
+        a.step()
+    b = KanEngine(mb, torch.from_numpy(t), torch.from_numpy(y), device=dev)
+    b.capture_graph()
+    for _ in range(4):
+        b.step()
+    assert torch.equal(a.params, b.params)
+    (la, ra), (lb, rb) = a.history(), b.history()
+    assert len(la) == 4 and np.array_equal(la, lb) and np.array_equal(ra, rb)
+
+
 def test_train_kan_end_to_end(dev, tmp_path):
     from inr_for_audio_amd.run import train
     g = np.load(os.path.join(G, "gt_bach_1s.npz"))
