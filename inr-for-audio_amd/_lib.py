@@ -6,7 +6,9 @@ compute path raises, so a GPU run can never silently degrade to eager PyTorch.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import enum
 import os
 
 import torch  # noqa: F401  -- load torch's HIP runtime first so the library binds to it
@@ -278,6 +280,51 @@ def check(status: int, what: str = "siren") -> None:
     if status != 0:
         msg = load().siren_status_string(status)
         raise SirenError(f"{what} failed with status {status}: {msg.decode() if msg else '?'}")
+
+
+class Opt(enum.IntEnum):
+    """enum siren_option (include/siren_hip.h): the process-global tuning knobs."""
+    NT_TILE = 0
+    TN_TILE = 1
+    NT_PIPE = 2
+    TN_PIPE = 3
+    NT_GRID = 4
+    NT_DIAG = 6
+    NT_QUEUE = 8
+    HEAD_FUSE = 9
+    HB_FAULT = 10
+
+
+# what a freshly loaded library holds (capi.hip's option table)
+OPT_DEFAULTS = {Opt.NT_TILE: 0, Opt.TN_TILE: 0, Opt.NT_PIPE: -1, Opt.TN_PIPE: -1, Opt.NT_GRID: 0,
+                Opt.NT_DIAG: 0, Opt.NT_QUEUE: 1, Opt.HEAD_FUSE: 1, Opt.HB_FAULT: 0}
+
+
+def _opt_shadow(lib) -> dict:
+    """The knob values `lib` holds.  The C-ABI has no getter, so each bound handle carries a shadow
+    that starts at OPT_DEFAULTS and that only set_option updates."""
+    return lib.__dict__.setdefault("_opt_shadow", dict(OPT_DEFAULTS))
+
+
+def set_option(lib, opt, value: int) -> None:
+    """siren_set_option(opt, value) on `lib`; raises SirenError when the library rejects it."""
+    opt = Opt(opt)
+    check(lib.siren_set_option(opt, value), f"siren_set_option({opt.name}, {value})")
+    _opt_shadow(lib)[opt] = value
+
+
+@contextlib.contextmanager
+def options(lib, values: dict):
+    """Set the given knobs {Opt.X: v, ...} for the body; on exit, by return or by exception, each
+    knob that was set goes back to the value it had on entry, in reverse order.  A value rejected
+    part-way puts the knobs already set back before the error propagates."""
+    shadow = _opt_shadow(lib)
+    with contextlib.ExitStack() as undo:
+        for opt, value in values.items():
+            before = shadow[Opt(opt)]
+            set_option(lib, opt, value)
+            undo.callback(set_option, lib, opt, before)
+        yield
 
 
 def ptr(t) -> int:

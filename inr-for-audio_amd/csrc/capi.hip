@@ -191,10 +191,9 @@ int hb_mode(int act) {
 // layer needs a backward scale before its forward that no bound gives tightly (|Y| is not bounded
 // by 1): it fuses only when the caller says gmax_part holds a previous launch's max|g| partials
 // (siren_batch.head_scale_prev); the range guard catches a step whose |g| outgrew that scale.
-int g_head_fuse = 1;
 bool head_fused(const siren_net* n, const siren_batch* b, hipStream_t s) {
   const int act = n->act[n->n_inner - 1];
-  if (!g_head_fuse || (act == SIREN_ACT_SNAKE && !b->head_scale_prev)) return false;
+  if (!tuning().head_fuse || (act == SIREN_ACT_SNAKE && !b->head_scale_prev)) return false;
   // the hand-off's timeout is only made loud through the guard's stall word: without a guard a
   // timed-out band would reach Adam as a NaN gradient, so a guard-less batch runs unfused
   if (!b->guard) return false;
@@ -944,39 +943,61 @@ int siren_fp32_linear_bwd(const float* x, int64_t rows, int32_t in, int32_t out,
   return (int)fp32_linear_bwd(x, rows, in, out, W, omega, gpre, gx, gW, gb, slab, splits, tmp, S(stream));
 }
 
+}  // extern "C"
+
+// ---- tuning knobs (siren_set_option) ------------------------------------------------------
+namespace {
+
+#ifdef SIREN_DIAG
+constexpr bool kDiagBuild = true;
+#else
+constexpr bool kDiagBuild = false;  // product builds carry no ablation and no fault injection
+#endif
+
+// One row per siren_option: where it lives, its default and the values it accepts.  Ids 5 and 7
+// (retired with their kernels) have no row, so they are rejected like any unknown id.
+struct OptionRow {
+  int id;
+  int Tuning::*member;
+  int def;
+  bool (*accepts)(int);
+  bool diag_only;  // a non-zero value is accepted only by SIREN_DIAG builds
+};
+bool tile_ok(int v) { return v == 0 || v == 128 || v == 256; }
+bool not_negative(int v) { return v >= 0; }
+const OptionRow kOptions[] = {
+    {SIREN_OPT_NT_TILE, &Tuning::nt_tile, 0, tile_ok, false},
+    {SIREN_OPT_TN_TILE, &Tuning::tn_tile, 0, tile_ok, false},
+    {SIREN_OPT_NT_PIPE, &Tuning::nt_pipe, -1, [](int v) { return v == -1 || v == 0 || v == 1 || (v >= 4 && v <= 7); }, false},
+    {SIREN_OPT_TN_PIPE, &Tuning::tn_pipe, -1, [](int v) { return v >= -1 && v <= 4; }, false},
+    {SIREN_OPT_NT_GRID, &Tuning::nt_grid, 0, not_negative, false},
+    {SIREN_OPT_NT_DIAG, &Tuning::nt_diag, 0, [](int v) { return v >= 0 && !(v & ~(1 | 4 | 8 | 512 | 1024 | 2048)); }, true},
+    {SIREN_OPT_NT_QUEUE, &Tuning::nt_queue, 1, [](int v) { return v >= 0 && v <= 2; }, false},
+    {SIREN_OPT_HEAD_FUSE, &Tuning::head_fuse, 1, [](int v) { return v == 0 || v == 1; }, false},
+    {SIREN_OPT_HB_FAULT, &Tuning::hb_fault, 0, not_negative, true},
+};
+
+Tuning default_tuning() {
+  Tuning t{};
+  for (const OptionRow& r : kOptions) t.*r.member = r.def;
+  return t;
+}
+
+}  // namespace
+
+Tuning& siren::tuning() {
+  static Tuning t = default_tuning();
+  return t;
+}
+
+extern "C" {
+
 int siren_set_option(int32_t option, int32_t value) {
-  switch (option) {
-    case SIREN_OPT_NT_TILE:
-    case SIREN_OPT_TN_TILE:
-      if (value != 0 && value != 128 && value != 256) return SIREN_ERR_CONFIG;
-      if (option == SIREN_OPT_NT_TILE) gemm_nt_set_tile(value);
-      else gemm_tn_set_tile(value);
-      return SIREN_OK;
-    case SIREN_OPT_NT_PIPE:
-      if (value != -1 && value != 0 && value != 1 && (value < 4 || value > 7)) return SIREN_ERR_CONFIG;
-      gemm_nt_set_pipe(value);
-      return SIREN_OK;
-    case SIREN_OPT_TN_PIPE:
-      if (value < -1 || value > 4) return SIREN_ERR_CONFIG;
-      gemm_tn_set_pipe(value);
-      return SIREN_OK;
-    case SIREN_OPT_NT_GRID:
-      if (value < 0) return SIREN_ERR_CONFIG;
-      gemm_nt_set_grid_cap(value);
-      return SIREN_OK;
-    case SIREN_OPT_NT_DIAG:
-      if (value < 0 || (value & ~(1 | 4 | 8 | 512 | 1024 | 2048))) return SIREN_ERR_CONFIG;
-      return gemm_nt_set_diag(value) ? SIREN_OK : SIREN_ERR_CONFIG;
-    case SIREN_OPT_NT_QUEUE:
-      if (value < 0 || value > 2) return SIREN_ERR_CONFIG;
-      gemm_nt_set_queue(value);
-      return SIREN_OK;
-    case SIREN_OPT_HEAD_FUSE:
-      if (value < 0 || value > 1) return SIREN_ERR_CONFIG;
-      g_head_fuse = value;
-      return SIREN_OK;
-    case SIREN_OPT_HB_FAULT:
-      return (value >= 0 && gemm_nt_set_hb_fault(value)) ? SIREN_OK : SIREN_ERR_CONFIG;
+  for (const OptionRow& r : kOptions) {
+    if (r.id != option) continue;
+    if (!r.accepts(value) || (r.diag_only && value && !kDiagBuild)) return SIREN_ERR_CONFIG;
+    tuning().*r.member = value;
+    return SIREN_OK;
   }
   return SIREN_ERR_CONFIG;
 }

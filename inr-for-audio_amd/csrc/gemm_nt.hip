@@ -1310,22 +1310,6 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_nt_kernel(NtParams p) {
 }
 
 static int g_num_cus[64] = {};
-static int g_nt_grid_cap = 0;  // test hook: persistent grid size (0 = one block per CU)
-void gemm_nt_set_grid_cap(int cap) { g_nt_grid_cap = cap; }
-static int g_nt_diag = 0;
-bool gemm_nt_set_diag(int bits) {
-  if (!SIREN_DIAG_ON && bits) return false;  // product builds carry no ablation
-  g_nt_diag = bits;
-  return true;
-}
-static int g_nt_queue = 1;  // 0 off, 1 forward modes, 2 every ping-pong mode
-void gemm_nt_set_queue(int v) { g_nt_queue = v; }
-static int g_hb_fault = 0;  // SIREN_OPT_HB_FAULT (SIREN_DIAG builds)
-bool gemm_nt_set_hb_fault(int v) {
-  if (!SIREN_DIAG_ON && v) return false;  // product builds carry no fault injection
-  g_hb_fault = v;
-  return true;
-}
 
 // CU count of the stream's device (queried once per device)
 static int stream_cus(hipStream_t s) {
@@ -1339,6 +1323,8 @@ static int stream_cus(hipStream_t s) {
   }
   return g_num_cus[dev];
 }
+// persistent grid size: SIREN_OPT_NT_GRID, or one block per CU
+static int nt_grid(hipStream_t s) { return tuning().nt_grid > 0 ? tuning().nt_grid : stream_cus(s); }
 
 // NT_FWD_HB co-residency: blocks per CU for the fused kernel x CUs >= grid (queried once per device)
 static int g_hb_per_cu[3][64] = {};
@@ -1349,13 +1335,13 @@ static hipError_t launch_nt(const NtParams& p_in, hipStream_t s, bool persistent
   // the static ping-pong schedule assumes an even number (>= 2) of K-tiles per tile
   if (Cfg::PP && (p_in.K % (2 * Cfg::BK) != 0 || !persistent)) return hipErrorInvalidValue;
   NtParams p = p_in;
-  p.diag = g_nt_diag;
+  p.diag = tuning().nt_diag;
   const int ntiles = (p.M / Cfg::BM) * (p.N / Cfg::BN);
-  const int cap = g_nt_grid_cap > 0 ? g_nt_grid_cap : stream_cus(s);
+  const int cap = nt_grid(s);
   const int grid = persistent ? (ntiles < cap ? ntiles : cap) : ntiles;
   // the queue's shards are blockIdx % 8: every shard must have blocks
   // (measured: the forward gains 3-4%; dX is unchanged and dX0 loses 2%, its K-loop spills)
-  const bool want = g_nt_queue == 2 || (g_nt_queue == 1 && nt_is_fwd(MODE));
+  const bool want = tuning().nt_queue == 2 || (tuning().nt_queue == 1 && nt_is_fwd(MODE));
   if constexpr (nt_is_hb(MODE)) {
     // the static walk g = bp + i G with G a multiple of tiles_n: the tiles_n column tiles of a row
     // band are tile i of tiles_n consecutive blocks (one XCD under the xcd_remap order), which wait
@@ -1376,8 +1362,9 @@ static hipError_t launch_nt(const NtParams& p_in, hipStream_t s, bool persistent
     else g -= g % tiles_n;
     if (g < tiles_n) g = tiles_n;
     if (!hb_coresident(MODE, g, s)) return hipErrorCooperativeLaunchTooLarge;
-    p.hb_fault = g_hb_fault & 0xff;
-    p.spin_limit = (g_hb_fault >> 8) > 0 ? (g_hb_fault >> 8) : kHeadSpinLimit;
+    const int fault = tuning().hb_fault;
+    p.hb_fault = fault & 0xff;
+    p.spin_limit = (fault >> 8) > 0 ? (fault >> 8) : kHeadSpinLimit;
     const hipError_t e = hipMemsetAsync(p.head_part, 0xFF, (size_t)tiles_n * p.M * sizeof(float), s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((gemm_nt_kernel<Cfg, MODE, HEAD>), dim3(g), dim3(Cfg::THREADS), 0, s, p);
@@ -1452,16 +1439,13 @@ static hipError_t dispatch_act(int mode, bool head, const NtParams& p, hipStream
 
 // tile override for A/B measurement: 0 = auto, 128 or 256; pipe (256x256): 0 = BK 64, one
 // tile per block; 1 = BK 64 persistent; 4 = BK 64 persistent ping-pong (pingpong2_tiles)
-static int g_nt_tile = 0;
-static int g_nt_pipe = -1;  // -1: automatic = ping-pong 4 for every mode (kernel_bench r06)
-static bool nt_pp() { return g_nt_pipe < 0 || (g_nt_pipe >= 4 && g_nt_pipe <= 7); }
-void gemm_nt_set_tile(int tile) { g_nt_tile = tile; }
-void gemm_nt_set_pipe(int v) { g_nt_pipe = v; }
+// (pipe -1: automatic = ping-pong 4 for every mode, kernel_bench r06)
+static bool nt_pp() { return tuning().nt_pipe < 0 || (tuning().nt_pipe >= 4 && tuning().nt_pipe <= 7); }
 
 int nt_choose_tile(int M, int N) {
   const bool large_ok = (M % 256 == 0) && (N % 256 == 0);
-  if (g_nt_tile == 128 || !large_ok) return 128;
-  if (g_nt_tile == 256) return 256;
+  if (tuning().nt_tile == 128 || !large_ok) return 128;
+  if (tuning().nt_tile == 256) return 256;
   // the 256x256 tile (1 block/CU) needs >= 2 tiles per CU to keep 256 CUs busy
   return (long)(M / 256) * (N / 256) >= 512 ? 256 : 128;
 }
@@ -1470,7 +1454,7 @@ bool gemm_nt_head_fusable(int M, int N, hipStream_t s, int mode) {
   if (!(nt_choose_tile(M, N) == 256 && nt_pp() && M % 256 == 0 && N % 256 == 0 && N / 256 <= 4 && N % 128 == 0))
     return false;
   // the grid launch_nt will use must be co-resident (one block per CU on an idle device)
-  const int ntiles = (M / 256) * (N / 256), cap = g_nt_grid_cap > 0 ? g_nt_grid_cap : stream_cus(s);
+  const int ntiles = (M / 256) * (N / 256), cap = nt_grid(s);
   return hb_coresident(mode, ntiles < cap ? ntiles : cap, s);
 }
 
@@ -1507,13 +1491,13 @@ static hipError_t gemm_nt_window(int mode, bool head, const NtParams& p, hipStre
   }
   if (p.tile == 256) {
     if (p.M % 256 || p.N % 256) return hipErrorInvalidValue;
-    const int pipe = g_nt_pipe >= 0 ? g_nt_pipe : 4;
+    const int pipe = tuning().nt_pipe >= 0 ? tuning().nt_pipe : 4;
     // pipe 5: the forward with its epilogue under the next tile's MFMAs (gemm_nt1.hip)
     if ((pipe == 5 || pipe == 7) && mode == NT_FWD && !head && p.ld == p.N && gemm_nt_one_ok(p))
-      return gemm_nt_one(p, g_nt_grid_cap > 0 ? g_nt_grid_cap : stream_cus(s), g_nt_diag, pipe == 5, s);
+      return gemm_nt_one(p, nt_grid(s), tuning().nt_diag, pipe == 5, s);
     // pipe 6: the forward with one wave per SIMD on 256x256 tiles (gemm_nt2.hip)
     if (pipe == 6 && mode == NT_FWD && !head && p.ld == p.N && gemm_nt_big_ok(p))
-      return gemm_nt_big(p, g_nt_grid_cap > 0 ? g_nt_grid_cap : stream_cus(s), g_nt_diag, s);
+      return gemm_nt_big(p, nt_grid(s), tuning().nt_diag, s);
     switch (pipe) {
       case 0: return dispatch_mode<NtLarge>(mode, head, p, s, false);
       case 4:

@@ -257,15 +257,10 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_tn_kernel(TnParams p) {
       dst[(i * SJ + j) * 64] = float4{acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
 }
 
-static int g_tn_tile = 0;
-static int g_tn_pipe = -1;  // -1: automatic = 4, two-segment ping-pong (fastest, kernel_bench r06)
-void gemm_tn_set_tile(int tile) { g_tn_tile = tile; }
-void gemm_tn_set_pipe(int v) { g_tn_pipe = v; }
-
 int tn_choose_tile(int R, int Hin, int Hout) {
   const bool large_ok = (Hin % 256 == 0) && (Hout % 256 == 0);
-  if (g_tn_tile == 128 || !large_ok) return 128;
-  if (g_tn_tile == 256) return 256;
+  if (tuning().tn_tile == 128 || !large_ok) return 128;
+  if (tuning().tn_tile == 256) return 256;
   // 256x256 tiles when slices of >= 8 K-steps still give >= 512 blocks
   const long blocks = (long)(R / 64 / 8) * (Hin / 256) * (Hout / 256);
   return blocks >= 512 ? 256 : 128;
@@ -282,7 +277,8 @@ hipError_t gemm_tn_dw(const TnParams& p, hipStream_t s) {
   if (p.Hin % 128 || p.Hout % 128 || p.R % 64 || p.R <= 0 || p.splits < 1) return hipErrorInvalidValue;
   if (p.tile == 256) {
     if (p.Hin % 256 || p.Hout % 256) return hipErrorInvalidValue;
-    switch (g_tn_pipe >= 0 ? g_tn_pipe : 4) {
+    // automatic = 4, the two-segment ping-pong (fastest, kernel_bench r06)
+    switch (tuning().tn_pipe >= 0 ? tuning().tn_pipe : 4) {
       case 0: return launch_tn<TnL0>(p, s);
       case 1: return (p.R % 32) ? hipErrorInvalidValue : launch_tn<TnL1>(p, s);
       case 2: return launch_tn<TnL2>(p, s);

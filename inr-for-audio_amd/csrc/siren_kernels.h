@@ -23,6 +23,20 @@ constexpr bool nt_is_fwd(int m) { return m == NT_FWD || m == NT_FWD_SNAKE || m =
 // forward modes that evaluate a Snake (they stage a and 1/a in LDS)
 constexpr bool nt_is_snake_fwd(int m) { return m == NT_FWD_SNAKE || m == NT_FWD_HB_SNAKE; }
 
+// The siren_set_option knobs (include/siren_hip.h enum siren_option), one member per option:
+// process-global and unsynchronised.  capi.hip's option table holds each one's default and
+// accepted values and is the only writer; the launchers read tuning().x.
+struct Tuning {
+  int nt_tile, tn_tile;  // forced GEMM tile edge (0 = automatic, 128, 256)
+  int nt_pipe, tn_pipe;  // 256x256 K-loop variant (-1 = automatic = 4)
+  int nt_grid;           // persistent NT grid size (0 = one block per CU)
+  int nt_diag;           // measurement-only NT ablation bits (SIREN_DIAG builds)
+  int nt_queue;          // dynamic tile queue: 0 off, 1 forward modes, 2 every ping-pong mode
+  int head_fuse;         // siren_train_step runs the last layer as NT_FWD_HB* when it can
+  int hb_fault;          // hand-off fault hook (SIREN_DIAG builds)
+};
+Tuning& tuning();
+
 struct NtParams {
   const h16* X;  // [M][K]
   const h16* W;  // [N][K]
@@ -87,14 +101,6 @@ hipError_t gemm_nt_big(const NtParams& p, int grid, int diag, hipStream_t s);
 // NT_FWD_HB is available for this shape under the current tile / K-loop settings
 // also false when the fused launch's grid could not be co-resident (occupancy x CUs < grid)
 bool gemm_nt_head_fusable(int M, int N, hipStream_t s, int mode = NT_FWD_HB);
-void gemm_nt_set_tile(int tile);  // 0 = auto, 128, 256 (A/B measurement)
-void gemm_tn_set_tile(int tile);
-void gemm_nt_set_pipe(int v);     // 256x256 K-loop: 4 ping-pong (default), 1 persistent, 0 one tile per block
-void gemm_tn_set_pipe(int v);     // 256x256 K-loop variant (TnL0..TnL2)
-void gemm_nt_set_grid_cap(int cap);  // persistent grid size override (0 = #CUs)
-bool gemm_nt_set_diag(int bits);     // SIREN_OPT_NT_DIAG (false: not a SIREN_DIAG build)
-void gemm_nt_set_queue(int on);       // SIREN_OPT_NT_QUEUE: dynamic tile queue (ping-pong K-loop)
-bool gemm_nt_set_hb_fault(int v);     // SIREN_OPT_HB_FAULT (false: not a SIREN_DIAG build)
 struct TnParams {
   const h16* Y;   // [R][Hin]   layer input (A role: dW column index k)
   const h16* dZ;  // [R][Hout]  layer pre-activation gradient (B role: dW row index o)

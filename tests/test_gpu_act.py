@@ -19,9 +19,10 @@ import numpy as np
 import pytest
 import torch
 
-from inr_for_audio_amd._lib import new_tileq
+from inr_for_audio_amd._lib import Opt, new_tileq, options
 from oracle import siren_oracle as orc
 from errlog import check_grads, log
+from gpu_util import ok, ptr, rel_np as _rel, release, stream as S, to_dev, within_f16
 
 pytestmark = pytest.mark.gpu
 
@@ -29,41 +30,16 @@ F32 = np.float32
 H16 = torch.float16
 SINE, SNAKE, TANH = 0, 1, 2
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-_KEEP = []
-
-
-def ptr(t):
-    return 0 if t is None else t.data_ptr()
-
-
-def S():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def ok(status, lib):
-    assert status == 0, lib.siren_status_string(status)
-
-
-def to_dev(a, dev, dtype=torch.float32):
-    t = torch.from_numpy(np.ascontiguousarray(a, dtype=F32)).to(dev).to(dtype)
-    _KEEP.append(t)
-    return t
 
 
 def f16_np(t):
     return t.float().cpu().numpy().astype(np.float64)
 
 
-def within_f16(got, ref, abs_slack):
-    err = np.abs(np.asarray(got, np.float64) - ref)
-    return float(np.max(err - (np.abs(ref) * 2.0 ** -11 + abs_slack + 2.0 ** -25)))
-
-
 @pytest.fixture(autouse=True)
 def _release():
     yield
-    torch.cuda.synchronize()
-    _KEEP.clear()
+    release()
 
 
 @pytest.fixture(params=[(128, 0, -1), (256, 0, -1), (256, 2, -1), (256, 0, 1), (256, 2, 1)],
@@ -72,13 +48,8 @@ def tile(request, lib):
     """NT tile edge, persistent grid (grid 2: every block walks several tiles) and 256x256
     K-loop (-1: the automatic ping-pong, 1: the persistent double buffer)."""
     t, grid, pipe = request.param
-    ok(lib.siren_set_option(0, t), lib)
-    ok(lib.siren_set_option(4, grid), lib)
-    ok(lib.siren_set_option(2, pipe), lib)
-    yield t
-    lib.siren_set_option(0, 0)
-    lib.siren_set_option(4, 0)
-    lib.siren_set_option(2, -1)
+    with options(lib, {Opt.NT_TILE: t, Opt.NT_GRID: grid, Opt.NT_PIPE: pipe}):
+        yield t
 
 
 def _inputs(rng, R, H):
@@ -143,18 +114,13 @@ def test_inner_fwd_act_lines_queue(lib, dev, act, H):
     a = (0.5 * rng.uniform(0.5, 1.5, H)).astype(F32)
     Xd, Wd, bd, ad = to_dev(X, dev, H16), to_dev(W, dev, H16), to_dev(b, dev), to_dev(a, dev)
     outs = []
-    ok(lib.siren_set_option(0, 256), lib)
-    try:
-        for queue in (1, 0):
-            ok(lib.siren_set_option(8, queue), lib)
+    for queue in (1, 0):
+        with options(lib, {Opt.NT_TILE: 256, Opt.NT_QUEUE: queue}):
             Y, C, E = (torch.full((R, H), float("nan"), dtype=H16, device=dev) for _ in range(3))
             ok(lib.siren_inner_fwd_act(ptr(Xd), ptr(Wd), ptr(bd), act, ctypes.c_float(1.0), ptr(ad), R, H, ptr(Y),
                                        ptr(C), ptr(E), None, None, ptr(new_tileq(dev)), S()), lib)
             torch.cuda.synchronize()
-            outs.append((Y, C, E) if act == SNAKE else (Y, C))
-    finally:
-        lib.siren_set_option(8, 1)
-        lib.siren_set_option(0, 0)
+        outs.append((Y, C, E) if act == SNAKE else (Y, C))
     for q, s in zip(*outs):
         assert torch.equal(q, s)
     z = X.astype(np.float64) @ W.astype(np.float64).T + b
@@ -275,10 +241,6 @@ def _signal(n, in_dim=1):
         t = torch.cat([t, ch], 1)
     y = 0.5 * torch.sin(37 * t[:, :1]) + 0.3 * torch.sin(91 * t[:, :1] + 0.5)
     return t, y
-
-
-def _rel(a, b):
-    return float(np.linalg.norm(np.asarray(a, np.float64) - b) / max(np.linalg.norm(b), 1e-30))
 
 
 @pytest.mark.parametrize("H,cfg,n,a0,in_dim,mb", [

@@ -6,6 +6,7 @@ import torch
 
 from oracle import siren_oracle as orc
 from errlog import check_grads, log
+from gpu_util import rel_np as _rel
 
 pytestmark = pytest.mark.gpu
 
@@ -18,10 +19,6 @@ def _model(H, L, w0, w=30.0, in_dim=1, seed=0):
 
 def _sd(model):
     return {k: v.detach().cpu().numpy().copy() for k, v in model.state_dict().items()}
-
-
-def _rel(a, b):
-    return float(np.linalg.norm(np.asarray(a, np.float64) - b) / max(np.linalg.norm(b), 1e-30))
 
 
 def _signal(n, in_dim=1):
@@ -69,10 +66,10 @@ def test_train_step_grads_vs_oracle(dev, H, L, n, w0, in_dim, mb):
 def test_train_step_forced_tiles(lib, dev, tile):
     """The fused step with the NT and TN GEMM tile edge forced (256 is what the 2^20-coord
     bench uses) against the oracle, SIREN 5x512 on 2048 rows."""
+    from inr_for_audio_amd._lib import Opt, options
     from inr_for_audio_amd.engine import SirenEngine
-    assert lib.siren_set_option(0, tile) == 0 and lib.siren_set_option(1, tile) == 0
-    assert lib.siren_set_option(4, 3) == 0   # persistent NT grid of 3 blocks: multi-tile walks
-    try:
+    # persistent NT grid of 3 blocks: multi-tile walks
+    with options(lib, {Opt.NT_TILE: tile, Opt.TN_TILE: tile, Opt.NT_GRID: 3}):
         L, H, w0 = 4, 512, 3000.0
         model = _model(H, L, w0)
         sd0 = _sd(model)
@@ -80,10 +77,6 @@ def test_train_step_forced_tiles(lib, dev, tile):
         eng = SirenEngine(model, t, y, device=dev)
         eng.step()
         torch.cuda.synchronize()
-    finally:
-        lib.siren_set_option(0, 0)
-        lib.siren_set_option(1, 0)
-        lib.siren_set_option(4, 0)
     got = {k: v.detach().cpu().numpy() for k, v in zip(eng.layout.names, eng.grad_views())}
     p = orc.Params.from_state_dict(sd0, L)
     out, cache = orc.forward(p, t.numpy(), w0, 30.0, half=True, dtype=np.float64)

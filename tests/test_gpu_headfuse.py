@@ -11,26 +11,19 @@ import numpy as np
 import pytest
 import torch
 
+from inr_for_audio_amd._lib import Opt, options
 from errlog import check_grads, log
+from gpu_util import grads as _grads, option_setter, rel as _rel
 from oracle import siren_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
-OPT_NT_TILE, OPT_NT_GRID, OPT_HEAD_FUSE = 0, 4, 9
-DEFAULTS = {OPT_NT_TILE: 0, OPT_NT_GRID: 0, OPT_HEAD_FUSE: 1}
-
 
 @pytest.fixture
 def opts(lib):
-    touched = []
-
-    def set_(o, v):
-        assert lib.siren_set_option(o, v) == 0, (o, v)
-        touched.append(o)
-
-    yield set_
-    for o in touched:
-        lib.siren_set_option(o, DEFAULTS[o])
+    """opts(Opt.X, v): set a knob for the rest of the test."""
+    with option_setter(lib) as set_:
+        yield set_
 
 
 def _engine(dev, H, L, n, *, w0=3000.0, ll=True, loss="mse", mb=1 << 20, seed=0):
@@ -45,22 +38,6 @@ def _engine(dev, H, L, n, *, w0=3000.0, ll=True, loss="mse", mb=1 << 20, seed=0)
     return eng, sd0, t, y
 
 
-def _grads(eng, lib):
-    """One siren_train_step per micro-batch (no update); (grads, out, g, per-kind launches)."""
-    from inr_for_audio_amd import _lib
-    _lib.check(lib.siren_profile_enable(64 * eng.n_micro), "profile_enable")
-    eng._launch_grads()
-    torch.cuda.synchronize()
-    prof = _lib.profile_read()
-    _lib.check(lib.siren_profile_enable(0), "profile_disable")
-    return eng.grads.clone(), eng.ws.out.clone(), eng.ws.g.clone(), {k: n for k, (_, n) in prof.items()}
-
-
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return float((a - b).norm() / max(float(b.norm()), 1e-30))
-
-
 @pytest.mark.parametrize("H,L,n,grid,ll,loss,mb", [
     (1024, 4, 8192, 0, True, "mse", 1 << 20),    # 4 column tiles per band, 32 bands on 128 blocks
     (1024, 4, 8192, 8, True, "mse", 1 << 20),    # 2 band groups walking 16 bands each
@@ -70,11 +47,11 @@ def _rel(a, b):
     (1024, 2, 6000, 4, True, "mse", 2048),       # 3 micro-batches accumulating
 ])
 def test_fused_matches_unfused(dev, lib, opts, H, L, n, grid, ll, loss, mb):
-    opts(OPT_NT_TILE, 256)
-    opts(OPT_NT_GRID, grid)
+    opts(Opt.NT_TILE, 256)
+    opts(Opt.NT_GRID, grid)
     eng, _, _, _ = _engine(dev, H, L, n, ll=ll, loss=loss, mb=mb)
     ga, oa, gga, ka = _grads(eng, lib)
-    opts(OPT_HEAD_FUSE, 0)
+    opts(Opt.HEAD_FUSE, 0)
     gb, ob, ggb, kb = _grads(eng, lib)
     # the fused path ran (one launch per micro-batch, no head_loss / head_bwd), the other did not
     assert ka["head_fwd"] == eng.n_micro and kb["head_fwd"] == 0
@@ -99,7 +76,7 @@ def test_fused_matches_unfused(dev, lib, opts, H, L, n, grid, ll, loss, mb):
     (256, 2, 4096, False, "mse"),
 ])
 def test_fused_vs_oracle(dev, lib, opts, H, L, n, ll, loss):
-    opts(OPT_NT_TILE, 256)
+    opts(Opt.NT_TILE, 256)
     eng, sd0, t, y = _engine(dev, H, L, n, ll=ll, loss=loss)
     got_g, _, _, kinds = _grads(eng, lib)
     assert kinds["head_fwd"] == 1
@@ -120,7 +97,7 @@ def test_fused_vs_oracle(dev, lib, opts, H, L, n, ll, loss):
 def test_fused_step_graph_and_determinism(dev, opts):
     """Eager steps, a captured step replayed, and a second engine: bit-identical parameters and
     losses (the hand-off's partial order is fixed, so no run-to-run drift)."""
-    opts(OPT_NT_TILE, 256)
+    opts(Opt.NT_TILE, 256)
     a, _, _, _ = _engine(dev, 1024, 3, 8192)
     b, _, _, _ = _engine(dev, 1024, 3, 8192)
     for _ in range(4):
@@ -149,8 +126,8 @@ def test_kernel_vs_unfused_launches(dev, lib, opts, H, R, n_valid, grid):
     to fp32 summation order."""
     import ctypes
     from inr_for_audio_amd._lib import new_tileq
-    opts(OPT_NT_TILE, 256)
-    opts(OPT_NT_GRID, grid)
+    opts(Opt.NT_TILE, 256)
+    opts(Opt.NT_GRID, grid)
     g_ = torch.Generator(device=dev).manual_seed(H + R)
     f16 = torch.float16
     P = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
@@ -194,11 +171,11 @@ def test_fused_head_needs_a_coresident_grid(dev, lib, opts):
     SIREN_OPT_NT_GRID) is not fused -- siren_train_step falls back to the unfused launches and
     computes the same step; siren_head_fused_fwd refuses it with an error instead of launching."""
     import ctypes
-    opts(OPT_NT_TILE, 256)
+    opts(Opt.NT_TILE, 256)
     eng, _, _, _ = _engine(dev, 1024, 2, 65536)   # 1 024 tiles of 256^2
     ga, oa, gga, ka = _grads(eng, lib)
     assert ka["head_fwd"] == 1
-    opts(OPT_NT_GRID, 1024)                        # more blocks than CUs x occupancy (1 per CU)
+    opts(Opt.NT_GRID, 1024)                        # more blocks than CUs x occupancy (1 per CU)
     gb, ob, ggb, kb = _grads(eng, lib)
     assert kb["head_fwd"] == 0 and kb["inner_fwd"] == 2
     assert torch.equal(oa, ob) and torch.equal(gga, ggb)
@@ -247,12 +224,11 @@ def test_handoff_timeout_voids_the_step(dev, monkeypatch, cfg):
     assert eng.steps_applied() == 2
     fused = eng.lib.siren_profile_enable(64) == 0
     before = [x.clone() for x in (eng.params, eng.exp_avg, eng.exp_avg_sq, eng.state, eng.loss_hist)]
-    assert diag.siren_set_option(10, (64 << 8) | 1) == 0
     try:
-        eng.step()
-        torch.cuda.synchronize()
+        with options(diag, {Opt.HB_FAULT: (64 << 8) | 1}):
+            eng.step()
+            torch.cuda.synchronize()
     finally:
-        assert diag.siren_set_option(10, 0) == 0
         prof = _lib.profile_read()
         diag.siren_profile_enable(0)
     assert fused and prof["head_fwd"][1] == 1, prof  # the fused last layer ran
@@ -292,9 +268,8 @@ def test_handoff_timeout_fails_fast(dev, monkeypatch):
     t = torch.linspace(-1, 1, n).reshape(n, 1)
     eng = SirenEngine(model, t, 0.5 * torch.sin(37 * t), micro_batch=16384, device=dev)
     assert eng.lib is diag and eng.n_micro == 4
-    assert diag.siren_set_option(0, 256) == 0  # 256 x 256 tiles at 16 384 rows (the fused path's tile)
-    assert diag.siren_set_option(4, 16) == 0  # 16 blocks: each walks 16 band tiles per launch
-    try:
+    # 256 x 256 tiles at 16 384 rows (the fused path's tile); 16 blocks: each walks 16 band tiles per launch
+    with options(diag, {Opt.NT_TILE: 256, Opt.NT_GRID: 16}):
         eng.step()
         torch.cuda.synchronize()
         fused = diag.siren_profile_enable(64 * eng.n_micro) == 0
@@ -306,17 +281,11 @@ def test_handoff_timeout_fails_fast(dev, monkeypatch):
         diag.siren_profile_enable(0)
         assert fused and prof["head_fwd"][1] == eng.n_micro, prof  # the fused last layer runs per micro-batch
         limit = 1 << 20
-        assert diag.siren_set_option(10, (limit << 8) | 1) == 0
-        try:
+        with options(diag, {Opt.HB_FAULT: (limit << 8) | 1}):
             t0 = time.perf_counter()
             eng.step()
             torch.cuda.synchronize()
             voided = time.perf_counter() - t0
-        finally:
-            assert diag.siren_set_option(10, 0) == 0
-    finally:
-        diag.siren_set_option(4, 0)
-        diag.siren_set_option(0, 0)
     per_limit = limit * 0.16e-6
     with pytest.raises(_lib.SirenError, match="hand-off"):
         eng.steps_applied()

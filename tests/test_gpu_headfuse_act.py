@@ -20,27 +20,21 @@ import numpy as np
 import pytest
 import torch
 
+from inr_for_audio_amd._lib import Opt
 from errlog import check_grads, log
+from gpu_util import grads as _grads, option_setter, rel as _rel
 from oracle import siren_oracle as orc
 
 pytestmark = pytest.mark.gpu
 
-OPT_NT_TILE, OPT_NT_GRID, OPT_HEAD_FUSE = 0, 4, 9
-DEFAULTS = {OPT_NT_TILE: 0, OPT_NT_GRID: 0, OPT_HEAD_FUSE: 1}
 SINE, SNAKE, TANH = 0, 1, 2
 
 
 @pytest.fixture
 def opts(lib):
-    touched = []
-
-    def set_(o, v):
-        assert lib.siren_set_option(o, v) == 0, (o, v)
-        touched.append(o)
-
-    yield set_
-    for o in touched:
-        lib.siren_set_option(o, DEFAULTS[o])
+    """opts(Opt.X, v): set a knob for the rest of the test."""
+    with option_setter(lib) as set_:
+        yield set_
 
 
 @pytest.mark.parametrize("act", [SNAKE, TANH])
@@ -52,8 +46,8 @@ def opts(lib):
 ])
 def test_kernel_act_vs_unfused_launches(dev, lib, opts, act, H, R, n_valid, grid, amag):
     from inr_for_audio_amd._lib import new_tileq
-    opts(OPT_NT_TILE, 256)
-    opts(OPT_NT_GRID, grid)
+    opts(Opt.NT_TILE, 256)
+    opts(Opt.NT_GRID, grid)
     g_ = torch.Generator(device=dev).manual_seed(H + R + act)
     f16 = torch.float16
     P = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
@@ -110,21 +104,6 @@ def _engine(dev, H, cfg, n, *, a0=0.5, mb=1 << 20, seed=0, w0=3000.0, loss="mse"
     return eng, sd0, t, y
 
 
-def _grads(eng, lib):
-    from inr_for_audio_amd import _lib
-    _lib.check(lib.siren_profile_enable(64 * eng.n_micro), "profile_enable")
-    eng._launch_grads()
-    torch.cuda.synchronize()
-    prof = _lib.profile_read()
-    _lib.check(lib.siren_profile_enable(0), "profile_disable")
-    return eng.grads.clone(), eng.ws.out.clone(), eng.ws.g.clone(), {k: n for k, (_, n) in prof.items()}
-
-
-def _rel(a, b):
-    a, b = a.double(), b.double()
-    return float((a - b).norm() / max(float(b.norm()), 1e-30))
-
-
 @pytest.mark.parametrize("H,cfg,n,grid,a0,mb,loss", [
     (1024, (2, 2, 0), 8192, 0, 0.5, 1 << 20, "mse"),   # run.py:30 train() default stack
     (1024, (0, 4, 0), 8000, 8, 50.0, 1 << 20, "mse"),  # run.py:466 __main__: 4 Snake layers, a = 50
@@ -132,8 +111,8 @@ def _rel(a, b):
     (1024, (1, 1, 0), 6000, 4, 0.5, 2048, "mse"),      # Snake last, 3 micro-batches
 ])
 def test_fused_act_matches_unfused(dev, lib, opts, H, cfg, n, grid, a0, mb, loss):
-    opts(OPT_NT_TILE, 256)
-    opts(OPT_NT_GRID, grid)
+    opts(Opt.NT_TILE, 256)
+    opts(Opt.NT_GRID, grid)
     eng, _, _, _ = _engine(dev, H, cfg, n, a0=a0, mb=mb, loss=loss)
     L = sum(cfg)
     snake_last = cfg[2] == 0
@@ -141,7 +120,7 @@ def test_fused_act_matches_unfused(dev, lib, opts, H, cfg, n, grid, a0, mb, loss
     g0, o0, gg0, k0 = _grads(eng, lib)
     assert k0["head_fwd"] == (0 if snake_last else eng.n_micro)
     ga, oa, gga, ka = _grads(eng, lib)
-    opts(OPT_HEAD_FUSE, 0)
+    opts(Opt.HEAD_FUSE, 0)
     gb, ob, ggb, kb = _grads(eng, lib)
     assert ka["head_fwd"] == eng.n_micro and kb["head_fwd"] == 0
     assert ka["inner_fwd"] == (L - 1) * eng.n_micro and kb["inner_fwd"] == L * eng.n_micro
@@ -167,7 +146,7 @@ def test_fused_act_matches_unfused(dev, lib, opts, H, cfg, n, grid, a0, mb, loss
     (1024, (0, 4, 0), 4096, 50.0),
 ])
 def test_fused_act_vs_oracle(dev, lib, opts, H, cfg, n, a0):
-    opts(OPT_NT_TILE, 256)
+    opts(Opt.NT_TILE, 256)
     eng, sd0, t, y = _engine(dev, H, cfg, n, a0=a0)
     _grads(eng, lib)                      # a Snake last layer's first launch: unfused
     got_g, _, _, kinds = _grads(eng, lib)
@@ -192,7 +171,7 @@ def test_fused_act_vs_oracle(dev, lib, opts, H, cfg, n, a0):
 def test_fused_act_training_graph_and_determinism(dev, opts):
     """The default train() stack (2 sine + 2 Snake): eager steps (first unfused, then fused) and a
     captured step replayed give bit-identical parameters and losses; no fp16 overflow."""
-    opts(OPT_NT_TILE, 256)
+    opts(Opt.NT_TILE, 256)
     a, _, _, _ = _engine(dev, 1024, (2, 2, 0), 8192)
     b, _, _, _ = _engine(dev, 1024, (2, 2, 0), 8192)
     for _ in range(5):
@@ -222,7 +201,7 @@ def test_snake_head_scale_per_micro_batch(dev, lib, opts):
     overflow count and gradient error are logged.)"""
     from inr_for_audio_amd.engine import SirenEngine
     from inr_for_audio_amd.models import SirenWithSnakeTanh
-    opts(OPT_NT_TILE, 256)
+    opts(Opt.NT_TILE, 256)
     torch.manual_seed(0)
     H, mb, n = 1024, 4096, 12288
     model = SirenWithSnakeTanh(1, 1, H, 1, 1, 0, first_omega_0=3000.0, hidden_omega_0=30.0, a_initial=0.5)
@@ -241,7 +220,7 @@ def test_snake_head_scale_per_micro_batch(dev, lib, opts):
     assert float(gmax[1]) > 100 * float(max(gmax[0], gmax[2])), gmax  # really a loud segment between quiet ones
     _grads(eng, lib)                      # every micro-batch's partials at these weights
     ga, oa, gga, ka = _grads(eng, lib)    # fused, each at its own scale
-    opts(OPT_HEAD_FUSE, 0)
+    opts(Opt.HEAD_FUSE, 0)
     gb, ob, ggb, kb = _grads(eng, lib)    # unfused: the scale from this launch's own max|g|
     assert ka["head_fwd"] == 3 and kb["head_fwd"] == 0
     assert torch.equal(oa, ob) and torch.equal(gga, ggb)
@@ -250,7 +229,7 @@ def test_snake_head_scale_per_micro_batch(dev, lib, opts):
     for k, e in errs.items():
         assert e < 2e-5, (k, e)
     # the round-4 behaviour, for the record: every micro-batch on one max|g| slice
-    opts(OPT_HEAD_FUSE, 1)
+    opts(Opt.HEAD_FUSE, 1)
     torch.manual_seed(0)
     model2 = SirenWithSnakeTanh(1, 1, H, 1, 1, 0, first_omega_0=3000.0, hidden_omega_0=30.0, a_initial=0.5)
     eng2 = SirenEngine(model2, t, y, micro_batch=mb, device=dev)
@@ -262,7 +241,7 @@ def test_snake_head_scale_per_micro_batch(dev, lib, opts):
     shared_overflows = eng2.guard_state()["overflows"]
     _grads(eng2, lib)
     gc, _, _, _ = _grads(eng2, lib)
-    opts(OPT_HEAD_FUSE, 0)
+    opts(Opt.HEAD_FUSE, 0)
     gd, _, _, _ = _grads(eng2, lib)
     lay2 = eng2.layout
     shared_errs = {k: _rel(lay2.view(gc, i), lay2.view(gd, i)) for i, k in enumerate(lay2.names)}

@@ -13,42 +13,19 @@ import numpy as np
 import pytest
 import torch
 
-from inr_for_audio_amd._lib import new_tileq
+from inr_for_audio_amd._lib import Opt, new_tileq, options
 from oracle import siren_oracle as orc
+from gpu_util import ok, ptr, release, stream as S, to_dev, within_f16
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 
 
-def ptr(t):
-    return 0 if t is None else t.data_ptr()
-
-
-def S():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def ok(status, lib):
-    assert status == 0, lib.siren_status_string(status)
-
-
-_KEEP = []
-
-
-def to_dev(a, dev, dtype=torch.float32):
-    """Host array -> device tensor.  Kept alive (module list) so a pointer taken from a
-    temporary inside one call can never be recycled by the caching allocator."""
-    t = torch.from_numpy(np.ascontiguousarray(a, dtype=F32)).to(dev).to(dtype)
-    _KEEP.append(t)
-    return t
-
-
 @pytest.fixture(autouse=True)
 def _release():
     yield
-    torch.cuda.synchronize()
-    _KEEP.clear()
+    release()
 
 
 @pytest.fixture(params=[(128, 0, 0), (256, 0, 0), (256, 1, 0), (256, 1, 2), (256, 1, 3), (256, 4, 0),
@@ -59,20 +36,14 @@ def nt_tile(request, lib):
     """Force the NT GEMM tile edge, persistence and persistent grid size (siren_set_option)
     for one test; grid 2 makes every block walk several tiles across the LDS ring."""
     tile, pipe, grid = request.param
-    ok(lib.siren_set_option(0, tile), lib)
-    ok(lib.siren_set_option(2, pipe), lib)
-    ok(lib.siren_set_option(4, grid), lib)
-    yield tile
-    lib.siren_set_option(0, 0)
-    lib.siren_set_option(2, -1)
-    lib.siren_set_option(4, 0)
+    with options(lib, {Opt.NT_TILE: tile, Opt.NT_PIPE: pipe, Opt.NT_GRID: grid}):
+        yield tile
 
 
 @pytest.fixture(params=[0, 1, 2, 3, 4], ids=lambda p: f"p{p}")
 def tn_pipe(request, lib):
-    ok(lib.siren_set_option(3, request.param), lib)
-    yield request.param
-    lib.siren_set_option(3, -1)
+    with options(lib, {Opt.TN_PIPE: request.param}):
+        yield request.param
 
 
 def _skip_tile(tile, R, H):
@@ -85,14 +56,6 @@ H16 = torch.float16
 
 def f16_np(t: torch.Tensor) -> np.ndarray:
     return t.float().cpu().numpy()
-
-
-def within_f16(got, ref, abs_slack=1e-5):
-    """|got - ref| <= 2^-11 * |ref| + abs_slack elementwise (one fp16 rounding + slack;
-    2^-25 covers the subnormal spacing)."""
-    err = np.abs(np.asarray(got, np.float64) - np.asarray(ref, np.float64))
-    bound = np.abs(np.asarray(ref, np.float64)) * 2.0 ** -11 + abs_slack + 2.0 ** -25
-    return float(np.max(err - bound))
 
 
 def gscale_dev(dev, k):
@@ -178,21 +141,14 @@ def test_inner_fwd_pipes_bit_identical(lib, dev, R, H, grid):
     b = (torch.rand(H, device=dev, generator=g) - 0.5) * 0.06
     tq = new_tileq(dev)
     outs = {}
-    try:
-        ok(lib.siren_set_option(0, 256), lib)
-        ok(lib.siren_set_option(4, grid), lib)
-        for pipe in (4, 5, 6, 7):
-            ok(lib.siren_set_option(2, pipe), lib)
+    for pipe in (4, 5, 6, 7):
+        with options(lib, {Opt.NT_TILE: 256, Opt.NT_GRID: grid, Opt.NT_PIPE: pipe}):
             Y = torch.full((R, H), float("nan"), dtype=H16, device=dev)
             C = torch.full_like(Y, float("nan"))
             ok(lib.siren_inner_fwd(ptr(X), ptr(W), ptr(b), ctypes.c_float(30.0), R, H, ptr(Y), ptr(C), None,
                                    None, ptr(tq), S()), lib)
             torch.cuda.synchronize()
-            outs[pipe] = (Y.view(torch.int16), C.view(torch.int16))
-    finally:
-        lib.siren_set_option(0, 0)
-        lib.siren_set_option(2, -1)
-        lib.siren_set_option(4, 0)
+        outs[pipe] = (Y.view(torch.int16), C.view(torch.int16))
     for pipe in (5, 6, 7):
         assert torch.equal(outs[pipe][0], outs[4][0]), pipe
         assert torch.equal(outs[pipe][1], outs[4][1]), pipe

@@ -15,26 +15,34 @@ import numpy as np
 import pytest
 import torch
 
+from inr_for_audio_amd._lib import Opt
+from gpu_util import ok, option_setter, ptr as P
+
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 H16 = torch.float16
 
 
-def ok(status, lib):
-    assert status == 0, lib.siren_status_string(status)
-
-
 @pytest.fixture(autouse=True)
 def _reset(lib):
-    yield
-    torch.cuda.synchronize()
-    for opt, v in ((0, 0), (2, -1), (4, 0), (8, 1)):
-        lib.siren_set_option(opt, v)
+    """A test's knobs go back once its launches have finished."""
+    with option_setter(lib) as set_:
+        yield set_
+        torch.cuda.synchronize()
 
 
-def P(t):
-    return 0 if t is None else t.data_ptr()
+@pytest.fixture
+def knobs(_reset):
+    """knobs(Opt.X, v): set a knob for the rest of the test."""
+    return _reset
+
+
+def _ping_pong_256(set_, grid):
+    """256 x 256 tiles on the ping-pong K-loop with a persistent grid of `grid` blocks."""
+    set_(Opt.NT_TILE, 256)
+    set_(Opt.NT_PIPE, 4)
+    set_(Opt.NT_GRID, grid)
 
 
 def _inputs(dev, R, H, seed):
@@ -77,11 +85,9 @@ def _same(a, b):
                                       (3072, 512, 8), (6144, 256, 16),
                                       # 20 tiles: shards of 2 and 3 tiles (uneven eighths)
                                       (2560, 512, 8), (2560, 512, 16)])
-def test_queue_bit_identical_to_static_walk(lib, dev, R, H, grid):
+def test_queue_bit_identical_to_static_walk(lib, dev, knobs, R, H, grid):
     from inr_for_audio_amd._lib import new_tileq
-    ok(lib.siren_set_option(0, 256), lib)
-    ok(lib.siren_set_option(2, 4), lib)
-    ok(lib.siren_set_option(4, grid), lib)
+    _ping_pong_256(knobs, grid)
     inp = _inputs(dev, R, H, seed=R + H + grid)
     st = torch.cuda.current_stream()
     ref = _run_all(lib, dev, R, H, inp, st, None)
@@ -94,15 +100,13 @@ def test_queue_bit_identical_to_static_walk(lib, dev, R, H, grid):
 
 
 @pytest.mark.parametrize("fill", [1, -1, 1 << 30, "random"])
-def test_queue_set_handed_over_dirty(lib, dev, fill):
+def test_queue_set_handed_over_dirty(lib, dev, knobs, fill):
     """A counter set left non-zero (an aborted launch, a caller's garbage) must not change any
     output: every queue launch zeroes its set on the stream first, and every pulled tile id is
     range-checked, so no block can skip a tile or walk past its shard."""
     from inr_for_audio_amd._lib import TILEQ_INTS
     R, H, grid = 4096, 1024, 16
-    ok(lib.siren_set_option(0, 256), lib)
-    ok(lib.siren_set_option(2, 4), lib)
-    ok(lib.siren_set_option(4, grid), lib)
+    _ping_pong_256(knobs, grid)
     inp = _inputs(dev, R, H, seed=5)
     st = torch.cuda.current_stream()
     ref = _run_all(lib, dev, R, H, inp, st, None)
@@ -117,14 +121,12 @@ def test_queue_set_handed_over_dirty(lib, dev, fill):
 
 @pytest.mark.parametrize("act", ["snake", "tanh"])
 @pytest.mark.parametrize("grid", [8, 0])
-def test_queue_act_forward_bit_identical(lib, dev, act, grid):
+def test_queue_act_forward_bit_identical(lib, dev, knobs, act, grid):
     """The Snake / Tanh forward epilogues (modes NT_FWD_SNAKE / NT_FWD_TANH, with and without the
     head partials) from the queue == from the static walk."""
     R, H = 4096, 512
     code = {"snake": 1, "tanh": 2}[act]  # SIREN_ACT_SNAKE, SIREN_ACT_TANH
-    ok(lib.siren_set_option(0, 256), lib)
-    ok(lib.siren_set_option(2, 4), lib)
-    ok(lib.siren_set_option(4, grid), lib)
+    _ping_pong_256(knobs, grid)
     from inr_for_audio_amd._lib import new_tileq
     X, W, b, hw, *_ = _inputs(dev, R, H, seed=11)
     a = 0.5 + torch.rand(H, device=dev)
@@ -147,11 +149,9 @@ def test_queue_act_forward_bit_identical(lib, dev, act, grid):
     assert _same(run(new_tileq(dev)), ref)
 
 
-def test_queue_forward_vs_fp64(lib, dev):
+def test_queue_forward_vs_fp64(lib, dev, knobs):
     R, H = 4096, 512
-    ok(lib.siren_set_option(0, 256), lib)
-    ok(lib.siren_set_option(2, 4), lib)
-    ok(lib.siren_set_option(4, 16), lib)
+    _ping_pong_256(knobs, 16)
     from inr_for_audio_amd._lib import new_tileq
     X, W, b, hw, *_ = _inputs(dev, R, H, seed=3)
     Y, C, hp = _run_all(lib, dev, R, H, _inputs(dev, R, H, seed=3), torch.cuda.current_stream(), new_tileq(dev))[2:]
@@ -173,13 +173,13 @@ def _engine(dev, seed, H=512, n=65536):
     return SirenEngine(model, t, y, device=dev)
 
 
-def test_queue_every_mode_in_the_fused_step(lib, dev):
+def test_queue_every_mode_in_the_fused_step(lib, dev, knobs):
     """SIREN_OPT_NT_QUEUE 2 sends the dX / dX0 launches of siren_train_step through the batch's
     set too: the step's gradients are bit-identical to the static walk's (0) and the default (1)."""
     assert lib.siren_nt_tile(65536, 512) == 256
     grads = []
     for q in (0, 1, 2):
-        ok(lib.siren_set_option(8, q), lib)
+        knobs(Opt.NT_QUEUE, q)
         e = _engine(dev, 0)
         e.step()
         torch.cuda.synchronize()

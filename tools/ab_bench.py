@@ -41,7 +41,8 @@ def main():
         # libraries built from older commits (tools/build_at.py) may carry an earlier ABI
         libs[nm] = _lib.bind(os.path.join(ROOT, path), check_abi=False)
     for lib_ in libs.values():
-        assert lib_.siren_set_option(4, args.grid) == 0 and lib_.siren_set_option(8, args.queue) == 0
+        _lib.set_option(lib_, _lib.Opt.NT_GRID, args.grid)
+        _lib.set_option(lib_, _lib.Opt.NT_QUEUE, args.queue)
     dev = torch.device("cuda:0")
     R, H = args.rows, args.hidden
     s = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731

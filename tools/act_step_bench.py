@@ -19,6 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import inr_for_audio_amd  # noqa: E402,F401
 from inr_for_audio_amd import _lib  # noqa: E402
+from inr_for_audio_amd._lib import Opt  # noqa: E402
 from inr_for_audio_amd.engine import SirenEngine  # noqa: E402
 from inr_for_audio_amd.models import SirenWithSnakeTanh  # noqa: E402
 
@@ -53,32 +54,29 @@ def main():
         settings = [(int(p), int(f)) for p in args.pipes.split(",") for f in args.fuse.split(",")]
         for _ in range(args.rounds):
             for pipe, fuse in settings:
-                _lib.check(lib.siren_set_option(2, pipe), "nt pipe")
-                _lib.check(lib.siren_set_option(9, fuse), "head fuse")
-                eng.step()
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                for _ in range(args.steps):
+                with _lib.options(lib, {Opt.NT_PIPE: pipe, Opt.HEAD_FUSE: fuse}):
                     eng.step()
-                torch.cuda.synchronize()
-                times.setdefault(f"{name}_p{pipe}_f{fuse}", []).append((time.perf_counter() - t0) / args.steps * 1e3)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for _ in range(args.steps):
+                        eng.step()
+                    torch.cuda.synchronize()
+                    ms = (time.perf_counter() - t0) / args.steps * 1e3
+                times.setdefault(f"{name}_p{pipe}_f{fuse}", []).append(ms)
         for pipe, fuse in settings:
             key = f"{name}_p{pipe}_f{fuse}"
             out[key] = float(np.median(times[key]))
             if args.breakdown:
-                _lib.check(lib.siren_set_option(2, pipe), "nt pipe")
-                _lib.check(lib.siren_set_option(9, fuse), "head fuse")
                 _lib.check(lib.siren_profile_enable(4096), "profile_enable")
-                for _ in range(args.steps):
-                    eng.step()
-                torch.cuda.synchronize()
+                with _lib.options(lib, {Opt.NT_PIPE: pipe, Opt.HEAD_FUSE: fuse}):
+                    for _ in range(args.steps):
+                        eng.step()
+                    torch.cuda.synchronize()
                 for k, (ms, cnt) in _lib.profile_read().items():
                     if cnt:
                         out[f"{key}:{k}"] = ms / args.steps
                 _lib.check(lib.siren_profile_enable(0), "profile_disable")
         out[f"{name}:overflows"] = eng.guard_state()["overflows"]
-    lib.siren_set_option(2, -1)
-    lib.siren_set_option(9, 1)
     print(json.dumps({k: round(v, 3) if isinstance(v, float) else v for k, v in out.items()}))
 
 

@@ -113,16 +113,15 @@ def main():
         step("none")
     for _ in range(args.rounds):
         for mode, q in cases:
-            _lib.check(lib.siren_set_option(8, q), "queue option")
-            step(mode)
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(args.steps):
+            with _lib.options(lib, {_lib.Opt.NT_QUEUE: q}):
                 step(mode)
-            e1.record()
-            torch.cuda.synchronize()
-            times[(mode, q)].append(e0.elapsed_time(e1) / args.steps)
-    lib.siren_set_option(8, 1)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(args.steps):
+                    step(mode)
+                e1.record()
+                torch.cuda.synchronize()
+                times[(mode, q)].append(e0.elapsed_time(e1) / args.steps)
     res = {f"{mode}_q{q}": round(sorted(v)[len(v) // 2], 4) for (mode, q), v in times.items()}
     print(json.dumps({"rows": n, "buckets": len(eng._buckets), "standin_blocks": args.blocks,
                       "standin_reps": args.reps, "standin_all_buckets_ms": round(alone_ms, 4),

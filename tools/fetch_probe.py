@@ -39,20 +39,17 @@ def main():
     Y, C = torch.empty(R, H, dtype=torch.float16, device=dev), torch.empty(R, H, dtype=torch.float16, device=dev)
     part = torch.empty(R // 128, 3, H, device=dev)
     tq = _lib.new_tileq(dev)
-    _lib.check(lib.siren_set_option(8, args.queue), "queue")
-    _lib.check(lib.siren_set_option(6, args.diag), "diag")
     s = torch.cuda.current_stream().cuda_stream
-    for _ in range(args.reps):
-        if args.mode == "fwd":
-            st = lib.siren_inner_fwd(X.data_ptr(), W.data_ptr(), b.data_ptr(), ctypes.c_float(30.0), R, H,
-                                     Y.data_ptr(), C.data_ptr(), None, None, tq.data_ptr(), s)
-        else:
-            st = lib.siren_inner_bwd_dx(X.data_ptr(), W.data_ptr(), C.data_ptr(), ctypes.c_float(30.0), R, H, None,
-                                        Y.data_ptr(), part.data_ptr(), s)
-        _lib.check(st, args.mode)
-    torch.cuda.synchronize()
-    lib.siren_set_option(6, 0)
-    lib.siren_set_option(8, 1)
+    with _lib.options(lib, {_lib.Opt.NT_QUEUE: args.queue, _lib.Opt.NT_DIAG: args.diag}):
+        for _ in range(args.reps):
+            if args.mode == "fwd":
+                st = lib.siren_inner_fwd(X.data_ptr(), W.data_ptr(), b.data_ptr(), ctypes.c_float(30.0), R, H,
+                                         Y.data_ptr(), C.data_ptr(), None, None, tq.data_ptr(), s)
+            else:
+                st = lib.siren_inner_bwd_dx(X.data_ptr(), W.data_ptr(), C.data_ptr(), ctypes.c_float(30.0), R, H,
+                                            None, Y.data_ptr(), part.data_ptr(), s)
+            _lib.check(st, args.mode)
+        torch.cuda.synchronize()
 
 
 if __name__ == "__main__":

@@ -48,14 +48,11 @@ def main():
     clean = time.perf_counter() - t0
     out = {"rows": n, "clean_step_s": clean, "runs": []}
     for lim in [int(x) for x in args.limits.split(",")]:
-        assert diag.siren_set_option(10, (lim << 8) | 1) == 0
-        try:
+        with _lib.options(diag, {_lib.Opt.HB_FAULT: (lim << 8) | 1}):
             t0 = time.perf_counter()
             eng.step()
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-        finally:
-            assert diag.siren_set_option(10, 0) == 0
         stalls = int(eng.guard[5].item())
         eng.clear_stalls()
         polls = lim if lim > 0 else DEFAULT_LIMIT

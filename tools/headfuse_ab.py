@@ -45,26 +45,25 @@ def main():
     times = {1: [], 0: []}
     breakdown = {}
     for mode in (1, 0):
-        _lib.check(lib.siren_set_option(9, mode), "head fuse option")
         _lib.check(lib.siren_profile_enable(128 * 3), "profile_enable")
-        for _ in range(2):
-            eng.step()
-        torch.cuda.synchronize()
+        with _lib.options(lib, {_lib.Opt.HEAD_FUSE: mode}):
+            for _ in range(2):
+                eng.step()
+            torch.cuda.synchronize()
         breakdown[mode] = {k: {"launches_per_step": c / 2, "ms_per_step": ms / 2}
                            for k, (ms, c) in _lib.profile_read().items() if c}
         _lib.check(lib.siren_profile_enable(0), "profile_disable")
     for _ in range(args.rounds):
         for mode in (1, 0):
-            _lib.check(lib.siren_set_option(9, mode), "head fuse option")
-            eng.step()
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(args.steps):
+            with _lib.options(lib, {_lib.Opt.HEAD_FUSE: mode}):
                 eng.step()
-            e1.record()
-            torch.cuda.synchronize()
-            times[mode].append(e0.elapsed_time(e1) / args.steps)
-    lib.siren_set_option(9, 1)
+                torch.cuda.synchronize()
+                e0.record()
+                for _ in range(args.steps):
+                    eng.step()
+                e1.record()
+                torch.cuda.synchronize()
+                times[mode].append(e0.elapsed_time(e1) / args.steps)
     med = {m: sorted(v)[len(v) // 2] for m, v in times.items()}
     print(json.dumps({"rows": n, "hidden": args.hidden, "layers": args.layers, "steps_per_round": args.steps,
                       "rounds": args.rounds, "ms_per_step_median": {"fused": med[1], "unfused": med[0]},

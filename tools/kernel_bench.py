@@ -43,6 +43,7 @@ def main():
     import __graft_entry__ as ge
     ge.build()
     from inr_for_audio_amd import _lib
+    from inr_for_audio_amd._lib import Opt
     # a fresh handle: _lib.load() has already cached the product library (ge.build() loads it), so
     # until round 3 `--lib` silently timed the product library against itself
     lib = _lib.bind(os.path.join(ROOT, args.lib)) if args.lib else _lib.load()
@@ -167,29 +168,20 @@ def main():
                 torch.cuda.synchronize()
                 times[name].append(ev0.elapsed_time(ev1) / args.reps)
                 continue
-            _lib.check(lib.siren_set_option(6, diag.get(name, 0)), "diag option")
-            _lib.check(lib.siren_set_option(8, queue.get(name, 1)), "queue option")
-            _lib.check(lib.siren_set_option(4, grid.get(name, 0)), "grid option")
-            lib.siren_set_option(0, tile if not name.startswith("dw") else 0)
+            knobs = {Opt.NT_DIAG: diag.get(name, 0), Opt.NT_QUEUE: queue.get(name, 1), Opt.NT_GRID: grid.get(name, 0)}
             if name.startswith("dw"):
-                lib.siren_set_option(3, pipe)
+                knobs.update({Opt.NT_TILE: 0, Opt.TN_PIPE: pipe})
             else:
-                lib.siren_set_option(2, pipe if tile == 256 else 1)
-            for _ in range(1):
+                knobs.update({Opt.NT_TILE: tile, Opt.NT_PIPE: pipe if tile == 256 else 1})
+            with _lib.options(lib, knobs):
                 _lib.check(fn(), name)
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
-            for _ in range(args.reps):
-                fn()
-            ev1.record()
-            torch.cuda.synchronize()
-            times[name].append(ev0.elapsed_time(ev1) / args.reps)
-    lib.siren_set_option(6, 0)
-    lib.siren_set_option(8, 1)
-    lib.siren_set_option(4, 0)
-    lib.siren_set_option(0, 0)
-    lib.siren_set_option(2, -1)
-    lib.siren_set_option(3, -1)
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record()
+                for _ in range(args.reps):
+                    fn()
+                ev1.record()
+                torch.cuda.synchronize()
+                times[name].append(ev0.elapsed_time(ev1) / args.reps)
     out = {}
     for name, (tile, pipe, fn, fl) in cases.items():
         ts = sorted(times[name])

@@ -20,7 +20,7 @@ sys.path.insert(0, {root!r})
 from inr_for_audio_amd import _lib
 lib = _lib.load({lib!r})
 for opt, val in {opts!r}:
-    _lib.check(lib.siren_set_option(opt, val), "set_option")
+    _lib.set_option(lib, opt, val)
 sys.argv = ["bench.py", "--config", {cfg!r}, "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline",
             "--no-recon-snr"]
 runpy.run_path({bench!r}, run_name="__main__")

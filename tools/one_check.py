@@ -47,11 +47,10 @@ def main():
 
     def fwd(pipe, grid, X, W, b, Y, C):
         R, H = X.shape
-        _lib.check(lib.siren_set_option(2, pipe), "pipe")
-        _lib.check(lib.siren_set_option(4, grid), "grid")
-        _lib.check(lib.siren_set_option(0, 256), "tile")
-        return lib.siren_inner_fwd(X.data_ptr(), W.data_ptr(), b.data_ptr(), ctypes.c_float(30.0), R, H,
-                                   Y.data_ptr(), C.data_ptr(), None, None, tq.data_ptr(), s())
+        # the launch reads the knobs on the host, so they need not outlive the call
+        with _lib.options(lib, {_lib.Opt.NT_PIPE: pipe, _lib.Opt.NT_GRID: grid, _lib.Opt.NT_TILE: 256}):
+            return lib.siren_inner_fwd(X.data_ptr(), W.data_ptr(), b.data_ptr(), ctypes.c_float(30.0), R, H,
+                                       Y.data_ptr(), C.data_ptr(), None, None, tq.data_ptr(), s())
 
     out = {"parity": [], "timing": {}}
     if not args.skip_parity:
@@ -110,9 +109,6 @@ def main():
         print(shape, json.dumps(res), flush=True)
         del X, W, b, Y, C
         torch.cuda.empty_cache()
-    lib.siren_set_option(2, -1)
-    lib.siren_set_option(4, 0)
-    lib.siren_set_option(0, 0)
     print(json.dumps(out, indent=1))
 
 

@@ -70,7 +70,7 @@ def main():
             sb.wait_stream(cur)
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             if c is None or isinstance(c, str):
-                lib.siren_set_option(4, 0)
+                _lib.set_option(lib, _lib.Opt.NT_GRID, 0)
                 ev0.record(sa)
                 for _ in range(args.reps):
                     if c in (None, "dx"):
@@ -80,7 +80,7 @@ def main():
                 ev1.record(sa)
             else:
                 cap, sp = c
-                lib.siren_set_option(4, cap)
+                _lib.set_option(lib, _lib.Opt.NT_GRID, cap)
                 ev0.record(sa)
                 sb.wait_event(ev0)
                 for _ in range(args.reps):
@@ -96,7 +96,7 @@ def main():
                 ev1.record(sa)
             torch.cuda.synchronize()
             times[name].append(ev0.elapsed_time(ev1) / args.reps)
-    lib.siren_set_option(4, 0)
+    _lib.set_option(lib, _lib.Opt.NT_GRID, _lib.OPT_DEFAULTS[_lib.Opt.NT_GRID])
     out = {k: {"median_ms": sorted(v)[len(v) // 2], "min_ms": min(v)} for k, v in times.items()}
     print(json.dumps({"rows": R, "hidden": H, "default_splits": full_splits, "results": out}, indent=1))
 
