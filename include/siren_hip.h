@@ -53,7 +53,7 @@ int siren_abi_version(void);
 const char* siren_build_id(void);
 /* sizeof of the ABI structs, for binding checks: 0 siren_net, 1 siren_grads, 2 siren_batch,
  * 3 siren_opt_state, 4 siren_kan_net, 5 siren_kan_grads, 6 siren_kan_batch, 7 siren_guard,
- * 8 siren_spectral (-1: unknown) */
+ * 8 siren_spectral, 9 siren_spectral_mr (-1: unknown) */
 int64_t siren_struct_size(int32_t which);
 const char* siren_status_string(int status);
 
@@ -403,6 +403,53 @@ typedef struct siren_spectral {
 } siren_spectral;
 int siren_train_step_spectral(const siren_net* net, const siren_grads* grads, siren_batch* batch,
                               const siren_spectral* loss, void* stream);
+
+/* ---- Multi-resolution STFT loss (run.py:127 auraloss.freq.MultiResolutionSTFTLoss(perceptual_weighting=
+ * False), the term the reference's 'mrstft' sweeps were fitted with; evaluated at run.py:160) ----------
+ * Restated from the published auraloss 0.4.0 defaults: three transforms r = 0, 1, 2 with
+ *   n_fft 1024 / 2048 / 512, hop 120 / 240 / 50, win_length 600 / 1200 / 240 (periodic Hann, zero-padded
+ *   and centred in the n_fft frame; center, reflect): T_r = 1 + n / hop frames of 513 / 1025 / 257 bins
+ *   L_r as L_stft above;  L_mrstft = (L_0 + L_1 + L_2) / 3
+ * Only the win_length taps that carry a non-zero window enter the GEMM: per resolution `basis` holds
+ * the rows k' = tap - (n_fft - win) / 2 < KWP (win rounded up to 16: 608 / 1200 / 240, zero past win) of
+ * v[c][k'][bin] (bin < NBP = 528 / 1040 / 272, zero past the last bin) as [c][k' / 16][bin][k' % 16],
+ * then as [c][bin / 16][k'][bin % 16]; resolution 0's 2 * 2 * KWP * NBP floats first, then 1, then 2.
+ * n > 1024 (reflect padding of the 2048-point frame is undefined below; else SIREN_ERR_SHAPE), n <= 2^30. */
+/* run.py:127, :160 frames of resolution r of an n-sample signal (0: n <= 1024 or r not 0..2) */
+int64_t siren_mrstft_frames(int64_t n, int32_t r);
+int64_t siren_mrstft_basis_floats(void);
+/* run.py:127 the three transforms' tables, fp64 rounded once -- `basis_host` is a HOST buffer of
+ * siren_mrstft_basis_floats() floats (copy it to the device) */
+int siren_mrstft_basis_fill(float* basis_host);
+/* floats of siren_spectral_mr.ws / `ws` below for n samples in a batch of `rows` rows (-1: bad shape) */
+int64_t siren_mrstft_workspace_floats(int32_t n, int32_t rows);
+/* float offset of a piece of resolution r (-1: unknown): 0 re [T_r][NBP], 1 im, 2 y_mag, 3 log y_mag,
+ * 4 dF [T_r][KWP], 5 the scalars [32] (the same for every r): 8 per resolution {S1, sum|dlog|, Sy, L_r,
+ * 1/(sqrt S1 sqrt Sy), 1/(T_r bins), -, -}, then {L_mrstft, point loss, mixed loss} */
+int64_t siren_mrstft_ws_offset(int32_t n, int32_t rows, int32_t r, int32_t which);
+/* run.py:160 magnitude side, one launch per resolution: target 0 -- re / im of x and the per-block
+ * partials against the stored target; target 1 -- y_mag, log y_mag and Sy of the target (once) */
+int siren_mrstft_forward(const float* x, int32_t n, int32_t rows, const float* basis, float* ws, int32_t target,
+                         void* stream);
+/* run.py:160 the finished scalars (fp64 on the device) from siren_mrstft_forward's partials:
+ * loss[0] = L_mrstft, loss[1..3] = L_0, L_1, L_2 (device) */
+int siren_mrstft_loss(int32_t n, int32_t rows, float* ws, float* loss, void* stream);
+/* autograd of run.py:160 after siren_mrstft_forward + siren_mrstft_loss: g [n] = dL_mrstft/dx (three
+ * transposed GEMMs, then one fixed-order gather: frames ascending, reflected images, resolutions
+ * 0, 1, 2 each times 1/3; no atomics) */
+int siren_mrstft_loss_bwd(int32_t n, int32_t rows, const float* basis, float* ws, float* g, void* stream);
+
+/* run.py:158-185 with loss = (1 - alpha) {MSE | L1 | SNR} + alpha L_mrstft (run.py:127, :160): composed
+ * exactly as siren_train_step_spectral (unfused last layer, the mixed g left in batch.g, zero on pad
+ * rows, the finished loss in grads.sse[0]); alpha != 0 needs n_valid > 1024. */
+typedef struct siren_spectral_mr {
+  double alpha;          /* weight of the multi-resolution STFT term */
+  const float* basis;    /* siren_mrstft_basis_floats() floats from siren_mrstft_basis_fill (alpha != 0) */
+  float* ws;             /* siren_mrstft_workspace_floats(n_valid, rows) floats; with alpha != 0 its target
+                            side set once by siren_mrstft_forward(target, ..., 1) */
+} siren_spectral_mr;
+int siren_train_step_mrstft(const siren_net* net, const siren_grads* grads, siren_batch* batch,
+                            const siren_spectral_mr* loss, void* stream);
 
 /* autograd addmm dW: slab[s] = partial dZ^T Y over coordinate slice s, tile edge 128/256
  * (0 = siren_dw_tile(rows, hidden)); siren_dw_reduce must get the same tile. */

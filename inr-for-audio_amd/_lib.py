@@ -93,6 +93,11 @@ class SirenSpectral(ctypes.Structure):
     _fields_ = [("alpha", ctypes.c_double), ("stft_basis", _p), ("stft_ws", _p)]
 
 
+class SirenSpectralMR(ctypes.Structure):
+    """siren_spectral_mr: the multi-resolution STFT term's weight, tables and workspace (run.py:127, :160)."""
+    _fields_ = [("alpha", ctypes.c_double), ("basis", _p), ("ws", _p)]
+
+
 KAN_MAX_LAYERS = 8
 
 
@@ -168,6 +173,16 @@ _SIGS = {
     "siren_stft_forward": (ctypes.c_int, [_p, _i32, _i32, _p, _p, _i32, _p]),
     "siren_stft_loss": (ctypes.c_int, [_i32, _i32, _p, _p, _p]),
     "siren_stft_loss_bwd": (ctypes.c_int, [_i32, _i32, _p, _p, _p, _p]),
+    "siren_mrstft_frames": (_i64, [_i64, _i32]),
+    "siren_mrstft_basis_floats": (_i64, []),
+    "siren_mrstft_basis_fill": (ctypes.c_int, [_p]),
+    "siren_mrstft_workspace_floats": (_i64, [_i32, _i32]),
+    "siren_mrstft_ws_offset": (_i64, [_i32, _i32, _i32, _i32]),
+    "siren_mrstft_forward": (ctypes.c_int, [_p, _i32, _i32, _p, _p, _i32, _p]),
+    "siren_mrstft_loss": (ctypes.c_int, [_i32, _i32, _p, _p, _p]),
+    "siren_mrstft_loss_bwd": (ctypes.c_int, [_i32, _i32, _p, _p, _p, _p]),
+    "siren_train_step_mrstft": (ctypes.c_int, [ctypes.POINTER(SirenNet), ctypes.POINTER(SirenGrads),
+                                               ctypes.POINTER(SirenBatch), ctypes.POINTER(SirenSpectralMR), _p]),
     "siren_snr_loss": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _p, _p, _p]),
     "siren_inner_bwd_dw": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "siren_dw_reduce": (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _i32, _p, _p]),
@@ -204,7 +219,7 @@ _SIGS = {
 }
 
 STRUCTS = [SirenNet, SirenGrads, SirenBatch, SirenOptState, SirenKanNet, SirenKanGrads, SirenKanBatch, SirenGuard,
-           SirenSpectral]
+           SirenSpectral, SirenSpectralMR]
 
 PROF_KINDS = ["first_fwd", "inner_fwd", "head", "bwd_dw", "bwd_dx", "bwd_dx0", "reduce", "update",
               "kan_fwd", "kan_dw", "kan_dx", "kan_misc", "head_fwd", "loss"]

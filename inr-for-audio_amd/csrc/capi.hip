@@ -137,8 +137,9 @@ bool spectral(const siren_batch* b, const siren_spectral* sp) { return (sp && sp
 
 // loss_step: the call evaluates the loss (siren_train_step*), so loss_mode 2 / alpha need their workspace;
 // siren_backward takes dLoss/dout as given and ignores both
+// mr: sp is a siren_spectral_mr's fields (run.py:127), whose transforms need n_valid > 1024
 int check_batch(const siren_net* n, const siren_batch* b, bool train, const siren_spectral* sp = nullptr,
-                bool loss_step = false) {
+                bool loss_step = false, bool mr = false) {
   if (!b) return SIREN_ERR_NULL;
   if (b->rows <= 0 || b->rows % SIREN_ROW_TILE || b->n_valid < 0 || b->n_valid > b->rows)
     return SIREN_ERR_SHAPE;
@@ -164,6 +165,7 @@ int check_batch(const siren_net* n, const siren_batch* b, bool train, const sire
     if (b->n_total != (double)b->n_valid) return SIREN_ERR_CONFIG;
     if (b->n_valid < 1 || b->n_valid > kStftMaxN || (sp->alpha != 0.0 && stft_frames(b->n_valid) < 1))
       return SIREN_ERR_SHAPE;
+    if (mr && sp->alpha != 0.0 && mrstft_frames(b->n_valid, 0) < 1) return SIREN_ERR_SHAPE;
   }
   return SIREN_OK;
 }
@@ -281,6 +283,7 @@ int64_t siren_struct_size(int32_t which) {
     case 6: return sizeof(siren_kan_batch);
     case 7: return sizeof(siren_guard);
     case 8: return sizeof(siren_spectral);
+    case 9: return sizeof(siren_spectral_mr);
   }
   return -1;
 }
@@ -496,11 +499,38 @@ static int run_spectral_step(const siren_net* net, const siren_grads* gr, siren_
   return backward_from_g(net, gr, &bb, s);
 }
 
+// run.py:158-185 with the multi-resolution term (run.py:127): run_spectral_step with the kernels of
+// mrstft.hip in the place of stft.hip's (sp: the siren_spectral_mr's alpha, basis and ws)
+static int run_mrstft_step(const siren_net* net, const siren_grads* gr, siren_batch* b, const siren_spectral* sp,
+                           float gfac, hipStream_t s) {
+  const int R = b->rows, n = b->n_valid;
+  const bool stft = sp->alpha != 0.0;
+  const MrWs w = mrstft_ws_map(sp->stft_ws, n, R);
+  SIREN_TRY(run_forward(net, b, s));
+  SIREN_PROF(SIREN_PROF_HEAD, s, head_loss(b->head_part, head_parts(R, net->hidden), R, net->b_head, b->target, n, gfac,
+                                           b->out, b->g, b->sse_part, b->gsum_part, b->gmax_part, s, net->head_omega,
+                                           b->loss_mode == 1 ? 1 : 0));
+  if (b->loss_mode == 2) SIREN_PROF(SIREN_PROF_LOSS, s, snr_sums(b->out, b->target, n, w.pt, s));
+  if (stft) SIREN_PROF(SIREN_PROF_LOSS, s, mrstft_forward(b->out, n, sp->stft_basis, w, false, s));
+  // the point loss's scalars (stft.hip), then the three terms, their mean and the mix
+  SIREN_PROF(SIREN_PROF_LOSS, s, loss_finish(w.pt, n, b->sse_part, bands(R), b->loss_mode, 0.0, b->n_total, false,
+                                             nullptr, s));
+  SIREN_PROF(SIREN_PROF_LOSS, s, mrstft_finish(w, stft, b->loss_mode, sp->alpha, gr->sse, false, s));
+  if (stft) SIREN_PROF(SIREN_PROF_LOSS, s, mrstft_backward(sp->stft_basis, w, s));
+  SIREN_PROF(SIREN_PROF_LOSS, s, mrstft_mix(b->out, b->target, n, R, w, b->loss_mode, sp->alpha, gfac, b->g, s));
+  siren_batch bb = *b;
+  if (net->head_omega > 0.f) {
+    SIREN_TRY(hipMemcpyAsync(w.pt.gchain, b->g, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, s));
+    bb.g = w.pt.gchain;
+  }
+  return backward_from_g(net, gr, &bb, s);
+}
+
 static int train_step(const siren_net* net, const siren_grads* gr, siren_batch* b, const siren_spectral* sp,
-                      void* stream) {
+                      void* stream, bool mr = false) {
   int st = check_net(net);
   if (st) return st;
-  if ((st = check_batch(net, b, true, sp, true))) return st;
+  if ((st = check_batch(net, b, true, sp, true, mr))) return st;
   if ((st = check_grads(net, gr))) return st;
   if (!gr->sse) return SIREN_ERR_NULL;
   hipStream_t s = S(stream);
@@ -508,7 +538,7 @@ static int train_step(const siren_net* net, const siren_grads* gr, siren_batch* 
 
   SIREN_TRY(zero_grads(gr, b, s));
   const float gfac = loss_gfac(b->loss_mode, b->n_total);
-  if (spectral(b, sp)) return run_spectral_step(net, gr, b, sp, gfac, s);
+  if (spectral(b, sp)) return mr ? run_mrstft_step(net, gr, b, sp, gfac, s) : run_spectral_step(net, gr, b, sp, gfac, s);
   const bool hb = head_fused(net, b, s);
   if (hb) {
     // the fused head needs the backward scale S before the forward.  Sine / Tanh last layer
@@ -547,6 +577,13 @@ int siren_train_step_spectral(const siren_net* net, const siren_grads* gr, siren
                               const siren_spectral* loss, void* stream) {
   if (!loss) return SIREN_ERR_NULL;
   return train_step(net, gr, b, loss, stream);
+}
+
+int siren_train_step_mrstft(const siren_net* net, const siren_grads* gr, siren_batch* b,
+                            const siren_spectral_mr* loss, void* stream) {
+  if (!loss) return SIREN_ERR_NULL;
+  const siren_spectral sp = {loss->alpha, loss->basis, loss->ws};
+  return train_step(net, gr, b, &sp, stream, true);
 }
 
 int siren_backward(const siren_net* net, const siren_grads* gr, siren_batch* b, void* stream) {
@@ -856,6 +893,59 @@ int siren_snr_loss(const float* x, const float* y, int32_t n, int32_t rows, floa
   SIREN_TRY(snr_sums(x, y, n, w, s));
   SIREN_TRY(loss_finish(w, n, nullptr, 0, 2, 0.0, (double)n, false, loss, s));
   return (int)loss_mix(x, y, n, n, w, 2, 0.0, 0.f, g, s);
+}
+
+// ---- multi-resolution STFT loss (run.py:127, :160) --------------------------------------------
+// n samples in a batch of `rows` rows; `stft`: the transforms need n > 1024
+static int mrstft_shape(int32_t n, int32_t rows, bool stft) {
+  if (n < 1 || n > kStftMaxN || rows < n || (stft && mrstft_frames(n, 0) < 1)) return SIREN_ERR_SHAPE;
+  return SIREN_OK;
+}
+
+int64_t siren_mrstft_frames(int64_t n, int32_t r) { return n >= 0 && n <= kStftMaxN ? mrstft_frames(n, r) : 0; }
+
+int64_t siren_mrstft_basis_floats(void) { return mrstft_basis_floats(); }
+
+int siren_mrstft_basis_fill(float* basis_host) {
+  if (!basis_host) return SIREN_ERR_NULL;
+  mrstft_basis_fill(basis_host);
+  return SIREN_OK;
+}
+
+int64_t siren_mrstft_workspace_floats(int32_t n, int32_t rows) {
+  return mrstft_shape(n, rows, false) ? -1 : mrstft_ws_floats(n, rows);
+}
+
+int64_t siren_mrstft_ws_offset(int32_t n, int32_t rows, int32_t r, int32_t which) {
+  if (mrstft_shape(n, rows, false) || r < 0 || r >= kMrRes) return -1;
+  const MrWs w = mrstft_ws_map(nullptr, n, rows);
+  const float* const p[6] = {w.re[r], w.im[r], w.ymag[r], w.ylog[r], w.dF[r], w.scal};
+  return which >= 0 && which < 6 ? (int64_t)((uintptr_t)p[which] / sizeof(float)) : -1;
+}
+
+int siren_mrstft_forward(const float* x, int32_t n, int32_t rows, const float* basis, float* ws, int32_t target,
+                         void* stream) {
+  if (!x || !basis || !ws) return SIREN_ERR_NULL;
+  if (target < 0 || target > 1) return SIREN_ERR_CONFIG;
+  int st = mrstft_shape(n, rows, true);
+  if (st) return st;
+  return (int)mrstft_forward(x, n, basis, mrstft_ws_map(ws, n, rows), target != 0, S(stream));
+}
+
+int siren_mrstft_loss(int32_t n, int32_t rows, float* ws, float* loss, void* stream) {
+  if (!ws || !loss) return SIREN_ERR_NULL;
+  int st = mrstft_shape(n, rows, true);
+  if (st) return st;
+  return (int)mrstft_finish(mrstft_ws_map(ws, n, rows), true, -1, 1.0, loss, true, S(stream));
+}
+
+int siren_mrstft_loss_bwd(int32_t n, int32_t rows, const float* basis, float* ws, float* g, void* stream) {
+  if (!basis || !ws || !g) return SIREN_ERR_NULL;
+  int st = mrstft_shape(n, rows, true);
+  if (st) return st;
+  const MrWs w = mrstft_ws_map(ws, n, rows);
+  SIREN_TRY(mrstft_backward(basis, w, S(stream)));
+  return (int)mrstft_gather(n, w, g, S(stream));
 }
 
 int siren_inner_bwd_dw(const uint16_t* Y, const uint16_t* dZ, int32_t rows, int32_t hidden,

@@ -218,6 +218,13 @@ struct StftWs {
   float* gchain;        // [rows] dLoss/d(head linear output) of a last_linear=False step
   int T, npart;
 };
+// scal[] slots (StftWs::scal)
+enum { SC_S1 = 0, SC_SL = 1, SC_SY = 2, SC_LSTFT = 3, SC_C1 = 4, SC_C2 = 5, SC_MX = 6, SC_MY = 7, SC_SYC = 8,
+       SC_SR = 9, SC_LSNR = 10, SC_FSNR = 11, SC_LPOINT = 12, SC_LOSS = 13 };
+// part[] rows (StftWs::part, each npart floats)
+// (the SNR sums are kept as a float pair hi + lo: L_snr crosses zero where the fit's residual
+// equals the signal, and an fp32 sum's 2^-24 is 1e-5 of a loss of 0.007 dB)
+enum { PT_S1 = 0, PT_SL = 1, PT_SX = 2, PT_SYM = 3, PT_SYC = 4, PT_SR = 5, PT_SYC_LO = 6, PT_SR_LO = 7, PT_ROWS = 8 };
 int64_t stft_frames(int64_t n);   // 1 + n / 256 (0: n <= 512, reflect padding undefined)
 int64_t stft_basis_floats();
 void stft_basis_fill(float* host);  // both tables, fp64 on the host rounded once
@@ -236,6 +243,39 @@ hipError_t stft_gather(int n, const StftWs& w, float* g_stft, hipStream_t s);  /
 // g[rows] = (1 - alpha) g_point + alpha gather(dF), 0 on pad rows
 hipError_t loss_mix(const float* out, const float* y, int n, int rows, const StftWs& w, int loss_mode, double alpha,
                     float gfac, float* g, hipStream_t s);
+
+// Multi-resolution STFT loss (mrstft.hip; run.py:127, :160): three transforms (n_fft / hop / win
+// 1024 / 120 / 600, 2048 / 240 / 1200, 512 / 50 / 240), L = (L_0 + L_1 + L_2) / 3.  One caller-owned
+// fp32 workspace of mrstft_ws_floats(n, rows) floats, carved up by mrstft_ws_map
+constexpr int kMrRes = 3, kMrMinN = 1024, kMrScalFloats = 32;
+// scal[]: MR_SLOTS floats per resolution, then the mean, the point loss and the mixed loss
+enum { MR_S1 = 0, MR_SL = 1, MR_SY = 2, MR_L = 3, MR_C1 = 4, MR_C2 = 5, MR_SLOTS = 8, MR_MEAN = 0, MR_POINT = 1, MR_LOSS = 2 };
+struct MrWs {
+  float *re[kMrRes], *im[kMrRes];       // [T_r][bins padded to 16] transform of the model output
+  float *ymag[kMrRes], *ylog[kMrRes];   // the target's magnitudes and their logs (constant)
+  float* dF[kMrRes];                    // [T_r][win padded to 16] gradient of the frames over the window's support
+  float* part[kMrRes];                  // [2][npart_r] per-block partial sums (S1 / Sy, sum|dlog|)
+  int T[kMrRes], npart[kMrRes];
+  float* scal;                          // [32] finished scalars (MR_*)
+  StftWs pt;                            // the point loss's partials, scalars (SC_*) and gchain; no frames
+};
+int64_t mrstft_frames(int64_t n, int r);   // 1 + n / hop_r (0: n <= 1024, reflect padding of 2048 undefined)
+int64_t mrstft_basis_floats();
+void mrstft_basis_fill(float* host);       // per resolution both table layouts, fp64 on the host rounded once
+int64_t mrstft_ws_floats(int n, int rows);
+MrWs mrstft_ws_map(float* ws, int n, int rows, int64_t* total = nullptr);
+// target: ymag, ylog and Sy per resolution; else re, im and the partials of S1 and sum|dlog|
+hipError_t mrstft_forward(const float* x, int n, const float* basis, const MrWs& w, bool target, hipStream_t s);
+// the finished scalars; stft: the partials of mrstft_forward are reduced; loss_mode >= 0: the point loss
+// is w.pt's (loss_finish), -1: none (loss = L_mrstft); loss_out[0] (nullable) <- the mixed loss, terms:
+// loss_out[1..3] <- L_0, L_1, L_2
+hipError_t mrstft_finish(const MrWs& w, bool stft, int loss_mode, double alpha, float* loss_out, bool terms,
+                         hipStream_t s);
+hipError_t mrstft_backward(const float* basis, const MrWs& w, hipStream_t s);   // -> w.dF
+hipError_t mrstft_gather(int n, const MrWs& w, float* g, hipStream_t s);        // dF -> dL_mrstft/dx [n]
+// g[rows] = (1 - alpha) g_point + alpha gather(dF), 0 on pad rows
+hipError_t mrstft_mix(const float* out, const float* y, int n, int rows, const MrWs& w, int loss_mode, double alpha,
+                      float gfac, float* g, hipStream_t s);
 
 // KAN (kan.hip): fp32, grid_size 5, spline_order 3 (9 A-columns per input)
 // fused layer kernels (the bases are recomputed in LDS; A and dA never reach HBM)

@@ -58,14 +58,6 @@ constexpr int SF_BGY = SF_N / 16 / (4 * SF_BWT);        // backward grid.y (4)
 constexpr float SF_EPS = 1e-8f;
 constexpr size_t SF_TAB = (size_t)2 * SF_N * SF_NBP;    // floats of one table
 
-// scal[] slots (StftWs::scal)
-enum { SC_S1 = 0, SC_SL = 1, SC_SY = 2, SC_LSTFT = 3, SC_C1 = 4, SC_C2 = 5, SC_MX = 6, SC_MY = 7, SC_SYC = 8,
-       SC_SR = 9, SC_LSNR = 10, SC_FSNR = 11, SC_LPOINT = 12, SC_LOSS = 13 };
-// part[] rows (StftWs::part, each npart floats)
-// (the SNR sums are kept as a float pair hi + lo: L_snr crosses zero where the fit's residual
-// equals the signal, and an fp32 sum's 2^-24 is 1e-5 of a loss of 0.007 dB)
-enum { PT_S1 = 0, PT_SL = 1, PT_SX = 2, PT_SYM = 3, PT_SYC = 4, PT_SR = 5, PT_SYC_LO = 6, PT_SR_LO = 7, PT_ROWS = 8 };
-
 __device__ __forceinline__ f32x4 sf_mfma(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }

@@ -254,6 +254,18 @@ def stft_basis(device) -> torch.Tensor:
     return host.to(device)
 
 
+STFT_LOSSES = ("stft", "mrstft")   # run.py:127-128: the single STFTLoss() or MultiResolutionSTFTLoss()
+
+
+def mrstft_basis(device) -> torch.Tensor:
+    """The multi-resolution STFT loss's tables (include/siren_hip.h "Multi-resolution STFT loss"): the three
+    transforms' windowed cos / -sin rows over each window's support, fp64 on the host rounded once."""
+    lib = _lib.load()
+    host = torch.empty(int(lib.siren_mrstft_basis_floats()), dtype=torch.float32)
+    check(lib.siren_mrstft_basis_fill(host.data_ptr()), "siren_mrstft_basis_fill")
+    return host.to(device)
+
+
 def new_guard(device) -> torch.Tensor:
     """A zeroed siren_guard with the default headroom (include/siren_hip.h): flag, headroom, clean,
     overflows, headroom0, stalls."""
@@ -494,7 +506,7 @@ class SirenEngine(FitEngine):
                  min_lr: float = 1e-6, factor: float = 0.8, patience: int = 200,
                  n_total: int | None = None, micro_batch: int = 1 << 20, hist_cap: int = 20000,
                  splits: int | None = None, device=None, loss_mode: str = "mse", encoding=None,
-                 alpha: float = 0.0):
+                 alpha: float = 0.0, stft_loss: str = "stft"):
         """`encoding` (encoding.GaussianEncoding, run.py:141-144): `coords` stay the raw [N][1]
         coordinates and model.in_features must be 2 * encoded_size -- the first layer's kernel
         builds the encoded input itself (training and infer()).
@@ -502,9 +514,16 @@ class SirenEngine(FitEngine):
         `alpha` and loss_mode='snr' (run.py:126-128, :160-169): loss = (1 - alpha) {MSE | L1 | SNR} +
         alpha L_stft, the two auraloss terms restated from their published definitions (csrc/stft.hip).
         Both see the flattened signal as a whole, so such an engine takes one micro-batch on one rank
-        and more than 512 samples when alpha > 0; its last layer runs unfused."""
+        and more than 512 samples when alpha > 0; its last layer runs unfused.
+
+        `stft_loss` (run.py:127-128): 'stft' is the single 1024 / 256 transform, 'mrstft' the mean of the
+        three of auraloss's MultiResolutionSTFTLoss() defaults (csrc/mrstft.hip), which needs more than
+        1024 samples when alpha > 0."""
         if loss_mode not in LOSS_MODES:
             raise NotImplementedError(f"loss_mode={loss_mode!r}: the HIP path has {sorted(LOSS_MODES)}")
+        if stft_loss not in STFT_LOSSES:
+            raise ValueError(f"stft_loss={stft_loss!r}: one of {STFT_LOSSES} (run.py:127-128)")
+        self.stft_loss = stft_loss
         self.alpha = float(alpha)
         if not 0.0 <= self.alpha <= 1.0:
             raise ValueError(f"alpha={alpha!r} must be in [0, 1] (run.py:161-169 mixes (1 - alpha) and alpha)")
@@ -522,6 +541,9 @@ class SirenEngine(FitEngine):
             if self.alpha != 0.0 and n_sig <= 512:
                 raise ValueError(f"the STFT loss needs more than 512 samples (reflect padding of a 1024-point "
                                  f"frame is undefined for {n_sig}; torch.stft refuses it too)")
+            if self.alpha != 0.0 and stft_loss == "mrstft" and n_sig <= 1024:
+                raise ValueError(f"the multi-resolution STFT loss needs more than 1024 samples (reflect padding of "
+                                 f"its 2048-point frame is undefined for {n_sig}; torch.stft refuses it too)")
         super().__init__(device)
         self.model = model
         self.encoding = encoding
@@ -596,6 +618,17 @@ class SirenEngine(FitEngine):
         once, they never change -- the target's magnitudes, their logs and Sy."""
         lib, b, n, dev = self.lib, self.batches[0], self.n_local, self.device
         assert self.n_micro == 1 and n == self.n_total
+        if self.stft_loss == "mrstft":   # run.py:127: the same pieces per resolution (csrc/mrstft.hip)
+            self.stft_ws = torch.zeros(int(lib.siren_mrstft_workspace_floats(n, self.rows)), dtype=torch.float32,
+                                       device=dev)
+            self.spectral_struct = sp = _lib.SirenSpectralMR()
+            sp.alpha, sp.ws = self.alpha, ptr(self.stft_ws)
+            if self.alpha != 0.0:
+                self.stft_basis = mrstft_basis(dev)
+                sp.basis = ptr(self.stft_basis)
+                check(lib.siren_mrstft_forward(ptr(self.target), n, self.rows, ptr(self.stft_basis),
+                                               ptr(self.stft_ws), 1, self._stream()), "siren_mrstft_forward")
+            return
         self.stft_ws = torch.zeros(int(lib.siren_stft_workspace_floats(n, self.rows)), dtype=torch.float32,
                                    device=dev)
         self.spectral_struct = sp = _lib.SirenSpectral()
@@ -636,6 +669,11 @@ class SirenEngine(FitEngine):
     def _launch_grads(self):
         s = self._stream()
         for b in self.batches:
+            if self.spectral and self.stft_loss == "mrstft":   # run.py:127, :160-169
+                check(self.lib.siren_train_step_mrstft(ctypes.byref(self.net), ctypes.byref(self.grad_struct),
+                                                       ctypes.byref(b), ctypes.byref(self.spectral_struct), s),
+                      "siren_train_step_mrstft")
+                continue
             if self.spectral:   # run.py:160-169: the STFT / SNR step (one batch: the whole signal)
                 check(self.lib.siren_train_step_spectral(ctypes.byref(self.net), ctypes.byref(self.grad_struct),
                                                          ctypes.byref(b), ctypes.byref(self.spectral_struct), s),

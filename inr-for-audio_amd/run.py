@@ -82,7 +82,8 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
           last_linear=True, hidden_omega=30, a_initial=0.5, total_steps=20000, learning_rate=1e-3,
           min_learning_rate=1e-6, alpha=0.0, prev_ckpt_path=None, visualization=False, *,
           filename=None, data_dir="data", seed=None, micro_batch=1 << 20, use_graph=True,
-          device=None, verbose=False, multichannel=False, patience=200, restated_losses=False):
+          device=None, verbose=False, multichannel=False, patience=200, restated_losses=False,
+          stft_loss="stft"):
     """Fit one clip; returns the checkpoint path (run.py:400).  Extra keyword-only knobs:
     ``filename`` (default ``{data_dir}/{inst}.wav`` as run.py:33), ``seed`` (torch.manual_seed
     before model construction), ``micro_batch`` (rows per fused micro-batch), ``use_graph``
@@ -92,7 +93,10 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     project's restatement of auraloss's STFTLoss / SNRLoss defaults -- run.py:126-128, :160-169 --
     instead of raising; parity is to the published formula, not to an installed auraloss.  For
     method 'wave' and 'mdct' of the MLP, the whole signal in one micro-batch on one GPU; with 'snr'
-    the loss is negative, so the dB history is NaN as in the reference, run.py:180)."""
+    the loss is negative, so the dB history is NaN as in the reference, run.py:180),
+    ``stft_loss`` (with ``restated_losses``: 'stft', the single STFTLoss() of run.py:128, or 'mrstft',
+    the MultiResolutionSTFTLoss() of run.py:127 -- more than 1024 samples; recorded in parameters.json
+    only when it is not 'stft')."""
     if method not in ("wave", "mdct"):
         raise ValueError("specify the correct fitting method as wave or mdct (run.py:77-78)")
     if method == "mdct" and bwe:
@@ -105,6 +109,8 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     if loss_mode not in ("mse", "mae", "snr") or (spectral and not restated_losses):
         raise NotImplementedError("HIP path implements loss_mode 'mse' / 'mae' with alpha=0 (run.py:161-169); "
                                   "restated_losses=True fits 'snr' and alpha > 0 with the restated auraloss terms")
+    if stft_loss not in ("stft", "mrstft"):
+        raise ValueError(f"stft_loss={stft_loss!r}: 'stft' (run.py:128) or 'mrstft' (run.py:127)")
     if spectral and (multichannel or arch != "mlp"):
         raise NotImplementedError("restated_losses fits the waveform / MDCT MLP (no multichannel, no arch='kan')")
     if arch == "kan" and loss_mode != "mse":
@@ -141,6 +147,10 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         ground_truth = torch.from_numpy(np.ascontiguousarray(pixels))
         input_dimension = 2
 
+    if alpha != 0.0 and stft_loss == "mrstft" and ground_truth.numel() <= 1024:
+        raise ValueError(f"stft_loss='mrstft' needs more than 1024 samples (reflect padding of its 2048-point "
+                         f"frame is undefined for {ground_truth.numel()}; torch.stft refuses it too)")
+
     if num_freq is not None:  # run.py:81-82
         input_dimension = num_freq * 2
 
@@ -172,6 +182,10 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     dev = torch.device(device or "cuda")
     Engine = KanEngine if arch == "kan" else SirenEngine
     kw = {} if arch == "kan" else {"loss_mode": loss_mode, "encoding": encoding, "alpha": alpha}
+    if stft_loss != "stft":
+        if arch == "kan":
+            raise NotImplementedError("stft_loss='mrstft' fits the MLP (arch='kan' is fitted with MSELoss only)")
+        kw["stft_loss"] = stft_loss
     engine = Engine(model, model_input, ground_truth, lr=learning_rate, min_lr=min_learning_rate,
                     patience=patience, micro_batch=micro_batch, hist_cap=total_steps, device=dev, **kw)
     if ckpt is not None:
@@ -263,6 +277,8 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
             "coord_samples_per_sec": engine.n_total * total_steps / max(total_time * 60, 1e-9),
             "n_gpus": n_gpus, "fp16_overflow_steps": engine.guard_state()["overflows"],
         }
+        if stft_loss != "stft":
+            params["stft_loss"] = stft_loss
         save_parameters(experiment_folder, **params)
         if verbose:
             print(json.dumps({"SNR": snr_final, "SNR_target": snr_target, "time_min": total_time}))
