@@ -12,7 +12,6 @@ same fp16 inputs.  Step level: the fused train step on train()'s default archite
 """
 import ctypes
 import json
-import math
 import os
 
 import numpy as np
@@ -23,6 +22,7 @@ from inr_for_audio_amd._lib import Opt, new_tileq, options
 from oracle import siren_oracle as orc
 from errlog import check_grads, log
 from gpu_util import ok, ptr, rel_np as _rel, release, stream as S, to_dev, within_f16
+from kernel_ref import act_inputs as _inputs, check_inner_bwd_dx_act, check_inner_fwd_act, snake_ref as _snake_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -52,19 +52,6 @@ def tile(request, lib):
         yield t
 
 
-def _inputs(rng, R, H):
-    X = orc.f16_round(rng.uniform(-1, 1, (R, H)).astype(F32))
-    lim = 1 / math.sqrt(H)     # nn.Linear default init range of the Snake / Tanh Linears
-    W = orc.f16_round(rng.uniform(-lim, lim, (H, H)).astype(F32))
-    b = rng.uniform(-lim, lim, H).astype(F32)
-    return X, W, b
-
-
-def _snake_ref(z, a):
-    s, c = np.sin(a * z), np.cos(a * z)
-    return z + s * s / a, 1.0 + 2.0 * s * c, (z * 2.0 * s * c) / a - s * s / (a * a)
-
-
 @pytest.mark.parametrize("act", [SNAKE, TANH])
 @pytest.mark.parametrize("R,H,amag", [(512, 256, 0.5), (512, 512, 50.0), (256, 1024, 3.0)])
 @pytest.mark.parametrize("head", [False, True])
@@ -83,22 +70,7 @@ def test_inner_fwd_act(lib, dev, tile, act, R, H, amag, head):
                                ctypes.c_float(30.0), ptr(to_dev(a, dev)), R, H, ptr(Y), ptr(C), ptr(E),
                                ptr(to_dev(hw, dev)) if head else None, ptr(hp) if head else None,
                                ptr(new_tileq(dev)), S()), lib)
-    z = X.astype(np.float64) @ W.astype(np.float64).T + b
-    # fp32 accumulation of z: |dz| ~ 1e-6; through sin(a z) that is a*|dz|
-    slack = 2e-6 * max(1.0, float(amag)) * 4
-    if act == SNAKE:
-        y, d, e = _snake_ref(z, a.astype(np.float64))
-        assert within_f16(f16_np(Y), y, slack) <= 0
-        assert within_f16(f16_np(C), d, 2 * slack) <= 0
-        assert within_f16(f16_np(E), e, 2 * slack * (np.max(np.abs(z)) + 1) / float(a.min())) <= 0
-    else:
-        y = np.tanh(z)
-        assert within_f16(f16_np(Y), y, 1e-6) <= 0
-        assert within_f16(f16_np(C), 1.0 - y * y, 2e-6) <= 0
-    if head:
-        ref = y @ hw.astype(np.float64)
-        got = hp.cpu().numpy().astype(np.float64).sum(0)
-        assert np.max(np.abs(got - ref)) < 1e-4 * max(1.0, np.max(np.abs(ref)))
+    check_inner_fwd_act(act, f16_np(Y), f16_np(C), f16_np(E), hp.cpu().numpy() if head else None, X, W, b, a, hw, amag)
 
 
 @pytest.mark.parametrize("act", [SNAKE, TANH])
@@ -123,18 +95,9 @@ def test_inner_fwd_act_lines_queue(lib, dev, act, H):
         outs.append((Y, C, E) if act == SNAKE else (Y, C))
     for q, s in zip(*outs):
         assert torch.equal(q, s)
-    z = X.astype(np.float64) @ W.astype(np.float64).T + b
-    slack = 8e-6
-    Y, C = outs[0][0], outs[0][1]
-    if act == SNAKE:
-        y, d, e = _snake_ref(z, a.astype(np.float64))
-        assert within_f16(f16_np(Y), y, slack) <= 0
-        assert within_f16(f16_np(C), d, 2 * slack) <= 0
-        assert within_f16(f16_np(outs[0][2]), e, 2 * slack * (np.max(np.abs(z)) + 1) / float(a.min())) <= 0
-    else:
-        y = np.tanh(z)
-        assert within_f16(f16_np(Y), y, 1e-6) <= 0
-        assert within_f16(f16_np(C), 1.0 - y * y, 2e-6) <= 0
+    # a drawn around 0.5: test_inner_fwd_act's slack at amag <= 1 (8e-6); no head partials
+    Yq, Cq, Eq = [f16_np(o) for o in outs[0]] + ([None] if act == TANH else [])
+    check_inner_fwd_act(act, Yq, Cq, Eq, None, X, W, b, a, None, 0.5)
 
 
 def test_snake_small_az_error(lib, dev):
@@ -183,24 +146,11 @@ def test_inner_bwd_dx_act(lib, dev, tile, act, R, H, k):
     ok(lib.siren_inner_bwd_dx_act(ptr(to_dev(dZ, dev, H16)), ptr(to_dev(WT, dev, H16)), ptr(to_dev(D, dev, H16)),
                                   ptr(to_dev(Ep, dev, H16)) if act == SNAKE else None, act, ctypes.c_float(30.0),
                                   R, H, ptr(gs), ptr(out), ptr(part), S()), lib)
-    dY = dZ.astype(np.float64) @ W.astype(np.float64)
-    ref = dY * D
-    scale = np.max(np.abs(ref))
-    assert within_f16(f16_np(out), ref, 1e-5 * scale) <= 0
-    tile_rows = lib.siren_nt_tile(R, H)
-    p = part.cpu().numpy().astype(np.float64)
-    if act == SNAKE:
-        p = p[: R // tile_rows]
-        db, da = p[:, 0].sum(0), p[:, 1].sum(0)
-    else:
-        db = p.reshape(-1)[: (R // tile_rows) * H].reshape(-1, H).sum(0)
-        da = None
-    sc = 2.0 ** (k or 0)
-    tol = 1e-4 * np.max(np.abs(ref.sum(0))) + 1e-6 * scale * math.sqrt(R)
-    assert np.max(np.abs(db * sc - ref.sum(0))) < tol
-    if da is not None:
-        dref = (dY * Ep).sum(0)
-        assert np.max(np.abs(da * sc - dref)) < 1e-4 * np.max(np.abs(dref)) + 1e-6 * np.max(np.abs(dY)) * math.sqrt(R)
+    # the written partial rows: Snake [R/tile][2][H] (db, da), Tanh [R/tile][H] (db)
+    nrow = R // lib.siren_nt_tile(R, H)
+    p = part.cpu().numpy()
+    p = p[:nrow] if act == SNAKE else p.reshape(-1)[: nrow * H].reshape(-1, H)
+    check_inner_bwd_dx_act(act, f16_np(out), p, dZ, W, D, Ep, k)
 
 
 @pytest.mark.parametrize("H", [128, 1024])

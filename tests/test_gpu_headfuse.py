@@ -118,6 +118,7 @@ def test_fused_step_graph_and_determinism(dev, opts):
     (1024, 4096, 3000, 8),    # pad rows; 2 band groups walking 8 bands each
     (512, 2048, 2048, 2),
     (256, 2048, 1500, 0),
+    (256, 2560, 2300, 3),     # width 256 (K = 256: 4 K-tiles), 10 bands on 3 blocks: walks of 4, 3, 3
 ])
 def test_kernel_vs_unfused_launches(dev, lib, opts, H, R, n_valid, grid):
     """siren_head_fused_fwd against siren_inner_fwd (+ head) -> siren_head_loss -> siren_head_bwd

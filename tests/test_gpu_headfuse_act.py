@@ -43,6 +43,8 @@ def opts(lib):
     (1024, 4096, 3000, 8, 50.0),   # pad rows; 2 band groups walking 8 bands each; __main__'s a = 50
     (512, 2048, 2048, 2, 3.0),
     (256, 2048, 1500, 0, 0.5),
+    (256, 2560, 2300, 3, 0.5),     # width 256 (K = 256: 4 K-tiles), 10 bands on 3 blocks: walks of 4, 3, 3
+    (256, 2560, 2300, 3, 50.0),    # ... with __main__'s a = 50
 ])
 def test_kernel_act_vs_unfused_launches(dev, lib, opts, act, H, R, n_valid, grid, amag):
     from inr_for_audio_amd._lib import new_tileq
@@ -109,6 +111,10 @@ def _engine(dev, H, cfg, n, *, a0=0.5, mb=1 << 20, seed=0, w0=3000.0, loss="mse"
     (1024, (0, 4, 0), 8000, 8, 50.0, 1 << 20, "mse"),  # run.py:466 __main__: 4 Snake layers, a = 50
     (512, (1, 1, 1), 4096, 6, 0.5, 1 << 20, "mae"),    # Tanh last, L1Loss
     (1024, (1, 1, 0), 6000, 4, 0.5, 2048, "mse"),      # Snake last, 3 micro-batches
+    # width 256, the production tile forced, 10 row bands on 3 blocks (walks of 4, 3, 3 tiles)
+    (256, (0, 4, 0), 2500, 3, 50.0, 1 << 20, "mse"),   # run.py:466 __main__ at its own width
+    (256, (2, 2, 0), 2500, 3, 0.5, 1280, "mse"),       # train() default, 2 micro-batches of 5 bands
+    (256, (1, 1, 1), 2500, 3, 0.5, 1 << 20, "mae"),    # Tanh last, L1Loss
 ])
 def test_fused_act_matches_unfused(dev, lib, opts, H, cfg, n, grid, a0, mb, loss):
     opts(Opt.NT_TILE, 256)
@@ -140,13 +146,18 @@ def test_fused_act_matches_unfused(dev, lib, opts, H, cfg, n, grid, a0, mb, loss
         assert max(errs0.values()) < 2e-5, errs0
 
 
-@pytest.mark.parametrize("H,cfg,n,a0", [
-    (1024, (2, 2, 0), 4096, 0.5),
-    (512, (1, 0, 2), 4096, 0.5),
-    (1024, (0, 4, 0), 4096, 50.0),
+@pytest.mark.parametrize("H,cfg,n,a0,grid", [
+    # grid 0: the automatic grid; these rows keep the ids they had before the grid became a parameter
+    pytest.param(1024, (2, 2, 0), 4096, 0.5, 0, id="1024-cfg0-4096-0.5"),
+    pytest.param(512, (1, 0, 2), 4096, 0.5, 0, id="512-cfg1-4096-0.5"),
+    pytest.param(1024, (0, 4, 0), 4096, 50.0, 0, id="1024-cfg2-4096-50.0"),
+    # width 256 on 3 persistent blocks: 10 row bands in walks of 4, 3, 3 tiles
+    pytest.param(256, (0, 4, 0), 2500, 50.0, 3, id="256-cfg3-2500-50.0-g3"),
+    pytest.param(256, (2, 2, 0), 2500, 0.5, 3, id="256-cfg4-2500-0.5-g3"),
 ])
-def test_fused_act_vs_oracle(dev, lib, opts, H, cfg, n, a0):
+def test_fused_act_vs_oracle(dev, lib, opts, H, cfg, n, a0, grid):
     opts(Opt.NT_TILE, 256)
+    opts(Opt.NT_GRID, grid)
     eng, sd0, t, y = _engine(dev, H, cfg, n, a0=a0)
     _grads(eng, lib)                      # a Snake last layer's first launch: unfused
     got_g, _, _, kinds = _grads(eng, lib)
@@ -162,7 +173,7 @@ def test_fused_act_vs_oracle(dev, lib, opts, H, cfg, n, a0):
         assert S == orc.grad_scale(eng.ws.g.cpu().numpy(), p.wf, 2.0)
     ref = orc.backward(p, t.numpy(), cache, gl, 3000.0, 30.0, half=True, scale=S)
     got = {k: eng.layout.view(got_g, i).cpu().numpy() for i, k in enumerate(eng.layout.names)}
-    check_grads(f"headfuse_act_vs_oracle[{H}x{cfg}x{n}]", got, ref)
+    check_grads(f"headfuse_act_vs_oracle[{H}x{cfg}x{n}x{grid}]", got, ref)
     lref = orc.mse(out, y.numpy())
     lgot = float(got_g[eng.layout.sse_offset]) / n
     assert abs(lgot - lref) <= 5e-4 * lref, (lgot, lref)

@@ -16,6 +16,7 @@ import torch
 from inr_for_audio_amd._lib import Opt, new_tileq, options
 from oracle import siren_oracle as orc
 from gpu_util import ok, ptr, release, stream as S, to_dev, within_f16
+from kernel_ref import check_first_bwd_dx, check_inner_bwd_dx, check_inner_fwd, inner_inputs as _inner_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -94,14 +95,6 @@ def test_first_fwd(lib, dev, in_dim, omega0):
         assert np.mean(got == orc.f16_round(ref)) > 0.995
 
 
-def _inner_inputs(rng, R, H):
-    X = orc.f16_round(rng.uniform(-1, 1, (R, H)).astype(F32))
-    lim = math.sqrt(6 / H) / 30
-    W = rng.uniform(-lim, lim, (H, H)).astype(F32)
-    b = rng.uniform(-1 / math.sqrt(H), 1 / math.sqrt(H), H).astype(F32)
-    return X, W, b
-
-
 @pytest.mark.parametrize("R,H", [(256, 128), (512, 256), (384, 512), (256, 1024), (768, 512)])
 @pytest.mark.parametrize("head", [False, True])
 def test_inner_fwd(lib, dev, R, H, head, nt_tile):
@@ -117,13 +110,7 @@ def test_inner_fwd(lib, dev, R, H, head, nt_tile):
                            ptr(to_dev(b, dev)), ctypes.c_float(30.0), R, H, ptr(Y), ptr(C),
                            ptr(to_dev(hw, dev)) if head else None, ptr(hp) if head else None,
                            ptr(new_tileq(dev)), S()), lib)
-    a = 30.0 * (X.astype(np.float64) @ Wh.astype(np.float64).T + b)
-    assert within_f16(f16_np(Y), np.sin(a), 2e-5) <= 0
-    assert within_f16(f16_np(C), np.cos(a), 2e-5) <= 0
-    if head:
-        ref = np.sin(a) @ hw.astype(np.float64)
-        got = hp.cpu().numpy().astype(np.float64).sum(0)
-        assert np.max(np.abs(got - ref)) < 1e-4 * max(1.0, np.max(np.abs(ref)))
+    check_inner_fwd(f16_np(Y), f16_np(C), hp.cpu().numpy() if head else None, X, Wh, b, hw)
 
 
 @pytest.mark.parametrize("R,H,grid", [(512, 256, 0), (4096, 512, 7), (65536, 1024, 0), (220160, 512, 0),
@@ -241,11 +228,7 @@ def test_inner_bwd_dx(lib, dev, R, H, k, nt_tile):
     ok(lib.siren_inner_bwd_dx(ptr(to_dev(dZ, dev, H16)), ptr(to_dev(WT, dev, H16)),
                               ptr(to_dev(Cp, dev, H16)), ctypes.c_float(30.0), R, H,
                               ptr(gscale_dev(dev, k)), ptr(out), ptr(dbp), S()), lib)
-    ref = (dZ.astype(np.float64) @ Wh.astype(np.float64)) * Cp * 30.0
-    scale = np.max(np.abs(ref))
-    assert within_f16(f16_np(out), ref, 1e-5 * scale) <= 0
-    db = dbp.cpu().numpy().astype(np.float64).sum(0) * 2.0 ** (k or 0)
-    assert np.max(np.abs(db - ref.sum(0))) < 1e-4 * np.max(np.abs(ref.sum(0))) + 1e-6 * scale
+    check_inner_bwd_dx(f16_np(out), dbp.cpu().numpy(), dZ, Wh, Cp, k)
 
 
 @pytest.mark.parametrize("in_dim", [1, 2])
@@ -267,14 +250,7 @@ def test_first_bwd_dx(lib, dev, in_dim, omega0, nt_tile):
     ok(lib.siren_first_bwd_dx(ptr(to_dev(dZ1, dev, H16)), ptr(to_dev(WT, dev, H16)),
                               ptr(to_dev(C0, dev, H16)), ptr(to_dev(t, dev)), in_dim,
                               ctypes.c_float(omega0), R, H, ptr(gscale_dev(dev, k)), ptr(part), S()), lib)
-    dz0 = (dZ1.astype(np.float64) @ Wh.astype(np.float64)) * C0 * omega0
-    got = part.cpu().numpy().astype(np.float64).sum(0) * 2.0 ** (k or 0)
-    ref_db = dz0.sum(0)
-    scale = np.max(np.abs(dz0)) * math.sqrt(R)
-    assert np.max(np.abs(got[0] - ref_db)) < 1e-4 * scale
-    for j in range(in_dim):
-        ref_w = (dz0 * t[:, j:j + 1]).sum(0)
-        assert np.max(np.abs(got[1 + j] - ref_w)) < 1e-4 * scale
+    check_first_bwd_dx(part.cpu().numpy(), dZ1, Wh, C0, t, omega0, k)
 
 
 @pytest.mark.parametrize("R,H,splits,tile", [(256, 128, 1, 128), (1024, 256, 3, 128), (2048, 256, 16, 128),
