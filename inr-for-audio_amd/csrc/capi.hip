@@ -130,16 +130,16 @@ hipError_t last_grad_scale(const siren_net* n, const siren_batch* b, hipStream_t
                     (const GuardState*)b->guard);
 }
 
-// run.py:160-169: a batch with an STFT term or the SNR loss takes the unfused step with the loss
+// run.py:160-169: a batch with a spectral term or the SNR loss takes the unfused step with the loss
 // kernels of stft.hip between the forward and the backward
 constexpr int kStftMaxN = 1 << 30;
 bool spectral(const siren_batch* b, const siren_spectral* sp) { return (sp && sp->alpha != 0.0) || b->loss_mode == 2; }
 
 // loss_step: the call evaluates the loss (siren_train_step*), so loss_mode 2 / alpha need their workspace;
 // siren_backward takes dLoss/dout as given and ignores both
-// mr: sp is a siren_spectral_mr's fields (run.py:127), whose transforms need n_valid > 1024
+// kind: which spectral loss sp's fields belong to (SPEC_MRSTFT: a siren_spectral_mr's, run.py:127)
 int check_batch(const siren_net* n, const siren_batch* b, bool train, const siren_spectral* sp = nullptr,
-                bool loss_step = false, bool mr = false) {
+                bool loss_step = false, SpecLoss kind = SPEC_STFT) {
   if (!b) return SIREN_ERR_NULL;
   if (b->rows <= 0 || b->rows % SIREN_ROW_TILE || b->n_valid < 0 || b->n_valid > b->rows)
     return SIREN_ERR_SHAPE;
@@ -163,9 +163,8 @@ int check_batch(const siren_net* n, const siren_batch* b, bool train, const sire
     // run.py:160-169: the STFT / SNR losses see the whole signal in one workspace
     if (!sp || !sp->stft_ws || (sp->alpha != 0.0 && !sp->stft_basis)) return SIREN_ERR_NULL;
     if (b->n_total != (double)b->n_valid) return SIREN_ERR_CONFIG;
-    if (b->n_valid < 1 || b->n_valid > kStftMaxN || (sp->alpha != 0.0 && stft_frames(b->n_valid) < 1))
+    if (b->n_valid < 1 || b->n_valid > kStftMaxN || (sp->alpha != 0.0 && spec_frames(kind, b->n_valid, 0) < 1))
       return SIREN_ERR_SHAPE;
-    if (mr && sp->alpha != 0.0 && mrstft_frames(b->n_valid, 0) < 1) return SIREN_ERR_SHAPE;
   }
   return SIREN_OK;
 }
@@ -468,56 +467,33 @@ static int backward_from_g(const siren_net* net, const siren_grads* gr, siren_ba
   return run_backward(net, gr, b, s);
 }
 
-// run.py:158-185 with an STFT term (alpha) or the SNR loss (run.py:126-128, :160-169).  The loss is
-// global -- every output sample feeds every gradient through 1024-point frames and the sums over the
-// whole signal -- so it cannot live in the fused last layer's epilogue: unfused forward and head_loss
-// (out, and the L1 / MSE sum), the loss kernels (stft.hip), then the backward from the mixed
-// g = dLoss/dout exactly as siren_backward runs it.  gr->sse[0] receives the finished mixed loss.
-static int run_spectral_step(const siren_net* net, const siren_grads* gr, siren_batch* b,
-                             const siren_spectral* sp, float gfac, hipStream_t s) {
+// run.py:158-185 with a spectral term (alpha; run.py:127-128: STFT or multi-resolution STFT) or the SNR
+// loss (run.py:126, :160-169).  The loss is global -- every output sample feeds every gradient through
+// the transforms' frames and the sums over the whole signal -- so it cannot live in the fused last
+// layer's epilogue: unfused forward and head_loss (out, and the L1 / MSE sum), the loss kernels
+// (stft.hip), then the backward from the mixed g = dLoss/dout exactly as siren_backward runs it.
+// gr->sse[0] receives the finished mixed loss.  kind SPEC_MRSTFT: sp holds a siren_spectral_mr's fields
+static int run_spectral_step(const siren_net* net, const siren_grads* gr, siren_batch* b, const siren_spectral* sp,
+                             SpecLoss kind, float gfac, hipStream_t s) {
   const int R = b->rows, n = b->n_valid;
-  const bool stft = sp->alpha != 0.0;
-  const StftWs w = stft_ws_map(sp->stft_ws, n, R);
+  const bool stft = sp->alpha != 0.0, mr = kind == SPEC_MRSTFT;
+  const SpecWs w = spec_ws_map(kind, sp->stft_ws, n, R);
   SIREN_TRY(run_forward(net, b, s));
   // out (through the final sine of last_linear=False) and the |err| / err^2 partials; its g is replaced
   SIREN_PROF(SIREN_PROF_HEAD, s, head_loss(b->head_part, head_parts(R, net->hidden), R, net->b_head, b->target, n, gfac,
                                            b->out, b->g, b->sse_part, b->gsum_part, b->gmax_part, s, net->head_omega,
                                            b->loss_mode == 1 ? 1 : 0));
   if (b->loss_mode == 2) SIREN_PROF(SIREN_PROF_LOSS, s, snr_sums(b->out, b->target, n, w, s));
-  if (stft) SIREN_PROF(SIREN_PROF_LOSS, s, stft_forward(b->out, n, sp->stft_basis, w, false, s));
-  SIREN_PROF(SIREN_PROF_LOSS, s, loss_finish(w, n, b->sse_part, bands(R), b->loss_mode, sp->alpha, b->n_total, stft,
-                                             gr->sse, s));
-  if (stft) SIREN_PROF(SIREN_PROF_LOSS, s, stft_backward(sp->stft_basis, w, s));
+  if (stft) SIREN_PROF(SIREN_PROF_LOSS, s, spec_forward(b->out, n, sp->stft_basis, w, false, s));
+  // the single transform's term is finished and mixed with the point loss in one launch; the
+  // multi-resolution one takes the point loss's scalars alone, then its three terms, their mean and the mix
+  SIREN_PROF(SIREN_PROF_LOSS, s, loss_finish(w, n, b->sse_part, bands(R), b->loss_mode, mr ? 0.0 : sp->alpha,
+                                             b->n_total, stft && !mr, mr ? nullptr : gr->sse, s));
+  if (mr) SIREN_PROF(SIREN_PROF_LOSS, s, mrstft_finish(w, stft, b->loss_mode, sp->alpha, gr->sse, false, s));
+  if (stft) SIREN_PROF(SIREN_PROF_LOSS, s, spec_backward(sp->stft_basis, w, s));
   SIREN_PROF(SIREN_PROF_LOSS, s, loss_mix(b->out, b->target, n, R, w, b->loss_mode, sp->alpha, gfac, b->g, s));
   // from here on siren_backward's sequence; batch->g keeps dLoss/dout, the chain through a final
   // sine (last_linear=False) goes to a copy
-  siren_batch bb = *b;
-  if (net->head_omega > 0.f) {
-    SIREN_TRY(hipMemcpyAsync(w.gchain, b->g, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, s));
-    bb.g = w.gchain;
-  }
-  return backward_from_g(net, gr, &bb, s);
-}
-
-// run.py:158-185 with the multi-resolution term (run.py:127): run_spectral_step with the kernels of
-// mrstft.hip in the place of stft.hip's (sp: the siren_spectral_mr's alpha, basis and ws)
-static int run_mrstft_step(const siren_net* net, const siren_grads* gr, siren_batch* b, const siren_spectral* sp,
-                           float gfac, hipStream_t s) {
-  const int R = b->rows, n = b->n_valid;
-  const bool stft = sp->alpha != 0.0;
-  const MrWs w = mrstft_ws_map(sp->stft_ws, n, R);
-  SIREN_TRY(run_forward(net, b, s));
-  SIREN_PROF(SIREN_PROF_HEAD, s, head_loss(b->head_part, head_parts(R, net->hidden), R, net->b_head, b->target, n, gfac,
-                                           b->out, b->g, b->sse_part, b->gsum_part, b->gmax_part, s, net->head_omega,
-                                           b->loss_mode == 1 ? 1 : 0));
-  if (b->loss_mode == 2) SIREN_PROF(SIREN_PROF_LOSS, s, snr_sums(b->out, b->target, n, w.pt, s));
-  if (stft) SIREN_PROF(SIREN_PROF_LOSS, s, mrstft_forward(b->out, n, sp->stft_basis, w, false, s));
-  // the point loss's scalars (stft.hip), then the three terms, their mean and the mix
-  SIREN_PROF(SIREN_PROF_LOSS, s, loss_finish(w.pt, n, b->sse_part, bands(R), b->loss_mode, 0.0, b->n_total, false,
-                                             nullptr, s));
-  SIREN_PROF(SIREN_PROF_LOSS, s, mrstft_finish(w, stft, b->loss_mode, sp->alpha, gr->sse, false, s));
-  if (stft) SIREN_PROF(SIREN_PROF_LOSS, s, mrstft_backward(sp->stft_basis, w, s));
-  SIREN_PROF(SIREN_PROF_LOSS, s, mrstft_mix(b->out, b->target, n, R, w, b->loss_mode, sp->alpha, gfac, b->g, s));
   siren_batch bb = *b;
   if (net->head_omega > 0.f) {
     SIREN_TRY(hipMemcpyAsync(w.pt.gchain, b->g, (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -527,10 +503,10 @@ static int run_mrstft_step(const siren_net* net, const siren_grads* gr, siren_ba
 }
 
 static int train_step(const siren_net* net, const siren_grads* gr, siren_batch* b, const siren_spectral* sp,
-                      void* stream, bool mr = false) {
+                      void* stream, SpecLoss kind = SPEC_STFT) {
   int st = check_net(net);
   if (st) return st;
-  if ((st = check_batch(net, b, true, sp, true, mr))) return st;
+  if ((st = check_batch(net, b, true, sp, true, kind))) return st;
   if ((st = check_grads(net, gr))) return st;
   if (!gr->sse) return SIREN_ERR_NULL;
   hipStream_t s = S(stream);
@@ -538,7 +514,7 @@ static int train_step(const siren_net* net, const siren_grads* gr, siren_batch* 
 
   SIREN_TRY(zero_grads(gr, b, s));
   const float gfac = loss_gfac(b->loss_mode, b->n_total);
-  if (spectral(b, sp)) return mr ? run_mrstft_step(net, gr, b, sp, gfac, s) : run_spectral_step(net, gr, b, sp, gfac, s);
+  if (spectral(b, sp)) return run_spectral_step(net, gr, b, sp, kind, gfac, s);
   const bool hb = head_fused(net, b, s);
   if (hb) {
     // the fused head needs the backward scale S before the forward.  Sine / Tanh last layer
@@ -583,7 +559,7 @@ int siren_train_step_mrstft(const siren_net* net, const siren_grads* gr, siren_b
                             const siren_spectral_mr* loss, void* stream) {
   if (!loss) return SIREN_ERR_NULL;
   const siren_spectral sp = {loss->alpha, loss->basis, loss->ws};
-  return train_step(net, gr, b, &sp, stream, true);
+  return train_step(net, gr, b, &sp, stream, SPEC_MRSTFT);
 }
 
 int siren_backward(const siren_net* net, const siren_grads* gr, siren_batch* b, void* stream) {
@@ -830,122 +806,113 @@ int siren_rff_first_bwd(const uint16_t* dZ1, const uint16_t* WTh1, const uint16_
                               red_tmp, slab, gW0, gb0, ga0, s);
 }
 
-// ---- STFT and SNR losses (run.py:126-128, :160-169) -----------------------------------------
-// n samples in a batch of `rows` rows; `stft`: the transform needs n > 512
-static int stft_shape(int32_t n, int32_t rows, bool stft) {
-  if (n < 1 || n > kStftMaxN || rows < n || (stft && stft_frames(n) < 1)) return SIREN_ERR_SHAPE;
+// ---- spectral losses (run.py:126-128, :160-169): the siren_stft_* / siren_mrstft_* pairs --------
+// n samples in a batch of `rows` rows; `stft`: the loss's transforms need n > kStftMinN / kMrMinN
+static int spec_shape(SpecLoss k, int32_t n, int32_t rows, bool stft) {
+  if (n < 1 || n > kStftMaxN || rows < n || (stft && spec_frames(k, n, 0) < 1)) return SIREN_ERR_SHAPE;
   return SIREN_OK;
 }
 
-int64_t siren_stft_frames(int64_t n) { return n >= 0 && n <= kStftMaxN ? stft_frames(n) : 0; }
+static int64_t spec_frames_api(SpecLoss k, int64_t n, int32_t r) {
+  return n >= 0 && n <= kStftMaxN ? spec_frames(k, n, r) : 0;
+}
 
-int64_t siren_stft_basis_floats(void) { return stft_basis_floats(); }
-
-int siren_stft_basis_fill(float* basis_host) {
+static int spec_basis_fill_api(SpecLoss k, float* basis_host) {
   if (!basis_host) return SIREN_ERR_NULL;
-  stft_basis_fill(basis_host);
+  spec_basis_fill(k, basis_host);
   return SIREN_OK;
 }
 
-int64_t siren_stft_workspace_floats(int32_t n, int32_t rows) {
-  return stft_shape(n, rows, false) ? -1 : stft_ws_floats(n, rows);
+static int64_t spec_workspace_floats(SpecLoss k, int32_t n, int32_t rows) {
+  if (spec_shape(k, n, rows, false)) return -1;
+  int64_t total = 0;
+  spec_ws_map(k, nullptr, n, rows, &total);
+  return total;
 }
 
-int64_t siren_stft_ws_offset(int32_t n, int32_t rows, int32_t which) {
-  if (stft_shape(n, rows, false)) return -1;
-  const StftWs w = stft_ws_map(nullptr, n, rows);
-  const float* const p[6] = {w.re, w.im, w.ymag, w.ylog, w.dF, w.scal};
+static int64_t spec_ws_offset(SpecLoss k, int32_t n, int32_t rows, int32_t r, int32_t which) {
+  if (spec_shape(k, n, rows, false)) return -1;
+  const SpecWs w = spec_ws_map(k, nullptr, n, rows);
+  if (r < 0 || r >= w.nres) return -1;
+  const float* const p[6] = {w.r[r].re, w.r[r].im, w.r[r].ymag, w.r[r].ylog, w.r[r].dF, w.scal};
   return which >= 0 && which < 6 ? (int64_t)((uintptr_t)p[which] / sizeof(float)) : -1;
 }
 
-int siren_stft_forward(const float* x, int32_t n, int32_t rows, const float* basis, float* ws, int32_t target,
-                       void* stream) {
+static int spec_forward_api(SpecLoss k, const float* x, int32_t n, int32_t rows, const float* basis, float* ws,
+                            int32_t target, void* stream) {
   if (!x || !basis || !ws) return SIREN_ERR_NULL;
   if (target < 0 || target > 1) return SIREN_ERR_CONFIG;
-  int st = stft_shape(n, rows, true);
+  int st = spec_shape(k, n, rows, true);
   if (st) return st;
-  return (int)stft_forward(x, n, basis, stft_ws_map(ws, n, rows), target != 0, S(stream));
+  return (int)spec_forward(x, n, basis, spec_ws_map(k, ws, n, rows), target != 0, S(stream));
 }
 
-int siren_stft_loss(int32_t n, int32_t rows, float* ws, float* loss, void* stream) {
+// loss[0] = the loss; SPEC_MRSTFT: loss[1..3] = its three terms
+static int spec_loss_api(SpecLoss k, int32_t n, int32_t rows, float* ws, float* loss, void* stream) {
   if (!ws || !loss) return SIREN_ERR_NULL;
-  int st = stft_shape(n, rows, true);
+  int st = spec_shape(k, n, rows, true);
   if (st) return st;
-  return (int)loss_finish(stft_ws_map(ws, n, rows), n, nullptr, 0, -1, 1.0, 1.0, true, loss, S(stream));
+  const SpecWs w = spec_ws_map(k, ws, n, rows);
+  if (k == SPEC_MRSTFT) return (int)mrstft_finish(w, true, -1, 1.0, loss, true, S(stream));
+  return (int)loss_finish(w, n, nullptr, 0, -1, 1.0, 1.0, true, loss, S(stream));
 }
 
-int siren_stft_loss_bwd(int32_t n, int32_t rows, const float* basis, float* ws, float* g_stft, void* stream) {
-  if (!basis || !ws || !g_stft) return SIREN_ERR_NULL;
-  int st = stft_shape(n, rows, true);
+static int spec_loss_bwd_api(SpecLoss k, int32_t n, int32_t rows, const float* basis, float* ws, float* g,
+                             void* stream) {
+  if (!basis || !ws || !g) return SIREN_ERR_NULL;
+  int st = spec_shape(k, n, rows, true);
   if (st) return st;
-  const StftWs w = stft_ws_map(ws, n, rows);
-  SIREN_TRY(stft_backward(basis, w, S(stream)));
-  return (int)stft_gather(n, w, g_stft, S(stream));
+  const SpecWs w = spec_ws_map(k, ws, n, rows);
+  SIREN_TRY(spec_backward(basis, w, S(stream)));
+  return (int)spec_gather(n, w, g, S(stream));
+}
+
+int64_t siren_stft_frames(int64_t n) { return spec_frames_api(SPEC_STFT, n, 0); }
+int64_t siren_stft_basis_floats(void) { return spec_basis_floats(SPEC_STFT); }
+int siren_stft_basis_fill(float* basis_host) { return spec_basis_fill_api(SPEC_STFT, basis_host); }
+int64_t siren_stft_workspace_floats(int32_t n, int32_t rows) { return spec_workspace_floats(SPEC_STFT, n, rows); }
+int64_t siren_stft_ws_offset(int32_t n, int32_t rows, int32_t which) {
+  return spec_ws_offset(SPEC_STFT, n, rows, 0, which);
+}
+int siren_stft_forward(const float* x, int32_t n, int32_t rows, const float* basis, float* ws, int32_t target,
+                       void* stream) {
+  return spec_forward_api(SPEC_STFT, x, n, rows, basis, ws, target, stream);
+}
+int siren_stft_loss(int32_t n, int32_t rows, float* ws, float* loss, void* stream) {
+  return spec_loss_api(SPEC_STFT, n, rows, ws, loss, stream);
+}
+int siren_stft_loss_bwd(int32_t n, int32_t rows, const float* basis, float* ws, float* g_stft, void* stream) {
+  return spec_loss_bwd_api(SPEC_STFT, n, rows, basis, ws, g_stft, stream);
+}
+
+int64_t siren_mrstft_frames(int64_t n, int32_t r) { return spec_frames_api(SPEC_MRSTFT, n, r); }
+int64_t siren_mrstft_basis_floats(void) { return spec_basis_floats(SPEC_MRSTFT); }
+int siren_mrstft_basis_fill(float* basis_host) { return spec_basis_fill_api(SPEC_MRSTFT, basis_host); }
+int64_t siren_mrstft_workspace_floats(int32_t n, int32_t rows) { return spec_workspace_floats(SPEC_MRSTFT, n, rows); }
+int64_t siren_mrstft_ws_offset(int32_t n, int32_t rows, int32_t r, int32_t which) {
+  return spec_ws_offset(SPEC_MRSTFT, n, rows, r, which);
+}
+int siren_mrstft_forward(const float* x, int32_t n, int32_t rows, const float* basis, float* ws, int32_t target,
+                         void* stream) {
+  return spec_forward_api(SPEC_MRSTFT, x, n, rows, basis, ws, target, stream);
+}
+int siren_mrstft_loss(int32_t n, int32_t rows, float* ws, float* loss, void* stream) {
+  return spec_loss_api(SPEC_MRSTFT, n, rows, ws, loss, stream);
+}
+int siren_mrstft_loss_bwd(int32_t n, int32_t rows, const float* basis, float* ws, float* g, void* stream) {
+  return spec_loss_bwd_api(SPEC_MRSTFT, n, rows, basis, ws, g, stream);
 }
 
 int siren_snr_loss(const float* x, const float* y, int32_t n, int32_t rows, float* ws, float* loss, float* g,
                    void* stream) {
   if (!x || !y || !ws || !loss || !g) return SIREN_ERR_NULL;
-  int st = stft_shape(n, rows, false);
+  int st = spec_shape(SPEC_STFT, n, rows, false);
   if (st) return st;
   hipStream_t s = S(stream);
-  const StftWs w = stft_ws_map(ws, n, rows);
+  const SpecWs w = spec_ws_map(SPEC_STFT, ws, n, rows);
   SIREN_TRY(snr_sums(x, y, n, w, s));
   SIREN_TRY(loss_finish(w, n, nullptr, 0, 2, 0.0, (double)n, false, loss, s));
   return (int)loss_mix(x, y, n, n, w, 2, 0.0, 0.f, g, s);
-}
-
-// ---- multi-resolution STFT loss (run.py:127, :160) --------------------------------------------
-// n samples in a batch of `rows` rows; `stft`: the transforms need n > 1024
-static int mrstft_shape(int32_t n, int32_t rows, bool stft) {
-  if (n < 1 || n > kStftMaxN || rows < n || (stft && mrstft_frames(n, 0) < 1)) return SIREN_ERR_SHAPE;
-  return SIREN_OK;
-}
-
-int64_t siren_mrstft_frames(int64_t n, int32_t r) { return n >= 0 && n <= kStftMaxN ? mrstft_frames(n, r) : 0; }
-
-int64_t siren_mrstft_basis_floats(void) { return mrstft_basis_floats(); }
-
-int siren_mrstft_basis_fill(float* basis_host) {
-  if (!basis_host) return SIREN_ERR_NULL;
-  mrstft_basis_fill(basis_host);
-  return SIREN_OK;
-}
-
-int64_t siren_mrstft_workspace_floats(int32_t n, int32_t rows) {
-  return mrstft_shape(n, rows, false) ? -1 : mrstft_ws_floats(n, rows);
-}
-
-int64_t siren_mrstft_ws_offset(int32_t n, int32_t rows, int32_t r, int32_t which) {
-  if (mrstft_shape(n, rows, false) || r < 0 || r >= kMrRes) return -1;
-  const MrWs w = mrstft_ws_map(nullptr, n, rows);
-  const float* const p[6] = {w.re[r], w.im[r], w.ymag[r], w.ylog[r], w.dF[r], w.scal};
-  return which >= 0 && which < 6 ? (int64_t)((uintptr_t)p[which] / sizeof(float)) : -1;
-}
-
-int siren_mrstft_forward(const float* x, int32_t n, int32_t rows, const float* basis, float* ws, int32_t target,
-                         void* stream) {
-  if (!x || !basis || !ws) return SIREN_ERR_NULL;
-  if (target < 0 || target > 1) return SIREN_ERR_CONFIG;
-  int st = mrstft_shape(n, rows, true);
-  if (st) return st;
-  return (int)mrstft_forward(x, n, basis, mrstft_ws_map(ws, n, rows), target != 0, S(stream));
-}
-
-int siren_mrstft_loss(int32_t n, int32_t rows, float* ws, float* loss, void* stream) {
-  if (!ws || !loss) return SIREN_ERR_NULL;
-  int st = mrstft_shape(n, rows, true);
-  if (st) return st;
-  return (int)mrstft_finish(mrstft_ws_map(ws, n, rows), true, -1, 1.0, loss, true, S(stream));
-}
-
-int siren_mrstft_loss_bwd(int32_t n, int32_t rows, const float* basis, float* ws, float* g, void* stream) {
-  if (!basis || !ws || !g) return SIREN_ERR_NULL;
-  int st = mrstft_shape(n, rows, true);
-  if (st) return st;
-  const MrWs w = mrstft_ws_map(ws, n, rows);
-  SIREN_TRY(mrstft_backward(basis, w, S(stream)));
-  return (int)mrstft_gather(n, w, g, S(stream));
 }
 
 int siren_inner_bwd_dw(const uint16_t* Y, const uint16_t* dZ, int32_t rows, int32_t hidden,

@@ -206,76 +206,68 @@ hipError_t rff_first_fwd(const float* x, const float* Bf, int F, const float* W0
 hipError_t rff_dw0(const h16* enc, const h16* dZ0, int F, int R, int H, float scale, const float* gscale,
                    float* slab, const float* db, float* gW0, float* gb0, hipStream_t s);
 
-// STFT / SNR losses and the loss mix (stft.hip; run.py:126-128, :160-169).  One caller-owned fp32
-// workspace of stft_ws_floats(n, rows) floats, carved up by stft_ws_map
-constexpr int kStftFft = 1024, kStftHop = 256, kStftBins = 513, kStftBinsPad = 528;
-struct StftWs {
-  float *re, *im;       // [T][528] transform of the model output
-  float *ymag, *ylog;   // [T][528] target magnitudes and their logs (constant: stft_forward(target))
-  float* dF;            // [T][1024] gradient of the frames
-  float* part;          // [8][npart] per-block partial sums
-  float* scal;          // [32] finished scalars (stft.hip SC_*)
-  float* gchain;        // [rows] dLoss/d(head linear output) of a last_linear=False step
+// The spectral losses and the loss mix (stft.hip; run.py:126-128, :160-169): the single STFT loss
+// (n_fft / hop / win 1024 / 256 / 1024), the multi-resolution one (1024 / 120 / 600, 2048 / 240 / 1200,
+// 512 / 50 / 240; L = (L_0 + L_1 + L_2) / 3) and the SNR loss.  One caller-owned fp32 workspace of
+// spec_ws_map's `total` floats per loss, carved up by spec_ws_map
+enum SpecLoss { SPEC_STFT = 0, SPEC_MRSTFT = 1 };
+// a loss's transforms need n > its largest n_fft / 2 (reflect padding)
+constexpr int kStftMinN = 512, kMrRes = 3, kMrMinN = 1024, kMrScalFloats = 32;
+struct SpecRes {          // one transform (T frames, bins and window support padded to 16)
+  float *re, *im;         // [T][bins] transform of the model output
+  float *ymag, *ylog;     // [T][bins] target magnitudes and their logs (constant: spec_forward(target))
+  float* dF;              // [T][win] gradient of the frames over the window's support
+  float* part;            // rows PT_S1, PT_SL of [.][npart] per-block partial sums
+  float* scal;            // its finished scalars SC_S1 .. SC_C2
   int T, npart;
 };
-// scal[] slots (StftWs::scal)
+struct PointWs {          // the point loss (L1 / MSE / SNR)
+  float* part;            // [PT_ROWS][npart] per-block partial sums
+  float* scal;            // [32] finished scalars (SC_*)
+  float* gchain;          // [rows] dLoss/d(head linear output) of a last_linear=False step
+  int npart;
+};
+// SPEC_STFT: r[0].part / .scal / .npart and scal are pt's (one block of partials, one scal[32]);
+// SPEC_MRSTFT: r[i].part is [2][npart_i], r[i].scal = scal + MR_SLOTS i, scal[kMrScalFloats] its own
+struct SpecWs {
+  SpecLoss loss;
+  int nres;               // 1 / kMrRes
+  SpecRes r[kMrRes];
+  float* scal;
+  PointWs pt;
+};
+// PointWs::scal slots; SC_S1 .. SC_C2 are also the slots of every SpecRes::scal
 enum { SC_S1 = 0, SC_SL = 1, SC_SY = 2, SC_LSTFT = 3, SC_C1 = 4, SC_C2 = 5, SC_MX = 6, SC_MY = 7, SC_SYC = 8,
        SC_SR = 9, SC_LSNR = 10, SC_FSNR = 11, SC_LPOINT = 12, SC_LOSS = 13 };
-// part[] rows (StftWs::part, each npart floats)
+// SPEC_MRSTFT's SpecWs::scal: MR_SLOTS floats per resolution, then the mean, the point loss and the mixed loss
+enum { MR_SLOTS = 8, MR_MEAN = 0, MR_POINT = 1, MR_LOSS = 2 };
+// part[] rows (each npart floats)
 // (the SNR sums are kept as a float pair hi + lo: L_snr crosses zero where the fit's residual
 // equals the signal, and an fp32 sum's 2^-24 is 1e-5 of a loss of 0.007 dB)
 enum { PT_S1 = 0, PT_SL = 1, PT_SX = 2, PT_SYM = 3, PT_SYC = 4, PT_SR = 5, PT_SYC_LO = 6, PT_SR_LO = 7, PT_ROWS = 8 };
-int64_t stft_frames(int64_t n);   // 1 + n / 256 (0: n <= 512, reflect padding undefined)
-int64_t stft_basis_floats();
-void stft_basis_fill(float* host);  // both tables, fp64 on the host rounded once
-int64_t stft_ws_floats(int n, int rows);
-StftWs stft_ws_map(float* ws, int n, int rows);
-// target: ymag, ylog and scal[Sy]; else re, im and the partials of S1 and sum|dlog|
-hipError_t stft_forward(const float* x, int n, const float* basis, const StftWs& w, bool target, hipStream_t s);
+int64_t spec_frames(SpecLoss k, int64_t n, int r);   // 1 + n / hop_r (0: n too short for the loss, or no such r)
+int64_t spec_basis_floats(SpecLoss k);
+void spec_basis_fill(SpecLoss k, float* host);  // per transform both table layouts, fp64 on the host rounded once
+SpecWs spec_ws_map(SpecLoss k, float* ws, int n, int rows, int64_t* total = nullptr);
+// target: ymag, ylog and Sy per transform; else re, im and the partials of S1 and sum|dlog|
+hipError_t spec_forward(const float* x, int n, const float* basis, const SpecWs& w, bool target, hipStream_t s);
 // partials of the means, then of sum yc^2 and sum (xc - yc)^2
-hipError_t snr_sums(const float* x, const float* y, int n, const StftWs& w, hipStream_t s);
-// the finished scalars; loss_mode 0 / 1: point loss = sum(sse_part) / n_total, 2: L_snr, -1: none
-// (loss = L_stft); stft: the partials of stft_forward are reduced; loss_out (nullable) <- the mixed loss
-hipError_t loss_finish(const StftWs& w, int n, const float* sse_part, int nsum, int loss_mode, double alpha,
+hipError_t snr_sums(const float* x, const float* y, int n, const SpecWs& w, hipStream_t s);
+// the point loss's finished scalars; loss_mode 0 / 1: sum(sse_part) / n_total, 2: L_snr, -1: none.
+// stft (SPEC_STFT only): the partials of spec_forward are reduced and loss = (1 - alpha) point +
+// alpha L_stft (loss_mode -1: L_stft); loss_out (nullable) <- the loss
+hipError_t loss_finish(const SpecWs& w, int n, const float* sse_part, int nsum, int loss_mode, double alpha,
                        double n_total, bool stft, float* loss_out, hipStream_t s);
-hipError_t stft_backward(const float* basis, const StftWs& w, hipStream_t s);   // -> w.dF
-hipError_t stft_gather(int n, const StftWs& w, float* g_stft, hipStream_t s);  // dF -> dL_stft/dx [n]
-// g[rows] = (1 - alpha) g_point + alpha gather(dF), 0 on pad rows
-hipError_t loss_mix(const float* out, const float* y, int n, int rows, const StftWs& w, int loss_mode, double alpha,
-                    float gfac, float* g, hipStream_t s);
-
-// Multi-resolution STFT loss (mrstft.hip; run.py:127, :160): three transforms (n_fft / hop / win
-// 1024 / 120 / 600, 2048 / 240 / 1200, 512 / 50 / 240), L = (L_0 + L_1 + L_2) / 3.  One caller-owned
-// fp32 workspace of mrstft_ws_floats(n, rows) floats, carved up by mrstft_ws_map
-constexpr int kMrRes = 3, kMrMinN = 1024, kMrScalFloats = 32;
-// scal[]: MR_SLOTS floats per resolution, then the mean, the point loss and the mixed loss
-enum { MR_S1 = 0, MR_SL = 1, MR_SY = 2, MR_L = 3, MR_C1 = 4, MR_C2 = 5, MR_SLOTS = 8, MR_MEAN = 0, MR_POINT = 1, MR_LOSS = 2 };
-struct MrWs {
-  float *re[kMrRes], *im[kMrRes];       // [T_r][bins padded to 16] transform of the model output
-  float *ymag[kMrRes], *ylog[kMrRes];   // the target's magnitudes and their logs (constant)
-  float* dF[kMrRes];                    // [T_r][win padded to 16] gradient of the frames over the window's support
-  float* part[kMrRes];                  // [2][npart_r] per-block partial sums (S1 / Sy, sum|dlog|)
-  int T[kMrRes], npart[kMrRes];
-  float* scal;                          // [32] finished scalars (MR_*)
-  StftWs pt;                            // the point loss's partials, scalars (SC_*) and gchain; no frames
-};
-int64_t mrstft_frames(int64_t n, int r);   // 1 + n / hop_r (0: n <= 1024, reflect padding of 2048 undefined)
-int64_t mrstft_basis_floats();
-void mrstft_basis_fill(float* host);       // per resolution both table layouts, fp64 on the host rounded once
-int64_t mrstft_ws_floats(int n, int rows);
-MrWs mrstft_ws_map(float* ws, int n, int rows, int64_t* total = nullptr);
-// target: ymag, ylog and Sy per resolution; else re, im and the partials of S1 and sum|dlog|
-hipError_t mrstft_forward(const float* x, int n, const float* basis, const MrWs& w, bool target, hipStream_t s);
-// the finished scalars; stft: the partials of mrstft_forward are reduced; loss_mode >= 0: the point loss
-// is w.pt's (loss_finish), -1: none (loss = L_mrstft); loss_out[0] (nullable) <- the mixed loss, terms:
+// SPEC_MRSTFT's finished scalars; stft: the partials of spec_forward are reduced; loss_mode >= 0: the point
+// loss is loss_finish's, -1: none (loss = L_mrstft); loss_out[0] (nullable) <- the mixed loss, terms:
 // loss_out[1..3] <- L_0, L_1, L_2
-hipError_t mrstft_finish(const MrWs& w, bool stft, int loss_mode, double alpha, float* loss_out, bool terms,
+hipError_t mrstft_finish(const SpecWs& w, bool stft, int loss_mode, double alpha, float* loss_out, bool terms,
                          hipStream_t s);
-hipError_t mrstft_backward(const float* basis, const MrWs& w, hipStream_t s);   // -> w.dF
-hipError_t mrstft_gather(int n, const MrWs& w, float* g, hipStream_t s);        // dF -> dL_mrstft/dx [n]
+hipError_t spec_backward(const float* basis, const SpecWs& w, hipStream_t s);   // -> every r[i].dF
+hipError_t spec_gather(int n, const SpecWs& w, float* g, hipStream_t s);        // dF -> dL_stft / dL_mrstft / dx [n]
 // g[rows] = (1 - alpha) g_point + alpha gather(dF), 0 on pad rows
-hipError_t mrstft_mix(const float* out, const float* y, int n, int rows, const MrWs& w, int loss_mode, double alpha,
-                      float gfac, float* g, hipStream_t s);
+hipError_t loss_mix(const float* out, const float* y, int n, int rows, const SpecWs& w, int loss_mode, double alpha,
+                    float gfac, float* g, hipStream_t s);
 
 // KAN (kan.hip): fp32, grid_size 5, spline_order 3 (9 A-columns per input)
 // fused layer kernels (the bases are recomputed in LDS; A and dA never reach HBM)

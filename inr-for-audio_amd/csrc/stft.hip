@@ -1,42 +1,67 @@
-// STFT and SNR losses (run.py:126-128, :160-169: auraloss.freq.STFTLoss() and
-// auraloss.time.SNRLoss(), restated from their published 0.4.0 definitions) and the loss mix
-//   loss = (1 - alpha) {L1 | L_snr | MSE} + alpha L_stft
+// The spectral losses (run.py:126-128, :160-169: auraloss.freq.STFTLoss(), auraloss.freq.
+// MultiResolutionSTFTLoss(perceptual_weighting=False) and auraloss.time.SNRLoss(), restated from their
+// published 0.4.0 definitions) and the loss mix
+//   loss = (1 - alpha) {L1 | L_snr | MSE} + alpha {L_stft | L_mrstft}
 // for the model output x and the target y, both one sequence of n samples.
 //
-//   X = stft(x, n_fft 1024, hop 256, periodic Hann, center, reflect)   T = 1 + n / 256 frames, 513 bins
+//   trait   n_fft   hop   win    left zero-pad   bins   frames T     needs
+//   SfR     1024    256   1024         0          513   1 + n / 256  n > 512    L_stft
+//   MrR0    1024    120    600       212          513   1 + n / 120  n > 1024 \.
+//   MrR1    2048    240   1200       424         1025   1 + n / 240  n > 1024  | L_mrstft = (L_0 + L_1 + L_2) / 3
+//   MrR2     512     50    240       136          257   1 + n / 50   n > 1024 /.
+//   X = stft(x, n_fft, hop, periodic Hann(win) centred in the n_fft frame, center, reflect)
 //   x_mag = sqrt(max(re^2 + im^2, 1e-8))
-//   L_stft = ||y_mag - x_mag||_F / ||y_mag||_F + mean |log x_mag - log y_mag|
+//   L = ||y_mag - x_mag||_F / ||y_mag||_F + mean |log x_mag - log y_mag|
 //   L_snr  = -10 log10(sum yc^2 / (sum (xc - yc)^2 + 1e-8) + 1e-8),  xc = x - mean x, yc = y - mean y
 //
-// The transform is a GEMM against windowed cos / -sin tables (fp64 on the host, rounded to fp32 once)
-// on v_mfma_f32_16x16x4_f32: a small bin's log amplifies its error by 1 / x_mag, so no fp16 operands.
+// Every transform is one instance of StftTraits and runs the same kernels: a GEMM against windowed
+// cos / -sin tables (fp64 on the host, rounded to fp32 once) on v_mfma_f32_16x16x4_f32: a small bin's
+// log amplifies its error by 1 / x_mag, so no fp16 operands.
 //
-// stft_fwd_kernel: a block owns 16 frames and 12 bin tiles of 16 (3 per wave; grid.y 3 covers the
-// 33 tiles of the 528 padded bins).  The 16 overlapping frames are read from the signal itself: the
-// 15 * 256 + 1024 = 4864 padded samples they span are staged once in LDS (reflection folded in the
-// staging index), never as a [T][1024] matrix.
-//   LDS map: sig[4940] fp32 (19 760 B): padded sample q of the tile at q + 4 (q >> 8)
-// Frame f starts at q = 256 f, so without the skew the 16 rows of one ds_read_b128 fragment would
-// be 256 floats apart -- one bank for all of them; with it they are 260 apart, i.e. 4 banks each,
-// the 16 rows x 4 floats of a read covering all 64 banks once.  A float4 never straddles a multiple
-// of 256, so it stays contiguous and 16-B aligned.
-// The basis is read from global memory (L2-resident, 4.3 MB) in a fragment-native layout,
-//   fwd[c][k / 16][bin][k % 16]   (c: 0 = w cos, 1 = -w sin; bin < 528, zero past 512)
-// so one wave's 16 bins x 16 k piece is 1 KB contiguous.  As in rff.hip a lane takes k = 4 (l >> 4) + s
+// K runs over the window's support only.  Taps outside [pad, pad + win) carry a zero window, so the
+// table holds the rows k' = tap - pad < KWP = win rounded up to the 16-k group (1024 / 608 / 1200 / 240;
+// the rows past win are zero) and frame t reads the padded samples t hop + pad + k'.
+//   fwd[c][k' / 16][bin][k' % 16]    bwd[c][bin / 16][k'][bin % 16]    (c: 0 = w cos, 1 = -w sin;
+//   bin < NBP = 528 / 528 / 1040 / 272, zero past the last bin); L_mrstft's three one after the other.
+// So one wave's 16 bins x 16 k piece is 1 KB contiguous.  As in rff.hip a lane takes k = 4 (l >> 4) + s
 // of a 16-k group as its operand of MFMA s for both operands (a permutation of the sum's terms).
 // The basis is the MFMA's A operand and the frames its B operand: a lane then holds 4 consecutive
 // bins of ONE frame in both the cos and the sin accumulator, forms the magnitude without a lane
-// exchange and stores re / im as 16-B pieces.  K is accumulated in two interleaved chains (even /
-// odd 16-k groups), summed at the end: 512-term instead of 1024-term fma chains.
+// exchange and stores re / im as 16-B pieces.
 //
-// stft_bwd_kernel: dF[T][1024] = [dRe | dIm][T][2 x 528] x basis^T, the table transposed to
-//   bwd[c][bin / 16][k][bin % 16]
-// The B operand (d of one frame, 4 consecutive bins per lane) is formed from re / im, the target's
-// magnitudes and the finished scalars as it is loaded:
-//   d = (x_mag - y_mag) / (sqrt S1 sqrt Sy) + sign(log x_mag - log y_mag) / (x_mag T 513),  0 at the clamp
+// stft_fwd_kernel<R>: a block owns 16 frames and 4 x WT bin tiles of 16 (WT per wave).  The frames
+// are read from the signal staged once in LDS (reflection folded in the staging index), never as a
+// [T][n_fft] matrix.  A lane (fr = l & 15, kq = l >> 4) reads the float4 at tap 16 kt + 4 kq of frame fr;
+// one ds_read_b128 is served in four groups of 16 lanes, {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and
+// the same + 32: a group holds all 16 frames, frames 0-3 and 12-15 at one kq and frames 4-11 at the
+// next.  A read is conflict-free when the 16 float4 slots (address / 4 mod 16) of a group differ.
+//   SfR (hop 256 = 64 slots = 0 mod 16: one bank for all 16 rows): sig[4940], padded sample q at
+//     q + 4 (q / 256): the frames are 260 floats apart, i.e. 4 banks each, the 16 rows x 4 floats of a
+//     read covering all 64 banks once.  A float4 never straddles a multiple of 256, so it stays
+//     contiguous and 16-B aligned.  Its tables (4.3 MB) stay L2-resident.
+//   MrR0 (hop 120 = 30 slots = -2 mod 16): sig[2408], padded sample q at q.  Slot -2 fr + kq: frames
+//     fr and fr + 8 share -2 fr, and exactly one of the two sits at the odd kq -- all 16 differ.
+//     Every address is a multiple of 4 floats (120, 16, 4).
+//   MrR1 (hop 240 = 60 slots = -4 mod 16, 4 distinct values: 4-way): sig[4960], sample q at
+//     q + 8 (q / 240): the frame stride becomes 248 floats = 62 slots = -2 mod 16, the case above.
+//     q / 240 = fr + kt / 15 (240 = 15 groups of 16), the same for a whole 16-k group, so a float4
+//     stays contiguous and 16-B aligned.  Its table (10 MB per layout) does not fit an XCD's 4 MB L2;
+//     keeping each table piece for 32 frames per block (half the table traffic, 35 KB of LDS) measured
+//     2 % slower than 16 frames per block, so every transform takes 16.
+//   MrR2 (hop 50 = 200 B: odd frames are only 8-B aligned, a ds_read_b128 there is replayed): the 16
+//     frames get a pitch of their own, sig[16][248] (pitch 62 slots = -2 mod 16, as above), 15.9 KB;
+//     the 240 taps of a frame are staged from global memory (L1 / L2 hits: frames overlap 4.8-fold).
+// K is accumulated in two interleaved chains (even / odd 16-k groups), summed at the end: fma chains
+// of at most 512 / 304 / 608 / 128 terms.
+//
+// stft_bwd_kernel<R>: dF[T][KWP] = [dRe | dIm][T][2 x NBP] x bwd table.  The B operand (d of one frame,
+// 4 consecutive bins per lane) is formed from re / im, the target's magnitudes and the finished
+// scalars as it is loaded:
+//   d = (x_mag - y_mag) / (sqrt S1 sqrt Sy) + sign(log x_mag - log y_mag) / (x_mag T bins),  0 at the clamp
 //   dRe = d re / x_mag, dIm = d im / x_mag
-// stft_gather then sums, per sample, the <= 4 frames that cover it and the same for its reflected
-// images, in a fixed order -- no float atomics anywhere, two runs are bit-identical.
+// The gather then sums, per sample, the <= 5 frames that cover it (win / hop <= 5) and the same for its
+// reflected images, ascending; L_mrstft adds its transforms in the order 0, 1, 2, each times 1/3 -- no
+// float atomics anywhere, two runs are bit-identical.  The scalars are finished in fp64 on the device.
 #include <math.h>
 #include "siren_common.h"
 #include "siren_kernels.h"
@@ -45,26 +70,64 @@ namespace siren {
 
 namespace {
 
-constexpr int SF_N = kStftFft, SF_HOP = kStftHop, SF_NB = kStftBins, SF_NBP = kStftBinsPad;
-constexpr int SF_NBT = SF_NBP / 16;                     // 33 bin tiles
-constexpr int SF_KT = SF_N / 16;                        // 64 k groups
-constexpr int SF_FT = 16;                               // frames per block
-constexpr int SF_SEG = (SF_FT - 1) * SF_HOP + SF_N;     // 4864 padded samples per block
-constexpr int SF_SEGP = SF_SEG + 4 * (SF_SEG / 256);    // + the skew
-constexpr int SF_WT = 3;                                // forward: bin tiles per wave
-constexpr int SF_FGY = (SF_NBT + 4 * SF_WT - 1) / (4 * SF_WT);  // forward grid.y (3)
-constexpr int SF_BWT = 4;                               // backward: sample tiles per wave
-constexpr int SF_BGY = SF_N / 16 / (4 * SF_BWT);        // backward grid.y (4)
 constexpr float SF_EPS = 1e-8f;
-constexpr size_t SF_TAB = (size_t)2 * SF_N * SF_NBP;    // floats of one table
+constexpr float MR_THIRD = 1.0f / 3.0f;
+
+template <int NFFT_, int HOP_, int WIN_, int WT_, int BWT_, int PITCH_, int SKEW_>
+struct StftTraits {
+  static constexpr int NFFT = NFFT_, HOP = HOP_, WIN = WIN_, PADL = (NFFT_ - WIN_) / 2;
+  static constexpr int NB = NFFT_ / 2 + 1, NBP = (NB + 15) / 16 * 16, NBT = NBP / 16;
+  static constexpr int KT = (WIN_ + 15) / 16, KWP = KT * 16;      // 16-k groups / table rows
+  static constexpr int FT = 16;                                   // frames per block
+  static constexpr int WT = WT_, FGY = (NBT + 4 * WT_ - 1) / (4 * WT_);   // bin tiles per wave, grid.y
+  static constexpr int BWT = BWT_, BGY = (KT + 4 * BWT_ - 1) / (4 * BWT_);  // backward: tap tiles per wave
+  static constexpr int PITCH = PITCH_, SKEW = SKEW_;
+  static constexpr int SEG = (FT - 1) * HOP_ + KWP;               // padded samples a block's frames span
+  static constexpr int LDS = PITCH_ ? FT * PITCH_ : SEG + SKEW_ * ((SEG + HOP_ - 1) / HOP_);
+  static constexpr size_t TAB = (size_t)2 * KWP * NBP;            // floats of one table layout
+  // guards that only some instances need: an odd number of 16-k groups leaves the second chain's last
+  // step empty; backward grids that overhang the taps clamp the overhanging tile's loads and skip its store
+  static constexpr bool KT_EVEN = KT % 2 == 0, BWD_EXACT = KT % (4 * BWT_) == 0;
+  static_assert(SKEW_ == 0 || HOP_ % 16 == 0, "the skew is constant over a 16-k group");
+  static_assert(PITCH_ % 4 == 0 && SKEW_ % 4 == 0 && (PITCH_ || HOP_ % 4 == 0), "16-B aligned float4 reads");
+  static_assert(PITCH_ == 0 || PITCH_ >= KWP, "a frame's taps fit its pitch");
+  // the frame q / hop that the block's padded sample q >= 0 starts or continues; spelt as a shift
+  // where it is one (the compiler cannot see q >= 0)
+  static constexpr bool HOP_POW2 = (HOP_ & (HOP_ - 1)) == 0;
+  __device__ static __forceinline__ int frame_of(int q) {
+    if constexpr (HOP_POW2) return q >> __builtin_ctz(HOP_);
+    else return q / HOP_;
+  }
+  // LDS index of tap 16 kt + fk (fk = 0, 4, 8, 12; + 0..3) of the block's frame f; without a pitch
+  // the block's padded sample q sits at q + SKEW frame_of(q)
+  __device__ static __forceinline__ int at(int f, int kt, int fk) {
+    const int q = HOP_ * f + 16 * kt + fk;
+    if constexpr (PITCH_ != 0) return PITCH_ * f + 16 * kt + fk;
+    else if constexpr (SKEW_ == 0) return q;
+    else if constexpr (HOP_POW2) return q + SKEW_ * frame_of(q);
+    else return q + SKEW_ * (f + kt / (HOP_ / 16));   // = frame_of(q), without a division per read
+  }
+};
+//                   n_fft  hop   win  WT BWT pitch skew
+using SfR = StftTraits<1024, 256, 1024, 3, 4, 0, 4>;
+using MrR0 = StftTraits<1024, 120, 600, 3, 5, 0, 0>;
+using MrR1 = StftTraits<2048, 240, 1200, 3, 4, 0, 8>;
+using MrR2 = StftTraits<512, 50, 240, 5, 4, 248, 0>;
+static_assert(SfR::LDS == 4940 && SfR::SEG == 4864 && SfR::FGY == 3 && SfR::BGY == 4 &&
+                  SfR::TAB == (size_t)2 * 1024 * 528 && SfR::PADL == 0 && SfR::KT_EVEN && SfR::BWD_EXACT,
+              "the single transform's layout");
+static_assert(kStftMinN == SfR::NFFT / 2 && kMrMinN == MrR1::NFFT / 2 && kMrMinN >= MrR0::NFFT / 2 &&
+                  kMrMinN >= MrR2::NFFT / 2, "one reflection lands inside the signal");
 
 __device__ __forceinline__ f32x4 sf_mfma(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-// sample at padded index j of the centred, reflect-padded signal (0 past the padded end: frames >= T)
+// sample at padded index j of the centred, reflect-padded signal (0 past the padded end: frames >= T);
+// n > n_fft / 2, so one reflection lands inside the signal
+template <int NFFT>
 __device__ __forceinline__ float stft_sample(const float* __restrict__ x, int n, int64_t j) {
-  int64_t i = j - SF_N / 2;
+  int64_t i = j - NFFT / 2;
   if (i < 0) {
     i = -i;
   } else if (i >= n) {
@@ -74,46 +137,52 @@ __device__ __forceinline__ float stft_sample(const float* __restrict__ x, int n,
   return x[i];
 }
 
-template <bool TARGET>
+template <class R, bool TARGET>
 __global__ __launch_bounds__(256) void stft_fwd_kernel(const float* __restrict__ x, int n, int T,
                                                        const float* __restrict__ basis, float* __restrict__ o0,
                                                        float* __restrict__ o1, const float* __restrict__ ymag,
                                                        const float* __restrict__ ylog, float* __restrict__ part,
                                                        int npart) {
-  __shared__ __attribute__((aligned(16))) float sig[SF_SEGP];
+  constexpr int WT = R::WT;
+  __shared__ __attribute__((aligned(16))) float sig[R::LDS];
   __shared__ float scratch[4];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int t0 = blockIdx.x * SF_FT;
-  const int64_t j0 = (int64_t)t0 * SF_HOP;
-  for (int q = tid; q < SF_SEG; q += 256) sig[q + 4 * (q >> 8)] = stft_sample(x, n, j0 + q);
+  const int t0 = blockIdx.x * R::FT;
+  const int64_t j0 = (int64_t)t0 * R::HOP + R::PADL;
+  if constexpr (R::PITCH != 0) {
+    for (int e = tid; e < R::FT * R::KWP; e += 256) {
+      const int f = e / R::KWP, u = e - f * R::KWP;
+      sig[R::PITCH * f + u] = stft_sample<R::NFFT>(x, n, j0 + f * R::HOP + u);
+    }
+  } else {
+    for (int q = tid; q < R::SEG; q += 256) sig[q + R::SKEW * R::frame_of(q)] = stft_sample<R::NFFT>(x, n, j0 + q);
+  }
   __syncthreads();
 
   const int fr = lane & 15, fk = 4 * (lane >> 4);
-  const int bt0 = (blockIdx.y * 4 + wave) * SF_WT;
-  f32x4 ac[2][SF_WT], as[2][SF_WT];
+  const int bt0 = (blockIdx.y * 4 + wave) * WT;
+  f32x4 ac[2][WT], as[2][WT];
 #pragma unroll
   for (int h = 0; h < 2; ++h)
 #pragma unroll
-    for (int j = 0; j < SF_WT; ++j) ac[h][j] = as[h][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < WT; ++j) ac[h][j] = as[h][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  auto load_b = [&](int kt, float4 (&bc)[SF_WT], float4 (&bs)[SF_WT]) {
+  auto load_b = [&](int kt, float4 (&bc)[WT], float4 (&bs)[WT]) {
 #pragma unroll
-    for (int j = 0; j < SF_WT; ++j) {
-      // a tile past the 33rd (the last wave of grid.y 2) re-reads tile 32: its results are not stored,
-      // and without a branch here the pieces stay in registers
-      const int bt = bt0 + j < SF_NBT ? bt0 + j : SF_NBT - 1;
-      const size_t o = ((size_t)kt * SF_NBP + bt * 16 + fr) * 16 + fk;
+    for (int j = 0; j < WT; ++j) {
+      // a tile past the last one re-reads the last: its results are not stored, and without a
+      // branch here the pieces stay in registers
+      const int bt = bt0 + j < R::NBT ? bt0 + j : R::NBT - 1;
+      const size_t o = ((size_t)kt * R::NBP + bt * 16 + fr) * 16 + fk;
       bc[j] = *(const float4*)(basis + o);
-      bs[j] = *(const float4*)(basis + (size_t)SF_N * SF_NBP + o);
+      bs[j] = *(const float4*)(basis + (size_t)R::KWP * R::NBP + o);
     }
   };
-  auto step = [&](int kt, const float4 (&bc)[SF_WT], const float4 (&bs)[SF_WT], f32x4 (&c)[SF_WT],
-                  f32x4 (&s)[SF_WT]) {
-    const int idx = 256 * fr + 16 * kt + fk;
-    const float4 a = *(const float4*)&sig[idx + 4 * (idx >> 8)];
+  auto step = [&](int kt, const float4 (&bc)[WT], const float4 (&bs)[WT], f32x4 (&c)[WT], f32x4 (&s)[WT]) {
+    const float4 a = *(const float4*)&sig[R::at(fr, kt, fk)];
 #pragma unroll
-    for (int j = 0; j < SF_WT; ++j) {
+    for (int j = 0; j < WT; ++j) {
       c[j] = sf_mfma(bc[j].x, a.x, c[j]);
       s[j] = sf_mfma(bs[j].x, a.x, s[j]);
       c[j] = sf_mfma(bc[j].y, a.y, c[j]);
@@ -124,24 +193,25 @@ __global__ __launch_bounds__(256) void stft_fwd_kernel(const float* __restrict__
       s[j] = sf_mfma(bs[j].w, a.w, s[j]);
     }
   };
-  // the next 16-k group's basis pieces travel under this group's MFMAs
-  float4 bcA[SF_WT], bsA[SF_WT], bcB[SF_WT], bsB[SF_WT];
+  // the next 16-k group's table pieces travel under this group's MFMAs
+  float4 bcA[WT], bsA[WT], bcB[WT], bsB[WT];
   load_b(0, bcA, bsA);
-  for (int kt = 0; kt < SF_KT; kt += 2) {
-    load_b(kt + 1, bcB, bsB);
+  for (int kt = 0; kt < R::KT; kt += 2) {
+    const bool odd = R::KT_EVEN || kt + 1 < R::KT;
+    if (odd) load_b(kt + 1, bcB, bsB);
     step(kt, bcA, bsA, ac[0], as[0]);
-    if (kt + 2 < SF_KT) load_b(kt + 2, bcA, bsA);
-    step(kt + 1, bcB, bsB, ac[1], as[1]);
+    if (kt + 2 < R::KT) load_b(kt + 2, bcA, bsA);
+    if (odd) step(kt + 1, bcB, bsB, ac[1], as[1]);
   }
 
   // lane: frame t0 + fr, bins (bt0 + j) 16 + fk + r
   const int t = t0 + fr;
   float s1 = 0.f, sl = 0.f;
 #pragma unroll
-  for (int j = 0; j < SF_WT; ++j) {
-    if (bt0 + j >= SF_NBT || t >= T) continue;
+  for (int j = 0; j < WT; ++j) {
+    if (bt0 + j >= R::NBT || t >= T) continue;
     const f32x4 re = ac[0][j] + ac[1][j], im = as[0][j] + as[1][j];
-    const size_t o = (size_t)t * SF_NBP + (bt0 + j) * 16 + fk;
+    const size_t o = (size_t)t * R::NBP + (bt0 + j) * 16 + fk;
     float mag[4], lg[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -153,7 +223,7 @@ __global__ __launch_bounds__(256) void stft_fwd_kernel(const float* __restrict__
       *(float4*)(o1 + o) = float4{lg[0], lg[1], lg[2], lg[3]};
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if ((bt0 + j) * 16 + fk + r < SF_NB) s1 += mag[r] * mag[r];
+        if ((bt0 + j) * 16 + fk + r < R::NB) s1 += mag[r] * mag[r];
     } else {
       *(float4*)(o0 + o) = float4{re[0], re[1], re[2], re[3]};
       *(float4*)(o1 + o) = float4{im[0], im[1], im[2], im[3]};
@@ -161,7 +231,7 @@ __global__ __launch_bounds__(256) void stft_fwd_kernel(const float* __restrict__
       const float ymv[4] = {ym.x, ym.y, ym.z, ym.w}, ylv[4] = {yl.x, yl.y, yl.z, yl.w};
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if ((bt0 + j) * 16 + fk + r < SF_NB) {
+        if ((bt0 + j) * 16 + fk + r < R::NB) {
           const float dm = ymv[r] - mag[r];
           s1 += dm * dm;
           sl += fabsf(lg[r] - ylv[r]);
@@ -177,28 +247,30 @@ __global__ __launch_bounds__(256) void stft_fwd_kernel(const float* __restrict__
   }
 }
 
+template <class R>
 __global__ __launch_bounds__(256) void stft_bwd_kernel(int T, const float* __restrict__ basisT,
                                                        const float* __restrict__ re, const float* __restrict__ im,
                                                        const float* __restrict__ ymag,
                                                        const float* __restrict__ ylog,
                                                        const float* __restrict__ scal, float* __restrict__ dF) {
+  constexpr int BWT = R::BWT;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fk = 4 * (lane >> 4);
-  const int t = blockIdx.x * SF_FT + fr;
+  const int t = blockIdx.x * R::FT + fr;
   const bool valid = t < T;
-  const int nt0 = (blockIdx.y * 4 + wave) * SF_BWT;
+  const int nt0 = (blockIdx.y * 4 + wave) * BWT;
   const float c1 = scal[SC_C1], c2 = scal[SC_C2];
-  f32x4 acc[2][SF_BWT];
+  f32x4 acc[2][BWT];
 #pragma unroll
   for (int h = 0; h < 2; ++h)
 #pragma unroll
-    for (int j = 0; j < SF_BWT; ++j) acc[h][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < BWT; ++j) acc[h][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   struct Raw { float4 re, im, ym, yl; };
   auto load_raw = [&](int bg, Raw& w) {
     if (valid) {
-      const size_t o = (size_t)t * SF_NBP + bg * 16 + fk;
+      const size_t o = (size_t)t * R::NBP + bg * 16 + fk;
       w.re = *(const float4*)(re + o);
       w.im = *(const float4*)(im + o);
       w.ym = *(const float4*)(ymag + o);
@@ -212,7 +284,7 @@ __global__ __launch_bounds__(256) void stft_bwd_kernel(int T, const float* __res
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       dre[s] = dim[s] = 0.f;
-      if (!valid || bg * 16 + fk + s >= SF_NB) continue;
+      if (!valid || bg * 16 + fk + s >= R::NB) continue;
       const float p = rv[s] * rv[s] + iv[s] * iv[s];
       if (!(p > SF_EPS)) continue;  // the clamp: no gradient
       const float xm = sqrtf(p);
@@ -224,18 +296,19 @@ __global__ __launch_bounds__(256) void stft_bwd_kernel(int T, const float* __res
       dim[s] = q * iv[s];
     }
   };
-  auto load_b = [&](int bg, float4 (&bc)[SF_BWT], float4 (&bs)[SF_BWT]) {
+  auto load_b = [&](int bg, float4 (&bc)[BWT], float4 (&bs)[BWT]) {
 #pragma unroll
-    for (int j = 0; j < SF_BWT; ++j) {
-      const size_t o = ((size_t)bg * SF_N + (nt0 + j) * 16 + fr) * 16 + fk;
+    for (int j = 0; j < BWT; ++j) {
+      const int nt = R::BWD_EXACT || nt0 + j < R::KT ? nt0 + j : R::KT - 1;   // a tile past the last: not stored
+      const size_t o = ((size_t)bg * R::KWP + nt * 16 + fr) * 16 + fk;
       bc[j] = *(const float4*)(basisT + o);
-      bs[j] = *(const float4*)(basisT + (size_t)SF_NBT * SF_N * 16 + o);
+      bs[j] = *(const float4*)(basisT + (size_t)R::NBT * R::KWP * 16 + o);
     }
   };
-  auto step = [&](const float (&dre)[4], const float (&dim)[4], const float4 (&bc)[SF_BWT],
-                  const float4 (&bs)[SF_BWT], f32x4 (&a)[SF_BWT]) {
+  auto step = [&](const float (&dre)[4], const float (&dim)[4], const float4 (&bc)[BWT], const float4 (&bs)[BWT],
+                  f32x4 (&a)[BWT]) {
 #pragma unroll
-    for (int j = 0; j < SF_BWT; ++j) {
+    for (int j = 0; j < BWT; ++j) {
       a[j] = sf_mfma(bc[j].x, dre[0], a[j]);
       a[j] = sf_mfma(bc[j].y, dre[1], a[j]);
       a[j] = sf_mfma(bc[j].z, dre[2], a[j]);
@@ -248,13 +321,13 @@ __global__ __launch_bounds__(256) void stft_bwd_kernel(int T, const float* __res
   };
 
   Raw raw = {};
-  float4 bcA[SF_BWT], bsA[SF_BWT], bcB[SF_BWT], bsB[SF_BWT];
+  float4 bcA[BWT], bsA[BWT], bcB[BWT], bsB[BWT];
   float drA[4], diA[4], drB[4], diB[4];
   load_raw(0, raw);
   load_b(0, bcA, bsA);
   make_d(0, raw, drA, diA);
-  for (int bg = 0; bg < SF_NBT; bg += 2) {
-    const bool odd = bg + 1 < SF_NBT, next = bg + 2 < SF_NBT;
+  for (int bg = 0; bg < R::NBT; bg += 2) {
+    const bool odd = bg + 1 < R::NBT, next = bg + 2 < R::NBT;
     if (odd) {
       load_raw(bg + 1, raw);
       load_b(bg + 1, bcB, bsB);
@@ -268,37 +341,94 @@ __global__ __launch_bounds__(256) void stft_bwd_kernel(int T, const float* __res
     if (odd) step(drB, diB, bcB, bsB, acc[1]);
     if (next) make_d(bg + 2, raw, drA, diA);
   }
-  // lane: frame t, samples (nt0 + j) 16 + fk + r of the frame
+  // lane: frame t, taps (nt0 + j) 16 + fk + r of the window's support
   if (valid) {
 #pragma unroll
-    for (int j = 0; j < SF_BWT; ++j) {
+    for (int j = 0; j < BWT; ++j) {
+      if (!R::BWD_EXACT && nt0 + j >= R::KT) continue;
       const f32x4 v = acc[0][j] + acc[1][j];
-      *(float4*)(dF + (size_t)t * SF_N + (nt0 + j) * 16 + fk) = float4{v[0], v[1], v[2], v[3]};
+      *(float4*)(dF + (size_t)t * R::KWP + (nt0 + j) * 16 + fk) = float4{v[0], v[1], v[2], v[3]};
     }
   }
 }
 
-// contributions of padded index j: the frames 256 t <= j < 256 t + 1024, t < T, ascending
+// contributions of padded index j: the frames t hop + pad <= j < t hop + pad + win, t < T, ascending
+template <class R>
 __device__ __forceinline__ float gather_j(const float* __restrict__ dF, int64_t j, int T) {
-  const int64_t tlo = j < SF_N ? 0 : (j - SF_N) / SF_HOP + 1;
-  int64_t thi = j / SF_HOP;
+  const int64_t a = j - R::PADL;   // tap 0 of frame t sits at a = t hop
+  if constexpr (R::PADL != 0)
+    if (a < 0) return 0.f;
+  const int64_t tlo = a < R::WIN ? 0 : (a - R::WIN) / R::HOP + 1;
+  int64_t thi = a / R::HOP;
   if (thi > T - 1) thi = T - 1;
   float s = 0.f;
-  for (int64_t t = tlo; t <= thi; ++t) s += dF[t * SF_N + (j - t * SF_HOP)];
+  for (int64_t t = tlo; t <= thi; ++t) s += dF[t * R::KWP + (a - t * R::HOP)];
   return s;
 }
-// dL_stft/dx_i: sample i itself (padded index i + 512), its image in the left reflection
-// (512 - i, i in 1..512) and in the right one (2 (n - 1) - i + 512, i in n - 513..n - 2), in that order
+// dL/dx_i of one transform: sample i itself (padded index i + n_fft / 2), its image in the left
+// reflection (n_fft / 2 - i, i in 1..n_fft / 2) and in the right one (2 (n - 1) - i + n_fft / 2, i in
+// n - 1 - n_fft / 2..n - 2), in that order
+template <class R>
 __device__ __forceinline__ float gather_sample(const float* __restrict__ dF, int i, int n, int T) {
-  float s = gather_j(dF, (int64_t)i + SF_N / 2, T);
-  if (i >= 1 && i <= SF_N / 2) s += gather_j(dF, SF_N / 2 - i, T);
-  if (i <= n - 2 && i >= n - SF_N / 2 - 1) s += gather_j(dF, 2 * (int64_t)(n - 1) - i + SF_N / 2, T);
+  constexpr int H = R::NFFT / 2;
+  float s = gather_j<R>(dF, (int64_t)i + H, T);
+  if (i >= 1 && i <= H) s += gather_j<R>(dF, H - i, T);
+  if (i <= n - 2 && i >= n - H - 1) s += gather_j<R>(dF, 2 * (int64_t)(n - 1) - i + H, T);
   return s;
 }
 
-__global__ void stft_gather_kernel(const float* __restrict__ dF, int n, int T, float* __restrict__ g) {
+// the two gathers: dL_stft/dx_i, and dL_mrstft/dx_i = the three transforms in the order 0, 1, 2, each times 1/3
+struct GatherSf {
+  const float* dF;
+  int T;
+  __device__ __forceinline__ float operator()(int i, int n) const { return gather_sample<SfR>(dF, i, n, T); }
+};
+struct GatherMr {
+  const float* dF[kMrRes];
+  int T[kMrRes];
+  __device__ __forceinline__ float operator()(int i, int n) const {
+    float s = MR_THIRD * gather_sample<MrR0>(dF[0], i, n, T[0]);
+    s += MR_THIRD * gather_sample<MrR1>(dF[1], i, n, T[1]);
+    s += MR_THIRD * gather_sample<MrR2>(dF[2], i, n, T[2]);
+    return s;
+  }
+};
+GatherSf gather_sf(const SpecWs& w) { return GatherSf{w.r[0].dF, w.r[0].T}; }
+GatherMr gather_mr(const SpecWs& w) {
+  GatherMr ga;
+  for (int r = 0; r < kMrRes; ++r) {
+    ga.dF[r] = w.r[r].dF;
+    ga.T[r] = w.r[r].T;
+  }
+  return ga;
+}
+
+template <class G>
+__global__ void stft_gather_kernel(G ga, int n, float* __restrict__ g) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) g[i] = gather_sample(dF, i, n, T);
+  if (i < n) g[i] = ga(i, n);
+}
+
+// g = (1 - alpha) g_point + alpha gather over the valid rows, 0 on pad rows (pscal: the point loss's scalars)
+template <class G>
+__global__ void loss_mix_kernel(const float* __restrict__ out, const float* __restrict__ y, int n, int rows, G ga,
+                                const float* __restrict__ pscal, int loss_mode, float wp, float ws, float gfac,
+                                float* __restrict__ g) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows) return;
+  float v = 0.f;
+  if (i < n) {
+    float gp;
+    if (loss_mode == 2) {
+      gp = pscal[SC_FSNR] * ((out[i] - pscal[SC_MX]) - (y[i] - pscal[SC_MY]));
+    } else {
+      const float err = out[i] - y[i];
+      gp = loss_mode == 1 ? (err > 0.f ? 1.0f : (err < 0.f ? -1.0f : 0.f)) * gfac : err * gfac;
+    }
+    v = wp * gp;
+    if (ws != 0.f) v += ws * ga(i, n);
+  }
+  g[i] = v;
 }
 
 // sums of x and y per 256 samples
@@ -359,8 +489,46 @@ __global__ void snr_sums2_kernel(const float* __restrict__ x, const float* __res
   }
 }
 
+// fp64 sum of cnt fp32 partials by one block of 256 in a fixed order (sh: 256 doubles); valid in thread 0
+__device__ __forceinline__ double block_total(const float* p, int cnt, double* sh) {
+  const int tid = threadIdx.x;
+  double a = 0.0;
+  for (int k = tid; k < cnt; k += 256) a += (double)p[k];
+  __syncthreads();
+  sh[tid] = a;
+  __syncthreads();
+  double s = 0.0;
+  if (tid == 0)
+    for (int k = 0; k < 256; ++k) s += sh[k];
+  return s;
+}
+
+// one transform's finished scalars from its nblk partials: S1, sum|dlog| -> L (returned, valid in
+// thread 0), c1 = 1 / (sqrt S1 sqrt Sy), c2 = 1 / (T bins), stored in sc[SC_S1..SC_C2]
+__device__ __forceinline__ double finish_term(const float* part, int npart, int nblk, int T, int bins, float* sc,
+                                              double* sh) {
+  const double S1 = block_total(part + (size_t)PT_S1 * npart, nblk, sh);
+  const double SL = block_total(part + (size_t)PT_SL * npart, nblk, sh);
+  double l = 0.0;
+  if (threadIdx.x == 0) {
+    const double Sy = (double)sc[SC_SY];
+    const double r1 = sqrt(S1), ry = sqrt(Sy), cnt = (double)T * bins;
+    l = r1 / ry + SL / cnt;
+    sc[SC_S1] = (float)S1;
+    sc[SC_SL] = (float)SL;
+    sc[SC_LSTFT] = (float)l;
+    sc[SC_C1] = (S1 > 0.0 && Sy > 0.0) ? (float)(1.0 / (r1 * ry)) : 0.f;
+    sc[SC_C2] = (float)(1.0 / cnt);
+  }
+  return l;
+}
+
+// The two finish kernels stay two: the single one mixes the fp64 point loss in the launch that forms
+// it, the multi-resolution one reads it back as fp32 from SC_LPOINT -- one kernel for both would change
+// the low bits of one path's loss history.
+//
 // the finished scalars (one block, fp64 sums of the fp32 partials in a fixed order):
-//   nstft > 0: S1, sum|dlog| -> L_stft, c1 = 1 / (sqrt S1 sqrt Sy), c2 = 1 / (T 513)
+//   nstft > 0: the single transform's term (finish_term)
 //   loss_mode 2: L_snr and the gradient factor; 0 / 1: the mean of sse_part's sum (MSE / L1); -1: none
 //   loss = (1 - alpha) point + alpha L_stft (loss_mode -1: L_stft), fp32, also to loss_out[0]
 __global__ __launch_bounds__(256) void loss_finish_kernel(float* __restrict__ scal, const float* __restrict__ part,
@@ -370,35 +538,13 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(float* __restrict__ sc
                                                           float* __restrict__ loss_out) {
   __shared__ double sh[256];
   const int tid = threadIdx.x;
-  auto total = [&](const float* p, int cnt) {  // valid in thread 0
-    double a = 0.0;
-    for (int k = tid; k < cnt; k += 256) a += (double)p[k];
-    __syncthreads();
-    sh[tid] = a;
-    __syncthreads();
-    double s = 0.0;
-    if (tid == 0)
-      for (int k = 0; k < 256; ++k) s += sh[k];
-    return s;
-  };
   double lstft = 0.0, lpoint = 0.0;
-  if (nstft > 0) {
-    const double S1 = total(part + (size_t)PT_S1 * npart, nstft);
-    const double SL = total(part + (size_t)PT_SL * npart, nstft);
-    if (tid == 0) {
-      const double Sy = (double)scal[SC_SY];
-      const double r1 = sqrt(S1), ry = sqrt(Sy), cnt = (double)T * SF_NB;
-      lstft = r1 / ry + SL / cnt;
-      scal[SC_S1] = (float)S1;
-      scal[SC_SL] = (float)SL;
-      scal[SC_LSTFT] = (float)lstft;
-      scal[SC_C1] = (S1 > 0.0 && Sy > 0.0) ? (float)(1.0 / (r1 * ry)) : 0.f;
-      scal[SC_C2] = (float)(1.0 / cnt);
-    }
-  }
+  if (nstft > 0) lstft = finish_term(part, npart, nstft, T, SfR::NB, scal, sh);
   if (loss_mode == 2) {
-    const double Syc = total(part + (size_t)PT_SYC * npart, nsnr) + total(part + (size_t)PT_SYC_LO * npart, nsnr);
-    const double Sr = total(part + (size_t)PT_SR * npart, nsnr) + total(part + (size_t)PT_SR_LO * npart, nsnr);
+    const double Syc = block_total(part + (size_t)PT_SYC * npart, nsnr, sh) +
+                       block_total(part + (size_t)PT_SYC_LO * npart, nsnr, sh);
+    const double Sr = block_total(part + (size_t)PT_SR * npart, nsnr, sh) +
+                      block_total(part + (size_t)PT_SR_LO * npart, nsnr, sh);
     if (tid == 0) {
       const double eps = 1e-8, q = Syc / (Sr + eps);
       lpoint = -10.0 * log10(q + eps);
@@ -408,7 +554,7 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(float* __restrict__ sc
       scal[SC_FSNR] = (float)((10.0 / log(10.0)) * (q / (q + eps)) * (2.0 / (Sr + eps)));
     }
   } else if (loss_mode >= 0) {
-    const double se = total(sse_part, nsum);
+    const double se = block_total(sse_part, nsum, sh);
     if (tid == 0) lpoint = se / n_total;
   }
   if (tid == 0) {
@@ -419,125 +565,241 @@ __global__ __launch_bounds__(256) void loss_finish_kernel(float* __restrict__ sc
   }
 }
 
-// g = (1 - alpha) g_point + alpha g_stft over the valid rows, 0 on pad rows
-__global__ void loss_mix_kernel(const float* __restrict__ out, const float* __restrict__ y, int n, int rows,
-                                const float* __restrict__ dF, int T, const float* __restrict__ scal, int loss_mode,
-                                float wp, float ws, float gfac, float* __restrict__ g) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= rows) return;
-  float v = 0.f;
-  if (i < n) {
-    float gp;
-    if (loss_mode == 2) {
-      gp = scal[SC_FSNR] * ((out[i] - scal[SC_MX]) - (y[i] - scal[SC_MY]));
-    } else {
-      const float err = out[i] - y[i];
-      gp = loss_mode == 1 ? (err > 0.f ? 1.0f : (err < 0.f ? -1.0f : 0.f)) * gfac : err * gfac;
+struct MrFinish {
+  const float* part[kMrRes];
+  int npart[kMrRes], nblk[kMrRes], T[kMrRes], NB[kMrRes];
+};
+// per resolution finish_term into scal[MR_SLOTS r + ...], then L_mrstft = (L_0 + L_1 + L_2) / 3 and
+// loss = (1 - alpha) point + alpha L_mrstft (loss_mode -1: L_mrstft), the point loss from
+// loss_finish_kernel's scalars.  nres 0: no spectral term (loss = point).
+// loss_out[0] <- loss; terms: loss_out[1..3] <- L_0, L_1, L_2
+__global__ __launch_bounds__(256) void mr_finish_kernel(MrFinish f, int nres, float* __restrict__ scal,
+                                                        const float* __restrict__ pscal, int loss_mode, double alpha,
+                                                        float* __restrict__ loss_out, int terms) {
+  __shared__ double sh[256];
+  const int tid = threadIdx.x;
+  double lsum = 0.0;
+  for (int r = 0; r < nres; ++r) {
+    const double l = finish_term(f.part[r], f.npart[r], f.nblk[r], f.T[r], f.NB[r], scal + MR_SLOTS * r, sh);
+    if (tid == 0) {
+      if (terms) loss_out[1 + r] = (float)l;
+      lsum += l;
     }
-    v = wp * gp;
-    if (ws != 0.f) v += ws * gather_sample(dF, i, n, T);
   }
-  g[i] = v;
+  if (tid == 0) {
+    const double lmr = nres > 0 ? lsum / 3.0 : 0.0;
+    const double lpoint = loss_mode < 0 ? 0.0 : (double)pscal[SC_LPOINT];
+    const double loss = loss_mode < 0 ? lmr : (1.0 - alpha) * lpoint + alpha * lmr;
+    scal[MR_SLOTS * kMrRes + MR_MEAN] = (float)lmr;
+    scal[MR_SLOTS * kMrRes + MR_POINT] = (float)lpoint;
+    scal[MR_SLOTS * kMrRes + MR_LOSS] = (float)loss;
+    if (loss_out) loss_out[0] = (float)loss;
+  }
 }
 
 inline size_t up4(size_t v) { return (v + 3) / 4 * 4; }
 
-}  // namespace
+// what the host needs of a trait: the sizes, the table fill and the two launches
+struct ResInfo {
+  int hop, nb, nbp, kwp, ft, fgy;
+  size_t tab;
+  void (*fill)(float* fwd);
+  hipError_t (*forward)(const float* x, int n, const float* basis, const SpecRes& q, bool target, hipStream_t s);
+  hipError_t (*backward)(const float* basis, const SpecRes& q, hipStream_t s);
+  int blocks(int64_t T) const { return (int)((T + ft - 1) / ft) * fgy; }   // forward blocks = partials per row
+};
 
-int64_t stft_frames(int64_t n) { return n > SF_N / 2 ? 1 + n / SF_HOP : 0; }
-
-int64_t stft_basis_floats() { return (int64_t)(2 * SF_TAB); }
-
-void stft_basis_fill(float* host) {
+template <class R>
+void fill_tables(float* fwd) {
   const double two_pi = 6.283185307179586476925286766559;
-  float* fwd = host;
-  float* bwd = host + SF_TAB;
-  for (size_t i = 0; i < 2 * SF_TAB; ++i) host[i] = 0.f;
-  for (int k = 0; k < SF_N; ++k) {
-    const double w = 0.5 - 0.5 * cos(two_pi * k / SF_N);  // periodic Hann
-    for (int b = 0; b < SF_NB; ++b) {
-      const double th = two_pi * (double)((k * b) % SF_N) / SF_N;  // the angle reduced exactly
+  float* bwd = fwd + R::TAB;
+  for (size_t i = 0; i < 2 * R::TAB; ++i) fwd[i] = 0.f;
+  for (int k = 0; k < R::WIN; ++k) {
+    const double w = 0.5 - 0.5 * cos(two_pi * k / R::WIN);  // periodic Hann over the window's support
+    for (int b = 0; b < R::NB; ++b) {
+      const double th = two_pi * (double)(((R::PADL + k) * b) % R::NFFT) / R::NFFT;  // the angle reduced exactly
       const float v[2] = {(float)(w * cos(th)), (float)(-w * sin(th))};
       for (int c = 0; c < 2; ++c) {
-        fwd[(((size_t)c * SF_KT + k / 16) * SF_NBP + b) * 16 + k % 16] = v[c];
-        bwd[(((size_t)c * SF_NBT + b / 16) * SF_N + k) * 16 + b % 16] = v[c];
+        fwd[(((size_t)c * R::KT + k / 16) * R::NBP + b) * 16 + k % 16] = v[c];
+        bwd[(((size_t)c * R::NBT + b / 16) * R::KWP + k) * 16 + b % 16] = v[c];
       }
     }
   }
 }
 
-static int stft_npart(int n, int rows) {
-  const int a = (int)((stft_frames(n) + SF_FT - 1) / SF_FT) * SF_FGY, b = (rows + 255) / 256;
-  return (int)up4(a > b ? a : b);
+template <class R>
+hipError_t forward_r(const float* x, int n, const float* basis, const SpecRes& q, bool target, hipStream_t s) {
+  const dim3 grid((q.T + R::FT - 1) / R::FT, R::FGY);
+  if (target) {
+    hipLaunchKernelGGL((stft_fwd_kernel<R, true>), grid, dim3(256), 0, s, x, n, q.T, basis, q.ymag, q.ylog, nullptr,
+                       nullptr, q.part, q.npart);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return sum_to(q.part + (size_t)PT_S1 * q.npart, (int)(grid.x * grid.y), q.scal + SC_SY, 0, s);
+  }
+  hipLaunchKernelGGL((stft_fwd_kernel<R, false>), grid, dim3(256), 0, s, x, n, q.T, basis, q.re, q.im, q.ymag, q.ylog,
+                     q.part, q.npart);
+  return hipGetLastError();
 }
 
-int64_t stft_ws_floats(int n, int rows) {
-  const size_t T = (size_t)stft_frames(n);
-  return (int64_t)(4 * T * SF_NBP + T * SF_N + PT_ROWS * (size_t)stft_npart(n, rows) + 32 + up4(rows));
+template <class R>
+hipError_t backward_r(const float* basis, const SpecRes& q, hipStream_t s) {
+  hipLaunchKernelGGL((stft_bwd_kernel<R>), dim3((q.T + R::FT - 1) / R::FT, R::BGY), dim3(256), 0, s, q.T,
+                     basis + R::TAB, q.re, q.im, q.ymag, q.ylog, q.scal, q.dF);
+  return hipGetLastError();
 }
 
-StftWs stft_ws_map(float* ws, int n, int rows) {
-  StftWs w;
-  const size_t T = (size_t)stft_frames(n);
-  w.T = (int)T;
-  w.npart = stft_npart(n, rows);
-  w.re = ws;
-  w.im = w.re + T * SF_NBP;
-  w.ymag = w.im + T * SF_NBP;
-  w.ylog = w.ymag + T * SF_NBP;
-  w.dF = w.ylog + T * SF_NBP;
-  w.part = w.dF + T * SF_N;
-  w.scal = w.part + PT_ROWS * (size_t)w.npart;
-  w.gchain = w.scal + 32;
+template <class R>
+constexpr ResInfo info_of() {
+  return {R::HOP, R::NB, R::NBP, R::KWP, R::FT, R::FGY, R::TAB, fill_tables<R>, forward_r<R>, backward_r<R>};
+}
+// a loss's transforms, their tables one after the other
+const ResInfo kSfRes[1] = {info_of<SfR>()};
+const ResInfo kMrResInfo[kMrRes] = {info_of<MrR0>(), info_of<MrR1>(), info_of<MrR2>()};
+const ResInfo* res_of(SpecLoss k) { return k == SPEC_MRSTFT ? kMrResInfo : kSfRes; }
+int nres_of(SpecLoss k) { return k == SPEC_MRSTFT ? kMrRes : 1; }
+
+// re .. dF of one transform at p; returns the float after them
+float* map_res(SpecRes& q, const ResInfo& ri, float* p, size_t T) {
+  q.T = (int)T;
+  q.re = p;
+  q.im = q.re + T * ri.nbp;
+  q.ymag = q.im + T * ri.nbp;
+  q.ylog = q.ymag + T * ri.nbp;
+  q.dF = q.ylog + T * ri.nbp;
+  return q.dF + T * ri.kwp;
+}
+// the point loss's pieces at p; returns the float after them
+float* map_point(PointWs& pt, float* p, int npart, int rows) {
+  pt.npart = npart;
+  pt.part = p;
+  pt.scal = pt.part + PT_ROWS * (size_t)npart;
+  pt.gchain = pt.scal + 32;
+  return pt.gchain + up4(rows);
+}
+
+}  // namespace
+
+int64_t spec_frames(SpecLoss k, int64_t n, int r) {
+  if (n <= (k == SPEC_MRSTFT ? kMrMinN : kStftMinN) || r < 0 || r >= nres_of(k)) return 0;
+  return 1 + n / res_of(k)[r].hop;
+}
+
+int64_t spec_basis_floats(SpecLoss k) {
+  size_t f = 0;
+  for (int r = 0; r < nres_of(k); ++r) f += 2 * res_of(k)[r].tab;
+  return (int64_t)f;
+}
+
+void spec_basis_fill(SpecLoss k, float* host) {
+  for (int r = 0; r < nres_of(k); ++r) {
+    res_of(k)[r].fill(host);
+    host += 2 * res_of(k)[r].tab;
+  }
+}
+
+// the pieces of the workspace, each a multiple of 4 floats
+SpecWs spec_ws_map(SpecLoss k, float* ws, int n, int rows, int64_t* total) {
+  const ResInfo* ri = res_of(k);
+  const int bands = (rows + 255) / 256;
+  SpecWs w = {};
+  w.loss = k;
+  w.nres = nres_of(k);
+  float* p = ws;
+  if (k == SPEC_STFT) {
+    // one [PT_ROWS][npart] block and one scal[32] serve the transform and the point loss
+    const size_t T = (size_t)spec_frames(k, n, 0);
+    const int blocks = ri[0].blocks((int64_t)T);
+    p = map_res(w.r[0], ri[0], p, T);
+    p = map_point(w.pt, p, (int)up4(blocks > bands ? blocks : bands), rows);
+    w.r[0].part = w.pt.part;
+    w.r[0].npart = w.pt.npart;
+    w.r[0].scal = w.scal = w.pt.scal;
+  } else {
+    // per transform its own [2][npart_r], then scal[kMrScalFloats] (MR_SLOTS each), then the point loss
+    for (int r = 0; r < kMrRes; ++r) {
+      const size_t T = (size_t)spec_frames(k, n, r);
+      w.r[r].part = map_res(w.r[r], ri[r], p, T);
+      w.r[r].npart = (int)up4((size_t)ri[r].blocks((int64_t)T));
+      p = w.r[r].part + 2 * (size_t)w.r[r].npart;
+    }
+    w.scal = p;
+    for (int r = 0; r < kMrRes; ++r) w.r[r].scal = w.scal + MR_SLOTS * r;
+    p = map_point(w.pt, p + kMrScalFloats, (int)up4((size_t)bands), rows);
+  }
+  if (total) *total = (int64_t)(p - ws);
   return w;
 }
 
-hipError_t stft_forward(const float* x, int n, const float* basis, const StftWs& w, bool target, hipStream_t s) {
-  if (w.T < 1) return hipErrorInvalidValue;
-  const dim3 grid((w.T + SF_FT - 1) / SF_FT, SF_FGY);
-  if (target) {
-    hipLaunchKernelGGL(stft_fwd_kernel<true>, grid, dim3(256), 0, s, x, n, w.T, basis, w.ymag, w.ylog, nullptr, nullptr,
-                       w.part, w.npart);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return sum_to(w.part + (size_t)PT_S1 * w.npart, (int)(grid.x * grid.y), w.scal + SC_SY, 0, s);
+hipError_t spec_forward(const float* x, int n, const float* basis, const SpecWs& w, bool target, hipStream_t s) {
+  if (w.r[0].T < 1) return hipErrorInvalidValue;
+  const ResInfo* ri = res_of((SpecLoss)w.loss);
+  hipError_t e = hipSuccess;
+  for (int r = 0; r < w.nres && e == hipSuccess; ++r) {
+    e = ri[r].forward(x, n, basis, w.r[r], target, s);
+    basis += 2 * ri[r].tab;
   }
-  hipLaunchKernelGGL(stft_fwd_kernel<false>, grid, dim3(256), 0, s, x, n, w.T, basis, w.re, w.im, w.ymag, w.ylog,
-                     w.part, w.npart);
-  return hipGetLastError();
+  return e;
 }
 
-hipError_t snr_sums(const float* x, const float* y, int n, const StftWs& w, hipStream_t s) {
+hipError_t spec_backward(const float* basis, const SpecWs& w, hipStream_t s) {
+  if (w.r[0].T < 1) return hipErrorInvalidValue;
+  const ResInfo* ri = res_of((SpecLoss)w.loss);
+  hipError_t e = hipSuccess;
+  for (int r = 0; r < w.nres && e == hipSuccess; ++r) {
+    e = ri[r].backward(basis, w.r[r], s);
+    basis += 2 * ri[r].tab;
+  }
+  return e;
+}
+
+hipError_t snr_sums(const float* x, const float* y, int n, const SpecWs& w, hipStream_t s) {
   const int nblk = (n + 255) / 256;
-  hipLaunchKernelGGL(snr_sums1_kernel, dim3(nblk), dim3(256), 0, s, x, y, n, w.part, w.npart);
-  hipLaunchKernelGGL(snr_sums2_kernel, dim3(nblk), dim3(256), 0, s, x, y, n, w.part, w.npart, nblk, w.scal);
+  hipLaunchKernelGGL(snr_sums1_kernel, dim3(nblk), dim3(256), 0, s, x, y, n, w.pt.part, w.pt.npart);
+  hipLaunchKernelGGL(snr_sums2_kernel, dim3(nblk), dim3(256), 0, s, x, y, n, w.pt.part, w.pt.npart, nblk, w.pt.scal);
   return hipGetLastError();
 }
 
-hipError_t loss_finish(const StftWs& w, int n, const float* sse_part, int nsum, int loss_mode, double alpha,
+hipError_t loss_finish(const SpecWs& w, int n, const float* sse_part, int nsum, int loss_mode, double alpha,
                        double n_total, bool stft, float* loss_out, hipStream_t s) {
-  const int nstft = stft ? (w.T + SF_FT - 1) / SF_FT * SF_FGY : 0;
-  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, s, w.scal, w.part, w.npart, nstft, (n + 255) / 256,
-                     sse_part, nsum, loss_mode, alpha, n_total, w.T, loss_out);
+  const int nstft = stft ? kSfRes[0].blocks(w.r[0].T) : 0;
+  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(256), 0, s, w.pt.scal, w.pt.part, w.pt.npart, nstft,
+                     (n + 255) / 256, sse_part, nsum, loss_mode, alpha, n_total, w.r[0].T, loss_out);
   return hipGetLastError();
 }
 
-hipError_t stft_backward(const float* basis, const StftWs& w, hipStream_t s) {
-  if (w.T < 1) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(stft_bwd_kernel, dim3((w.T + SF_FT - 1) / SF_FT, SF_BGY), dim3(256), 0, s, w.T, basis + SF_TAB,
-                     w.re, w.im, w.ymag, w.ylog, w.scal, w.dF);
+hipError_t mrstft_finish(const SpecWs& w, bool stft, int loss_mode, double alpha, float* loss_out, bool terms,
+                         hipStream_t s) {
+  MrFinish f;
+  for (int r = 0; r < kMrRes; ++r) {
+    f.part[r] = w.r[r].part;
+    f.npart[r] = w.r[r].npart;
+    f.nblk[r] = kMrResInfo[r].blocks(w.r[r].T);
+    f.T[r] = w.r[r].T;
+    f.NB[r] = kMrResInfo[r].nb;
+  }
+  hipLaunchKernelGGL(mr_finish_kernel, dim3(1), dim3(256), 0, s, f, stft ? kMrRes : 0, w.scal, w.pt.scal, loss_mode,
+                     alpha, loss_out, terms ? 1 : 0);
   return hipGetLastError();
 }
 
-hipError_t stft_gather(int n, const StftWs& w, float* g_stft, hipStream_t s) {
-  hipLaunchKernelGGL(stft_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, s, w.dF, n, w.T, g_stft);
+hipError_t spec_gather(int n, const SpecWs& w, float* g, hipStream_t s) {
+  const dim3 grid((n + 255) / 256), block(256);
+  if (w.loss == SPEC_MRSTFT) hipLaunchKernelGGL(stft_gather_kernel<GatherMr>, grid, block, 0, s, gather_mr(w), n, g);
+  else hipLaunchKernelGGL(stft_gather_kernel<GatherSf>, grid, block, 0, s, gather_sf(w), n, g);
   return hipGetLastError();
 }
 
-hipError_t loss_mix(const float* out, const float* y, int n, int rows, const StftWs& w, int loss_mode, double alpha,
+hipError_t loss_mix(const float* out, const float* y, int n, int rows, const SpecWs& w, int loss_mode, double alpha,
                     float gfac, float* g, hipStream_t s) {
-  hipLaunchKernelGGL(loss_mix_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, out, y, n, rows, w.dF, w.T, w.scal,
-                     loss_mode, (float)(1.0 - alpha), (float)alpha, gfac, g);
+  const dim3 grid((rows + 255) / 256), block(256);
+  const float wp = (float)(1.0 - alpha), wsp = (float)alpha;
+  if (w.loss == SPEC_MRSTFT)
+    hipLaunchKernelGGL(loss_mix_kernel<GatherMr>, grid, block, 0, s, out, y, n, rows, gather_mr(w), w.pt.scal,
+                       loss_mode, wp, wsp, gfac, g);
+  else
+    hipLaunchKernelGGL(loss_mix_kernel<GatherSf>, grid, block, 0, s, out, y, n, rows, gather_sf(w), w.pt.scal,
+                       loss_mode, wp, wsp, gfac, g);
   return hipGetLastError();
 }
 

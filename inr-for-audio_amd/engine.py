@@ -245,25 +245,30 @@ def cast_shadows(spec, Ws, Whs, WThs, stream):
 LOSS_MODES = {"mse": 0, "mae": 1, "snr": 2}   # run.py:161-169 (MSELoss / L1Loss / auraloss SNRLoss)
 
 
-def stft_basis(device) -> torch.Tensor:
-    """The STFT loss's windowed cos / -sin tables (include/siren_hip.h "STFT and SNR losses"): computed
-    by the library in fp64 on the host, rounded to fp32 once, copied to `device`."""
-    lib = _lib.load()
-    host = torch.empty(int(lib.siren_stft_basis_floats()), dtype=torch.float32)
-    check(lib.siren_stft_basis_fill(host.data_ptr()), "siren_stft_basis_fill")
+STFT_LOSSES = ("stft", "mrstft")   # run.py:127-128: the single STFTLoss() or MultiResolutionSTFTLoss()
+# per stft_loss: the loss struct, its (alpha, basis, workspace) fields and the C entry points' prefix
+_SPECTRAL = {
+    "stft": (_lib.SirenSpectral, ("alpha", "stft_basis", "stft_ws"), "siren_stft", "siren_train_step_spectral"),
+    "mrstft": (_lib.SirenSpectralMR, ("alpha", "basis", "ws"), "siren_mrstft", "siren_train_step_mrstft"),
+}
+
+
+def _basis(stft_loss: str, device) -> torch.Tensor:
+    """A spectral loss's windowed cos / -sin tables (include/siren_hip.h "STFT and SNR losses" /
+    "Multi-resolution STFT loss"; per transform the rows over the window's support): computed by the
+    library in fp64 on the host, rounded to fp32 once, copied to `device`."""
+    lib, prefix = _lib.load(), _SPECTRAL[stft_loss][2]
+    host = torch.empty(int(getattr(lib, prefix + "_basis_floats")()), dtype=torch.float32)
+    check(getattr(lib, prefix + "_basis_fill")(host.data_ptr()), prefix + "_basis_fill")
     return host.to(device)
 
 
-STFT_LOSSES = ("stft", "mrstft")   # run.py:127-128: the single STFTLoss() or MultiResolutionSTFTLoss()
+def stft_basis(device) -> torch.Tensor:
+    return _basis("stft", device)
 
 
 def mrstft_basis(device) -> torch.Tensor:
-    """The multi-resolution STFT loss's tables (include/siren_hip.h "Multi-resolution STFT loss"): the three
-    transforms' windowed cos / -sin rows over each window's support, fp64 on the host rounded once."""
-    lib = _lib.load()
-    host = torch.empty(int(lib.siren_mrstft_basis_floats()), dtype=torch.float32)
-    check(lib.siren_mrstft_basis_fill(host.data_ptr()), "siren_mrstft_basis_fill")
-    return host.to(device)
+    return _basis("mrstft", device)
 
 
 def new_guard(device) -> torch.Tensor:
@@ -517,7 +522,7 @@ class SirenEngine(FitEngine):
         and more than 512 samples when alpha > 0; its last layer runs unfused.
 
         `stft_loss` (run.py:127-128): 'stft' is the single 1024 / 256 transform, 'mrstft' the mean of the
-        three of auraloss's MultiResolutionSTFTLoss() defaults (csrc/mrstft.hip), which needs more than
+        three of auraloss's MultiResolutionSTFTLoss() defaults (csrc/stft.hip), which needs more than
         1024 samples when alpha > 0."""
         if loss_mode not in LOSS_MODES:
             raise NotImplementedError(f"loss_mode={loss_mode!r}: the HIP path has {sorted(LOSS_MODES)}")
@@ -618,26 +623,17 @@ class SirenEngine(FitEngine):
         once, they never change -- the target's magnitudes, their logs and Sy."""
         lib, b, n, dev = self.lib, self.batches[0], self.n_local, self.device
         assert self.n_micro == 1 and n == self.n_total
-        if self.stft_loss == "mrstft":   # run.py:127: the same pieces per resolution (csrc/mrstft.hip)
-            self.stft_ws = torch.zeros(int(lib.siren_mrstft_workspace_floats(n, self.rows)), dtype=torch.float32,
-                                       device=dev)
-            self.spectral_struct = sp = _lib.SirenSpectralMR()
-            sp.alpha, sp.ws = self.alpha, ptr(self.stft_ws)
-            if self.alpha != 0.0:
-                self.stft_basis = mrstft_basis(dev)
-                sp.basis = ptr(self.stft_basis)
-                check(lib.siren_mrstft_forward(ptr(self.target), n, self.rows, ptr(self.stft_basis),
-                                               ptr(self.stft_ws), 1, self._stream()), "siren_mrstft_forward")
-            return
-        self.stft_ws = torch.zeros(int(lib.siren_stft_workspace_floats(n, self.rows)), dtype=torch.float32,
-                                   device=dev)
-        self.spectral_struct = sp = _lib.SirenSpectral()
-        sp.alpha, sp.stft_ws = self.alpha, ptr(self.stft_ws)
+        struct, (f_alpha, f_basis, f_ws), prefix, _ = _SPECTRAL[self.stft_loss]   # run.py:127-128
+        self.stft_ws = torch.zeros(int(getattr(lib, prefix + "_workspace_floats")(n, self.rows)),
+                                   dtype=torch.float32, device=dev)
+        self.spectral_struct = sp = struct()
+        setattr(sp, f_alpha, self.alpha)
+        setattr(sp, f_ws, ptr(self.stft_ws))
         if self.alpha != 0.0:
-            self.stft_basis = stft_basis(dev)
-            sp.stft_basis = ptr(self.stft_basis)
-            check(lib.siren_stft_forward(ptr(self.target), n, self.rows, ptr(self.stft_basis), ptr(self.stft_ws), 1,
-                                         self._stream()), "siren_stft_forward")
+            self.stft_basis = _basis(self.stft_loss, dev)
+            setattr(sp, f_basis, ptr(self.stft_basis))
+            check(getattr(lib, prefix + "_forward")(ptr(self.target), n, self.rows, ptr(self.stft_basis),
+                                                    ptr(self.stft_ws), 1, self._stream()), prefix + "_forward")
 
     def _setup_buckets(self):
         """One bucket per layer (contiguous in the flat layout): the head (+ the SSE tail slot),
@@ -669,15 +665,10 @@ class SirenEngine(FitEngine):
     def _launch_grads(self):
         s = self._stream()
         for b in self.batches:
-            if self.spectral and self.stft_loss == "mrstft":   # run.py:127, :160-169
-                check(self.lib.siren_train_step_mrstft(ctypes.byref(self.net), ctypes.byref(self.grad_struct),
-                                                       ctypes.byref(b), ctypes.byref(self.spectral_struct), s),
-                      "siren_train_step_mrstft")
-                continue
-            if self.spectral:   # run.py:160-169: the STFT / SNR step (one batch: the whole signal)
-                check(self.lib.siren_train_step_spectral(ctypes.byref(self.net), ctypes.byref(self.grad_struct),
-                                                         ctypes.byref(b), ctypes.byref(self.spectral_struct), s),
-                      "siren_train_step_spectral")
+            if self.spectral:   # run.py:127-128, :160-169: the STFT / SNR step (one batch: the whole signal)
+                step = _SPECTRAL[self.stft_loss][3]
+                check(getattr(self.lib, step)(ctypes.byref(self.net), ctypes.byref(self.grad_struct),
+                                              ctypes.byref(b), ctypes.byref(self.spectral_struct), s), step)
                 continue
             check(self.lib.siren_train_step(ctypes.byref(self.net), ctypes.byref(self.grad_struct),
                                             ctypes.byref(b), s), "siren_train_step")

@@ -1,10 +1,11 @@
-"""The multi-resolution STFT loss kernels (csrc/mrstft.hip; run.py:127, :160) one entry point at a
+"""The multi-resolution STFT loss kernels (csrc/stft.hip; run.py:127, :160) one entry point at a
 time against tests/mrstft_ref.py, the definition written with torch.stft and autograd in fp64.
 
 Inputs (spectral_ref.signals, seed 1): n = 1536 (every frame of the 2048-point resolution touches a
 reflected edge), n = 5003 (a multiple of no hop, rows pad to 5120; T = 42 / 21 / 101), n = 8448, and the
-clamp case n = 5003 with x[:2048] = 0.  All four pass the clamp-margin precondition at all three
-resolutions.  The kernels get the fp32 roundings of x and y, and the fp64 reference is evaluated on
+clamp case n = 5003 with x[:2048] = 0; and, with seed 2, n = 1025 (the shortest signal the loss takes,
+one or two tiles per grid; seed 1 fails the precondition there).  All five pass the clamp-margin
+precondition at all three resolutions.  The kernels get the fp32 roundings of x and y, and the fp64 reference is evaluated on
 those same fp32 values."""
 import numpy as np
 import pytest
@@ -14,7 +15,8 @@ import mrstft_ref as mr
 
 pytestmark = pytest.mark.gpu
 
-CASES = {"n1536": (1536, False), "n5003": (5003, False), "n8448": (8448, False), "clamp": (5003, True)}
+CASES = {"n1025": (1025, False, 2), "n1536": (1536, False), "n5003": (5003, False), "n8448": (8448, False),
+         "clamp": (5003, True)}   # (n, clamp[, seed])
 NBP = (528, 1040, 272)            # bins padded to 16, per resolution
 CHAIN = (304, 608, 128)           # the longer of the two interleaved fp32 chains: 16 * ceil(ceil(win / 16) / 2)
 _REF, _GPU, _BASIS = {}, {}, {}
@@ -27,8 +29,8 @@ def rows_of(n):
 def ref(case):
     """Inputs and fp64 / fp32 CPU results of one case: computed once, shared, never modified."""
     if case not in _REF:
-        n, clamp = CASES[case]
-        x, y = mr.signals(n)
+        n, clamp, *seed = CASES[case]
+        x, y = mr.signals(n, *seed)
         if clamp:
             x[:2048] = 0
         x32, y32 = x.float(), y.float()

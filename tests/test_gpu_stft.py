@@ -1,7 +1,8 @@
 """The STFT / SNR loss kernels (csrc/stft.hip; run.py:126-128, :160-169) one entry point at a time
 against tests/spectral_ref.py, the definition written with torch.stft and autograd in fp64.
 
-Inputs (spectral_ref.signals, seed 1): n = 1536 (T = 7, every frame touches a reflected edge),
+Inputs (spectral_ref.signals, seed 1): n = 513 (the shortest signal the transform takes: T = 3, one
+tile in every grid, every frame mostly reflection), n = 1536 (T = 7, every frame touches a reflected edge),
 n = 5000 (not a multiple of the hop, rows pad to 5120, T = 20 = one 16-frame tile plus a remainder),
 n = 8448 (T = 34), and the clamp case n = 5000 with x[:2048] = 0 (seven silent frames).  The kernels
 get the fp32 roundings of x and y, and the fp64 reference is evaluated on those same fp32 values."""
@@ -13,7 +14,7 @@ import spectral_ref as sr
 
 pytestmark = pytest.mark.gpu
 
-CASES = {"n1536": (1536, False), "n5000": (5000, False), "n8448": (8448, False), "clamp": (5000, True)}
+CASES = {"n513": (513, False), "n1536": (1536, False), "n5000": (5000, False), "n8448": (8448, False), "clamp": (5000, True)}
 _REF, _GPU, _BASIS = {}, {}, {}
 
 

@@ -1,6 +1,6 @@
-"""Cost of the multi-resolution STFT loss (csrc/mrstft.hip; run.py:127, :160) at the reference's live
+"""Cost of the multi-resolution STFT loss (csrc/stft.hip; run.py:127, :160) at the reference's live
 config (run.py:466): a first sine layer + 4 Snake hidden layers, width 256, 441 000 rows (10 s at
-44.1 kHz; T = 3676 / 1838 / 8821 frames), beside the single-resolution kernels of csrc/stft.hip
+44.1 kHz; T = 3676 / 1838 / 8821 frames), beside the single-resolution kernels of the same file
 re-measured in the same process as the yardstick.
 
 * the individual entry points (HIP events around `reps` back-to-back calls, rounds interleaved):
