@@ -451,6 +451,59 @@ typedef struct siren_spectral_mr {
 int siren_train_step_mrstft(const siren_net* net, const siren_grads* grads, siren_batch* batch,
                             const siren_spectral_mr* loss, void* stream);
 
+/* ---- The spectral losses across micro-batches and ranks (run.py:126-128, :160-169 on a signal that one
+ * batch on one GPU does not hold; the sweeps of run.py:439-476 on more than one GPU) ------------------
+ * The loss of siren_train_step_spectral / _mrstft in three calls on a signal-length `x` = out [n] that the
+ * caller assembled from every micro-batch's (and rank's) siren_forward, target `y` [n], `ws` the
+ * whole-signal workspace of siren_{stft,mrstft}_workspace_floats(n, rows) (rows >= n; its target side set
+ * once by siren_*_forward(y, ..., 1)).  The caller then runs siren_backward per micro-batch from its slice
+ * of g.  loss_mode 0 MSE | 1 L1 | 2 SNR, alpha in [0, 1] (else SIREN_ERR_CONFIG); alpha 0 runs no transform
+ * and ignores basis and win.
+ *
+ * A transform's frames come in blocks of 16; a call runs the frame blocks [win[2 r], win[2 r + 1]) of
+ * transform r (win: HOST array of 2 ints for stft, 6 for mrstft), and a block writes its re / im / dF rows
+ * and its partial where the whole-signal launch writes them.  siren_*_window gives, for the samples
+ * [lo, hi), blocks[0..1] = the blocks to run (every block with a frame over i + n_fft / 2 or one of i's two
+ * reflected images, lo <= i < hi) and blocks[2..3] = the blocks owned (first frame t0 with min(t0 hop,
+ * n - 1) in [lo, hi)): for any partition of [0, n) the owned ranges partition the blocks, and the run range
+ * contains the owned one.  Ranks zero the partials of blocks they do not own and sum the arrays
+ * (x + 0 = x: exact); with complete arrays every scalar is the one-batch step's, bit for bit.
+ * Status: NULL pointers SIREN_ERR_NULL; n too short, rows < n, a window outside [0, blocks], lo > hi or
+ * hi > n SIREN_ERR_SHAPE -- all before any launch. */
+/* run.py:128, :160 blocks[4] (HOST) for the samples [lo, hi) of an n-sample signal */
+int siren_stft_window(int32_t n, int32_t lo, int32_t hi, int32_t* blocks);
+/* run.py:160 where the partials live (-1: bad shape or `which`): 0 float offset in ws of the transform's
+ * [2][npart] partials {S1, sum|dlog|}, 1 npart, 2 its frame blocks B, 3 its grid.y (block (b, y) owns the
+ * partial y B + b of either row), 4 float offset of the point loss's [8][npart'] partials, 5 npart' */
+int64_t siren_stft_signal_parts(int32_t n, int32_t rows, int32_t which);
+/* run.py:160-169 partials of the point loss over the whole signal (L1 / MSE per 256 samples, or the SNR
+ * sums) and the transform of x on the window */
+int siren_stft_signal_forward(const float* x, const float* y, int32_t n, int32_t rows, int32_t loss_mode, double alpha,
+                              const float* basis, float* ws, const int32_t* win, void* stream);
+/* run.py:160-169 the fp64 finishes over the complete partial arrays; loss[0] = (1 - alpha) point + alpha
+ * L_stft (device) */
+int siren_stft_signal_finish(int32_t n, int32_t rows, int32_t loss_mode, double alpha, float* ws, float* loss,
+                             void* stream);
+/* autograd of run.py:160-169 after the finish: the transposed GEMM on the window, then g[lo..hi) =
+ * dLoss/dx, indexed by global sample (g [n], device) */
+int siren_stft_signal_backward(const float* x, const float* y, int32_t n, int32_t rows, int32_t loss_mode, double alpha,
+                               const float* basis, float* ws, const int32_t* win, int32_t lo, int32_t hi, float* g,
+                               void* stream);
+/* run.py:127, :160 the same for the multi-resolution loss; r = 0, 1, 2 */
+int siren_mrstft_window(int32_t n, int32_t r, int32_t lo, int32_t hi, int32_t* blocks);
+/* run.py:127, :160 resolution r's partials, `which` as siren_stft_signal_parts */
+int64_t siren_mrstft_signal_parts(int32_t n, int32_t rows, int32_t r, int32_t which);
+/* run.py:127, :160-169 */
+int siren_mrstft_signal_forward(const float* x, const float* y, int32_t n, int32_t rows, int32_t loss_mode,
+                                double alpha, const float* basis, float* ws, const int32_t* win, void* stream);
+/* run.py:127, :160-169 loss[0] = (1 - alpha) point + alpha L_mrstft */
+int siren_mrstft_signal_finish(int32_t n, int32_t rows, int32_t loss_mode, double alpha, float* ws, float* loss,
+                               void* stream);
+/* autograd of run.py:127, :160-169 */
+int siren_mrstft_signal_backward(const float* x, const float* y, int32_t n, int32_t rows, int32_t loss_mode,
+                                 double alpha, const float* basis, float* ws, const int32_t* win, int32_t lo,
+                                 int32_t hi, float* g, void* stream);
+
 /* autograd addmm dW: slab[s] = partial dZ^T Y over coordinate slice s, tile edge 128/256
  * (0 = siren_dw_tile(rows, hidden)); siren_dw_reduce must get the same tile. */
 int siren_inner_bwd_dw(const uint16_t* Y, const uint16_t* dZ, int32_t rows, int32_t hidden,

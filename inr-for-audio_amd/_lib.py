@@ -184,6 +184,19 @@ _SIGS = {
     "siren_train_step_mrstft": (ctypes.c_int, [ctypes.POINTER(SirenNet), ctypes.POINTER(SirenGrads),
                                                ctypes.POINTER(SirenBatch), ctypes.POINTER(SirenSpectralMR), _p]),
     "siren_snr_loss": (ctypes.c_int, [_p, _p, _i32, _i32, _p, _p, _p, _p]),
+    # the split spectral step (run.py:126-128, :160-169 across micro-batches and ranks)
+    "siren_stft_window": (ctypes.c_int, [_i32, _i32, _i32, _p]),
+    "siren_stft_signal_parts": (_i64, [_i32, _i32, _i32]),
+    "siren_stft_signal_forward": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, ctypes.c_double, _p, _p, _p, _p]),
+    "siren_stft_signal_finish": (ctypes.c_int, [_i32, _i32, _i32, ctypes.c_double, _p, _p, _p]),
+    "siren_stft_signal_backward": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, ctypes.c_double, _p, _p, _p, _i32, _i32,
+                                                  _p, _p]),
+    "siren_mrstft_window": (ctypes.c_int, [_i32, _i32, _i32, _i32, _p]),
+    "siren_mrstft_signal_parts": (_i64, [_i32, _i32, _i32, _i32]),
+    "siren_mrstft_signal_forward": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, ctypes.c_double, _p, _p, _p, _p]),
+    "siren_mrstft_signal_finish": (ctypes.c_int, [_i32, _i32, _i32, ctypes.c_double, _p, _p, _p]),
+    "siren_mrstft_signal_backward": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, ctypes.c_double, _p, _p, _p, _i32, _i32,
+                                                    _p, _p]),
     "siren_inner_bwd_dw": (ctypes.c_int, [_p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "siren_dw_reduce": (ctypes.c_int, [_p, _i32, _i32, _i32, _p, _i32, _p, _p]),
     "siren_nt_tile": (_i32, [_i32, _i32]),

@@ -915,6 +915,128 @@ int siren_snr_loss(const float* x, const float* y, int32_t n, int32_t rows, floa
   return (int)loss_mix(x, y, n, n, w, 2, 0.0, 0.f, g, s);
 }
 
+// ---- the split spectral step (run.py:126-128, :160-169 across micro-batches and ranks) ----
+// The loss of run_spectral_step in three calls on a signal-length `out`: the partials (transforms on a
+// window of frame blocks), the fp64 finishes over the complete partial arrays, and g over [lo, hi).
+// With the same out every scalar is run_spectral_step's bit for bit: the same kernels, the L1 / MSE
+// partials by head_loss's arithmetic and reduction (point_partials), trailing zero partials aside.
+static int signal_config(int32_t loss_mode, double alpha) {
+  return loss_mode < 0 || loss_mode > 2 || !(alpha >= 0.0 && alpha <= 1.0) ? SIREN_ERR_CONFIG : SIREN_OK;
+}
+
+// per transform 0 <= win[2 r] <= win[2 r + 1] <= its frame blocks
+static int window_ok(SpecLoss k, int32_t n, const int32_t* win) {
+  for (int r = 0; r < (k == SPEC_MRSTFT ? kMrRes : 1); ++r)
+    if (win[2 * r] < 0 || win[2 * r] > win[2 * r + 1] || win[2 * r + 1] > spec_frame_blocks(k, n, r))
+      return SIREN_ERR_SHAPE;
+  return SIREN_OK;
+}
+
+static int spec_window_api(SpecLoss k, int32_t n, int32_t r, int32_t lo, int32_t hi, int32_t* blocks) {
+  if (!blocks) return SIREN_ERR_NULL;
+  if (n > kStftMaxN || spec_frames(k, n, r) < 1 || lo < 0 || lo > hi || hi > n) return SIREN_ERR_SHAPE;
+  spec_window(k, r, n, lo, hi, blocks, blocks + 2);
+  return SIREN_OK;
+}
+
+static int64_t spec_signal_parts(SpecLoss k, int32_t n, int32_t rows, int32_t r, int32_t which) {
+  if (spec_shape(k, n, rows, true)) return -1;
+  const SpecWs w = spec_ws_map(k, nullptr, n, rows);
+  if (r < 0 || r >= w.nres) return -1;
+  switch (which) {
+    case 0: return (int64_t)((uintptr_t)w.r[r].part / sizeof(float));
+    case 1: return w.r[r].npart;
+    case 2: return spec_frame_blocks(k, n, r);
+    case 3: return spec_grid_y(k, r);
+    case 4: return (int64_t)((uintptr_t)w.pt.part / sizeof(float));
+    case 5: return w.pt.npart;
+  }
+  return -1;
+}
+
+static int spec_signal_forward(SpecLoss k, const float* x, const float* y, int32_t n, int32_t rows, int32_t loss_mode,
+                               double alpha, const float* basis, float* ws, const int32_t* win, void* stream) {
+  const bool stft = alpha != 0.0;
+  if (!x || !y || !ws || (stft && (!basis || !win))) return SIREN_ERR_NULL;
+  int st = signal_config(loss_mode, alpha);
+  if (st || (st = spec_shape(k, n, rows, stft)) || (stft && (st = window_ok(k, n, win)))) return st;
+  hipStream_t s = S(stream);
+  const SpecWs w = spec_ws_map(k, ws, n, rows);
+  if (loss_mode == 2) SIREN_TRY(snr_sums(x, y, n, w, s));
+  else SIREN_TRY(point_partials(x, y, n, loss_mode, w, s));
+  if (stft) SIREN_TRY(spec_forward(x, n, basis, w, false, s, win));
+  return SIREN_OK;
+}
+
+static int spec_signal_finish(SpecLoss k, int32_t n, int32_t rows, int32_t loss_mode, double alpha, float* ws,
+                              float* loss, void* stream) {
+  if (!ws || !loss) return SIREN_ERR_NULL;
+  const bool stft = alpha != 0.0, mr = k == SPEC_MRSTFT;
+  int st = signal_config(loss_mode, alpha);
+  if (st || (st = spec_shape(k, n, rows, stft))) return st;
+  hipStream_t s = S(stream);
+  const SpecWs w = spec_ws_map(k, ws, n, rows);
+  // run_spectral_step's two finishes, the L1 / MSE partials from the workspace's own row
+  SIREN_TRY(loss_finish(w, n, w.pt.part + (size_t)PT_SSE * w.pt.npart, bands(n), loss_mode, mr ? 0.0 : alpha,
+                        (double)n, stft && !mr, mr ? nullptr : loss, s));
+  if (mr) SIREN_TRY(mrstft_finish(w, stft, loss_mode, alpha, loss, false, s));
+  return SIREN_OK;
+}
+
+static int spec_signal_backward(SpecLoss k, const float* x, const float* y, int32_t n, int32_t rows, int32_t loss_mode,
+                                double alpha, const float* basis, float* ws, const int32_t* win, int32_t lo,
+                                int32_t hi, float* g, void* stream) {
+  const bool stft = alpha != 0.0;
+  if (!x || !y || !ws || !g || (stft && (!basis || !win))) return SIREN_ERR_NULL;
+  int st = signal_config(loss_mode, alpha);
+  if (st || (st = spec_shape(k, n, rows, stft)) || (stft && (st = window_ok(k, n, win)))) return st;
+  if (lo < 0 || lo > hi || hi > n) return SIREN_ERR_SHAPE;
+  hipStream_t s = S(stream);
+  const SpecWs w = spec_ws_map(k, ws, n, rows);
+  if (stft) SIREN_TRY(spec_backward(basis, w, s, win));
+  return (int)loss_mix(x, y, n, hi, w, loss_mode, alpha, loss_gfac(loss_mode, (double)n), g, s, lo);
+}
+
+int siren_stft_window(int32_t n, int32_t lo, int32_t hi, int32_t* blocks) {
+  return spec_window_api(SPEC_STFT, n, 0, lo, hi, blocks);
+}
+int64_t siren_stft_signal_parts(int32_t n, int32_t rows, int32_t which) {
+  return spec_signal_parts(SPEC_STFT, n, rows, 0, which);
+}
+int siren_stft_signal_forward(const float* x, const float* y, int32_t n, int32_t rows, int32_t loss_mode, double alpha,
+                              const float* basis, float* ws, const int32_t* win, void* stream) {
+  return spec_signal_forward(SPEC_STFT, x, y, n, rows, loss_mode, alpha, basis, ws, win, stream);
+}
+int siren_stft_signal_finish(int32_t n, int32_t rows, int32_t loss_mode, double alpha, float* ws, float* loss,
+                             void* stream) {
+  return spec_signal_finish(SPEC_STFT, n, rows, loss_mode, alpha, ws, loss, stream);
+}
+int siren_stft_signal_backward(const float* x, const float* y, int32_t n, int32_t rows, int32_t loss_mode, double alpha,
+                               const float* basis, float* ws, const int32_t* win, int32_t lo, int32_t hi, float* g,
+                               void* stream) {
+  return spec_signal_backward(SPEC_STFT, x, y, n, rows, loss_mode, alpha, basis, ws, win, lo, hi, g, stream);
+}
+
+int siren_mrstft_window(int32_t n, int32_t r, int32_t lo, int32_t hi, int32_t* blocks) {
+  return spec_window_api(SPEC_MRSTFT, n, r, lo, hi, blocks);
+}
+int64_t siren_mrstft_signal_parts(int32_t n, int32_t rows, int32_t r, int32_t which) {
+  return spec_signal_parts(SPEC_MRSTFT, n, rows, r, which);
+}
+int siren_mrstft_signal_forward(const float* x, const float* y, int32_t n, int32_t rows, int32_t loss_mode,
+                                double alpha, const float* basis, float* ws, const int32_t* win, void* stream) {
+  return spec_signal_forward(SPEC_MRSTFT, x, y, n, rows, loss_mode, alpha, basis, ws, win, stream);
+}
+int siren_mrstft_signal_finish(int32_t n, int32_t rows, int32_t loss_mode, double alpha, float* ws, float* loss,
+                               void* stream) {
+  return spec_signal_finish(SPEC_MRSTFT, n, rows, loss_mode, alpha, ws, loss, stream);
+}
+int siren_mrstft_signal_backward(const float* x, const float* y, int32_t n, int32_t rows, int32_t loss_mode,
+                                 double alpha, const float* basis, float* ws, const int32_t* win, int32_t lo,
+                                 int32_t hi, float* g, void* stream) {
+  return spec_signal_backward(SPEC_MRSTFT, x, y, n, rows, loss_mode, alpha, basis, ws, win, lo, hi, g, stream);
+}
+
 int siren_inner_bwd_dw(const uint16_t* Y, const uint16_t* dZ, int32_t rows, int32_t hidden,
                        int32_t splits, int32_t tile, float* slab, void* stream) {
   if (!Y || !dZ || !slab) return SIREN_ERR_NULL;

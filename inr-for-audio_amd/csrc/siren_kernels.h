@@ -245,12 +245,25 @@ enum { MR_SLOTS = 8, MR_MEAN = 0, MR_POINT = 1, MR_LOSS = 2 };
 // (the SNR sums are kept as a float pair hi + lo: L_snr crosses zero where the fit's residual
 // equals the signal, and an fp32 sum's 2^-24 is 1e-5 of a loss of 0.007 dB)
 enum { PT_S1 = 0, PT_SL = 1, PT_SX = 2, PT_SYM = 3, PT_SYC = 4, PT_SR = 5, PT_SYC_LO = 6, PT_SR_LO = 7, PT_ROWS = 8 };
+// the split step keeps the L1 / MSE partials per 256 samples of the whole signal in the row
+// that only the SNR loss uses otherwise (a one-batch step has them in siren_batch.sse_part)
+enum { PT_SSE = PT_SX };
 int64_t spec_frames(SpecLoss k, int64_t n, int r);   // 1 + n / hop_r (0: n too short for the loss, or no such r)
 int64_t spec_basis_floats(SpecLoss k);
 void spec_basis_fill(SpecLoss k, float* host);  // per transform both table layouts, fp64 on the host rounded once
 SpecWs spec_ws_map(SpecLoss k, float* ws, int n, int rows, int64_t* total = nullptr);
+// frame blocks (16 frames each) of transform r over the whole signal, and its forward grid.y: the block
+// (bx, by) writes the partial by * spec_frame_blocks + bx of its two rows
+int spec_frame_blocks(SpecLoss k, int64_t n, int r);
+int spec_grid_y(SpecLoss k, int r);
+// the frame blocks of transform r that the samples [lo, hi) need (compute) and contribute partials for (owned)
+void spec_window(SpecLoss k, int r, int n, int lo, int hi, int compute[2], int owned[2]);
 // target: ymag, ylog and Sy per transform; else re, im and the partials of S1 and sum|dlog|
-hipError_t spec_forward(const float* x, int n, const float* basis, const SpecWs& w, bool target, hipStream_t s);
+// win (model side; null: every block): per transform the frame blocks [win[2 r], win[2 r + 1]) that run
+hipError_t spec_forward(const float* x, int n, const float* basis, const SpecWs& w, bool target, hipStream_t s,
+                        const int* win = nullptr);
+// the L1 (loss_mode 1) / MSE partials per 256 samples of out against y -> row PT_SSE of w.pt.part
+hipError_t point_partials(const float* out, const float* y, int n, int loss_mode, const SpecWs& w, hipStream_t s);
 // partials of the means, then of sum yc^2 and sum (xc - yc)^2
 hipError_t snr_sums(const float* x, const float* y, int n, const SpecWs& w, hipStream_t s);
 // the point loss's finished scalars; loss_mode 0 / 1: sum(sse_part) / n_total, 2: L_snr, -1: none.
@@ -263,11 +276,11 @@ hipError_t loss_finish(const SpecWs& w, int n, const float* sse_part, int nsum, 
 // loss_out[1..3] <- L_0, L_1, L_2
 hipError_t mrstft_finish(const SpecWs& w, bool stft, int loss_mode, double alpha, float* loss_out, bool terms,
                          hipStream_t s);
-hipError_t spec_backward(const float* basis, const SpecWs& w, hipStream_t s);   // -> every r[i].dF
+hipError_t spec_backward(const float* basis, const SpecWs& w, hipStream_t s, const int* win = nullptr);  // -> r[i].dF
 hipError_t spec_gather(int n, const SpecWs& w, float* g, hipStream_t s);        // dF -> dL_stft / dL_mrstft / dx [n]
-// g[rows] = (1 - alpha) g_point + alpha gather(dF), 0 on pad rows
+// g[lo .. rows) = (1 - alpha) g_point + alpha gather(dF), 0 on pad rows
 hipError_t loss_mix(const float* out, const float* y, int n, int rows, const SpecWs& w, int loss_mode, double alpha,
-                    float gfac, float* g, hipStream_t s);
+                    float gfac, float* g, hipStream_t s, int lo = 0);
 
 // KAN (kan.hip): fp32, grid_size 5, spline_order 3 (9 A-columns per input)
 // fused layer kernels (the bases are recomputed in LDS; A and dA never reach HBM)

@@ -62,6 +62,14 @@
 // The gather then sums, per sample, the <= 5 frames that cover it (win / hop <= 5) and the same for its
 // reflected images, ascending; L_mrstft adds its transforms in the order 0, 1, 2, each times 1/3 -- no
 // float atomics anywhere, two runs are bit-identical.  The scalars are finished in fp64 on the device.
+//
+// A window (the split step of a micro-batched or data-parallel fit): the forward and the
+// backward can run the frame blocks [b0, b1) of the whole signal's ceil(T / 16) alone, the mix (which
+// gathers as it goes) the samples [lo, hi) alone.  A block keeps the index it has in the whole-signal
+// launch (blockIdx.y * whole gridDim.x + block) for its re / im / dF rows and its partial, and the
+// workspace keeps the whole-signal layout; a window starts at a multiple of 16 frames, so the staging
+// maps and the alignment arguments above hold as they stand.  spec_window gives the blocks a sample
+// range needs (compute) and the ones whose partials it contributes (owned).
 #include <math.h>
 #include "siren_common.h"
 #include "siren_kernels.h"
@@ -142,13 +150,14 @@ __global__ __launch_bounds__(256) void stft_fwd_kernel(const float* __restrict__
                                                        const float* __restrict__ basis, float* __restrict__ o0,
                                                        float* __restrict__ o1, const float* __restrict__ ymag,
                                                        const float* __restrict__ ylog, float* __restrict__ part,
-                                                       int npart) {
+                                                       int npart, int blk0, int gx) {
   constexpr int WT = R::WT;
   __shared__ __attribute__((aligned(16))) float sig[R::LDS];
   __shared__ float scratch[4];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int t0 = blockIdx.x * R::FT;
+  const int bx = blk0 + blockIdx.x;   // the frame block of the whole signal's gx (a window starts at blk0)
+  const int t0 = bx * R::FT;
   const int64_t j0 = (int64_t)t0 * R::HOP + R::PADL;
   if constexpr (R::PITCH != 0) {
     for (int e = tid; e < R::FT * R::KWP; e += 256) {
@@ -241,7 +250,7 @@ __global__ __launch_bounds__(256) void stft_fwd_kernel(const float* __restrict__
   s1 = block_sum(s1, scratch);
   sl = block_sum(sl, scratch);
   if (tid == 0) {
-    const int blk = blockIdx.y * gridDim.x + blockIdx.x;
+    const int blk = blockIdx.y * gx + bx;
     part[(size_t)PT_S1 * npart + blk] = s1;
     part[(size_t)PT_SL * npart + blk] = sl;
   }
@@ -252,12 +261,13 @@ __global__ __launch_bounds__(256) void stft_bwd_kernel(int T, const float* __res
                                                        const float* __restrict__ re, const float* __restrict__ im,
                                                        const float* __restrict__ ymag,
                                                        const float* __restrict__ ylog,
-                                                       const float* __restrict__ scal, float* __restrict__ dF) {
+                                                       const float* __restrict__ scal, float* __restrict__ dF,
+                                                       int blk0) {
   constexpr int BWT = R::BWT;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15, fk = 4 * (lane >> 4);
-  const int t = blockIdx.x * R::FT + fr;
+  const int t = (blk0 + blockIdx.x) * R::FT + fr;
   const bool valid = t < T;
   const int nt0 = (blockIdx.y * 4 + wave) * BWT;
   const float c1 = scal[SC_C1], c2 = scal[SC_C2];
@@ -409,12 +419,13 @@ __global__ void stft_gather_kernel(G ga, int n, float* __restrict__ g) {
   if (i < n) g[i] = ga(i, n);
 }
 
-// g = (1 - alpha) g_point + alpha gather over the valid rows, 0 on pad rows (pscal: the point loss's scalars)
+// g = (1 - alpha) g_point + alpha gather over the valid rows, 0 on pad rows (pscal: the point loss's scalars);
+// rows [lo, rows) of the batch
 template <class G>
-__global__ void loss_mix_kernel(const float* __restrict__ out, const float* __restrict__ y, int n, int rows, G ga,
-                                const float* __restrict__ pscal, int loss_mode, float wp, float ws, float gfac,
+__global__ void loss_mix_kernel(const float* __restrict__ out, const float* __restrict__ y, int n, int lo, int rows,
+                                G ga, const float* __restrict__ pscal, int loss_mode, float wp, float ws, float gfac,
                                 float* __restrict__ g) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = lo + blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= rows) return;
   float v = 0.f;
   if (i < n) {
@@ -429,6 +440,22 @@ __global__ void loss_mix_kernel(const float* __restrict__ out, const float* __re
     if (ws != 0.f) v += ws * ga(i, n);
   }
   g[i] = v;
+}
+
+// The point loss's |err| (loss_mode 1) or err^2 per 256 samples of a signal whose `out` is already
+// written: head_loss_kernel's err and its block reduction (block_sum2_max keeps block_sum's tree), so
+// the partials are those of a one-batch step over the same out, bit for bit
+__global__ void point_partials_kernel(const float* __restrict__ out, const float* __restrict__ y, int n,
+                                      int loss_mode, float* __restrict__ part) {
+  __shared__ float scratch[4];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  float e2 = 0.f;
+  if (i < n) {
+    const float err = out[i] - y[i];
+    e2 = loss_mode == 1 ? fabsf(err) : err * err;
+  }
+  const float se = block_sum(e2, scratch);
+  if (threadIdx.x == 0) part[blockIdx.x] = se;
 }
 
 // sums of x and y per 256 samples
@@ -601,12 +628,15 @@ inline size_t up4(size_t v) { return (v + 3) / 4 * 4; }
 
 // what the host needs of a trait: the sizes, the table fill and the two launches
 struct ResInfo {
-  int hop, nb, nbp, kwp, ft, fgy;
+  int hop, nb, nbp, kwp, ft, fgy, nfft, win;
   size_t tab;
   void (*fill)(float* fwd);
-  hipError_t (*forward)(const float* x, int n, const float* basis, const SpecRes& q, bool target, hipStream_t s);
-  hipError_t (*backward)(const float* basis, const SpecRes& q, hipStream_t s);
-  int blocks(int64_t T) const { return (int)((T + ft - 1) / ft) * fgy; }   // forward blocks = partials per row
+  // b0, b1: the frame blocks [b0, b1) of the whole signal's that run (a window; the target side runs them all)
+  hipError_t (*forward)(const float* x, int n, const float* basis, const SpecRes& q, bool target, int b0, int b1,
+                        hipStream_t s);
+  hipError_t (*backward)(const float* basis, const SpecRes& q, int b0, int b1, hipStream_t s);
+  int fblocks(int64_t T) const { return (int)((T + ft - 1) / ft); }        // frame blocks of the whole signal
+  int blocks(int64_t T) const { return fblocks(T) * fgy; }                 // forward blocks = partials per row
 };
 
 template <class R>
@@ -628,30 +658,37 @@ void fill_tables(float* fwd) {
 }
 
 template <class R>
-hipError_t forward_r(const float* x, int n, const float* basis, const SpecRes& q, bool target, hipStream_t s) {
-  const dim3 grid((q.T + R::FT - 1) / R::FT, R::FGY);
+hipError_t forward_r(const float* x, int n, const float* basis, const SpecRes& q, bool target, int b0, int b1,
+                     hipStream_t s) {
+  const int gx = (q.T + R::FT - 1) / R::FT;
   if (target) {
+    const dim3 grid(gx, R::FGY);
     hipLaunchKernelGGL((stft_fwd_kernel<R, true>), grid, dim3(256), 0, s, x, n, q.T, basis, q.ymag, q.ylog, nullptr,
-                       nullptr, q.part, q.npart);
+                       nullptr, q.part, q.npart, 0, gx);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return sum_to(q.part + (size_t)PT_S1 * q.npart, (int)(grid.x * grid.y), q.scal + SC_SY, 0, s);
   }
-  hipLaunchKernelGGL((stft_fwd_kernel<R, false>), grid, dim3(256), 0, s, x, n, q.T, basis, q.re, q.im, q.ymag, q.ylog,
-                     q.part, q.npart);
+  if (b0 < 0 || b1 > gx || b0 > b1) return hipErrorInvalidValue;
+  if (b0 == b1) return hipSuccess;   // an empty window
+  hipLaunchKernelGGL((stft_fwd_kernel<R, false>), dim3(b1 - b0, R::FGY), dim3(256), 0, s, x, n, q.T, basis, q.re,
+                     q.im, q.ymag, q.ylog, q.part, q.npart, b0, gx);
   return hipGetLastError();
 }
 
 template <class R>
-hipError_t backward_r(const float* basis, const SpecRes& q, hipStream_t s) {
-  hipLaunchKernelGGL((stft_bwd_kernel<R>), dim3((q.T + R::FT - 1) / R::FT, R::BGY), dim3(256), 0, s, q.T,
-                     basis + R::TAB, q.re, q.im, q.ymag, q.ylog, q.scal, q.dF);
+hipError_t backward_r(const float* basis, const SpecRes& q, int b0, int b1, hipStream_t s) {
+  if (b0 < 0 || b1 > (q.T + R::FT - 1) / R::FT || b0 > b1) return hipErrorInvalidValue;
+  if (b0 == b1) return hipSuccess;
+  hipLaunchKernelGGL((stft_bwd_kernel<R>), dim3(b1 - b0, R::BGY), dim3(256), 0, s, q.T, basis + R::TAB, q.re, q.im,
+                     q.ymag, q.ylog, q.scal, q.dF, b0);
   return hipGetLastError();
 }
 
 template <class R>
 constexpr ResInfo info_of() {
-  return {R::HOP, R::NB, R::NBP, R::KWP, R::FT, R::FGY, R::TAB, fill_tables<R>, forward_r<R>, backward_r<R>};
+  return {R::HOP, R::NB, R::NBP, R::KWP, R::FT, R::FGY, R::NFFT, R::WIN, R::TAB, fill_tables<R>, forward_r<R>,
+          backward_r<R>};
 }
 // a loss's transforms, their tables one after the other
 const ResInfo kSfRes[1] = {info_of<SfR>()};
@@ -731,26 +768,81 @@ SpecWs spec_ws_map(SpecLoss k, float* ws, int n, int rows, int64_t* total) {
   return w;
 }
 
-hipError_t spec_forward(const float* x, int n, const float* basis, const SpecWs& w, bool target, hipStream_t s) {
+int spec_frame_blocks(SpecLoss k, int64_t n, int r) {
+  const int64_t T = spec_frames(k, n, r);
+  return T > 0 ? res_of(k)[r].fblocks(T) : 0;
+}
+
+int spec_grid_y(SpecLoss k, int r) { return r >= 0 && r < nres_of(k) ? res_of(k)[r].fgy : 0; }
+
+// The frame blocks of transform r that the samples [lo, hi) of an n-sample signal need and own.
+// Frame t covers the padded indices j with t hop <= j - pad < t hop + win.  compute: every block with
+// a frame that covers i + n_fft / 2 or one of i's two reflected images (gather_sample's) for an i in
+// [lo, hi) -- what the gather of dL/dx_i reads, hence what the forward and the backward of that range
+// must have run.  owned: the blocks whose first frame t0 has min(t0 hop, n - 1) in [lo, hi); that
+// sample is monotone in the block, so any partition of [0, n) partitions the blocks, and frame t0
+// covers its image (win / 2 taps in), so compute contains owned.  A block is 16 frames: a window starts
+// at a multiple of 16 frames and every staging map of the kernels holds unchanged.
+void spec_window(SpecLoss k, int r, int n, int lo, int hi, int compute[2], int owned[2]) {
+  const ResInfo& ri = res_of(k)[r];
+  const int64_t T = spec_frames(k, n, r), H = ri.nfft / 2, pad = (ri.nfft - ri.win) / 2;
+  const int nblk = ri.fblocks(T);
+  int64_t fmin = T, fmax = -1;   // covering frames
+  auto cover = [&](int64_t j0, int64_t j1) {   // the padded indices [j0, j1]
+    const int64_t a0 = j0 - pad < 0 ? 0 : j0 - pad, a1 = j1 - pad;
+    if (j0 > j1 || a1 < 0) return;
+    const int64_t tlo = a0 < ri.win ? 0 : (a0 - ri.win) / ri.hop + 1;
+    const int64_t thi = a1 / ri.hop > T - 1 ? T - 1 : a1 / ri.hop;
+    if (tlo > thi) return;
+    if (tlo < fmin) fmin = tlo;
+    if (thi > fmax) fmax = thi;
+  };
+  if (lo < hi) {
+    const int64_t last = hi - 1, N1 = n - 1;
+    cover(lo + H, last + H);
+    cover(H - (last < H ? last : H), H - (lo > 1 ? lo : 1));                              // i in 1 .. n_fft / 2
+    cover(2 * N1 - (last < N1 - 1 ? last : N1 - 1) + H, 2 * N1 - (lo > N1 - H ? lo : N1 - H) + H);  // n-1-H .. n-2
+  }
+  compute[0] = fmax < 0 ? 0 : (int)(fmin / ri.ft);
+  compute[1] = fmax < 0 ? 0 : (int)(fmax / ri.ft) + 1;
+  const int64_t bs = (int64_t)ri.ft * ri.hop;   // samples between two blocks' first frames
+  auto first_at = [&](int64_t x) {   // the first block whose min(t0 hop, n - 1) >= x
+    const int64_t b = (x + bs - 1) / bs;
+    return x > n - 1 || b > nblk ? nblk : (int)b;
+  };
+  owned[0] = first_at(lo);
+  owned[1] = first_at(hi);
+}
+
+// win: per transform the frame blocks [win[2 r], win[2 r + 1]) that run; null: all of them
+hipError_t spec_forward(const float* x, int n, const float* basis, const SpecWs& w, bool target, hipStream_t s,
+                        const int* win) {
   if (w.r[0].T < 1) return hipErrorInvalidValue;
   const ResInfo* ri = res_of((SpecLoss)w.loss);
   hipError_t e = hipSuccess;
   for (int r = 0; r < w.nres && e == hipSuccess; ++r) {
-    e = ri[r].forward(x, n, basis, w.r[r], target, s);
+    e = ri[r].forward(x, n, basis, w.r[r], target, win ? win[2 * r] : 0, win ? win[2 * r + 1] : ri[r].fblocks(w.r[r].T),
+                      s);
     basis += 2 * ri[r].tab;
   }
   return e;
 }
 
-hipError_t spec_backward(const float* basis, const SpecWs& w, hipStream_t s) {
+hipError_t spec_backward(const float* basis, const SpecWs& w, hipStream_t s, const int* win) {
   if (w.r[0].T < 1) return hipErrorInvalidValue;
   const ResInfo* ri = res_of((SpecLoss)w.loss);
   hipError_t e = hipSuccess;
   for (int r = 0; r < w.nres && e == hipSuccess; ++r) {
-    e = ri[r].backward(basis, w.r[r], s);
+    e = ri[r].backward(basis, w.r[r], win ? win[2 * r] : 0, win ? win[2 * r + 1] : ri[r].fblocks(w.r[r].T), s);
     basis += 2 * ri[r].tab;
   }
   return e;
+}
+
+hipError_t point_partials(const float* out, const float* y, int n, int loss_mode, const SpecWs& w, hipStream_t s) {
+  hipLaunchKernelGGL(point_partials_kernel, dim3((n + 255) / 256), dim3(256), 0, s, out, y, n, loss_mode,
+                     w.pt.part + (size_t)PT_SSE * w.pt.npart);
+  return hipGetLastError();
 }
 
 hipError_t snr_sums(const float* x, const float* y, int n, const SpecWs& w, hipStream_t s) {
@@ -791,14 +883,15 @@ hipError_t spec_gather(int n, const SpecWs& w, float* g, hipStream_t s) {
 }
 
 hipError_t loss_mix(const float* out, const float* y, int n, int rows, const SpecWs& w, int loss_mode, double alpha,
-                    float gfac, float* g, hipStream_t s) {
-  const dim3 grid((rows + 255) / 256), block(256);
+                    float gfac, float* g, hipStream_t s, int lo) {
+  if (lo >= rows) return hipSuccess;
+  const dim3 grid((rows - lo + 255) / 256), block(256);
   const float wp = (float)(1.0 - alpha), wsp = (float)alpha;
   if (w.loss == SPEC_MRSTFT)
-    hipLaunchKernelGGL(loss_mix_kernel<GatherMr>, grid, block, 0, s, out, y, n, rows, gather_mr(w), w.pt.scal,
+    hipLaunchKernelGGL(loss_mix_kernel<GatherMr>, grid, block, 0, s, out, y, n, lo, rows, gather_mr(w), w.pt.scal,
                        loss_mode, wp, wsp, gfac, g);
   else
-    hipLaunchKernelGGL(loss_mix_kernel<GatherSf>, grid, block, 0, s, out, y, n, rows, gather_sf(w), w.pt.scal,
+    hipLaunchKernelGGL(loss_mix_kernel<GatherSf>, grid, block, 0, s, out, y, n, lo, rows, gather_sf(w), w.pt.scal,
                        loss_mode, wp, wsp, gfac, g);
   return hipGetLastError();
 }

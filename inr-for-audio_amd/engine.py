@@ -511,7 +511,7 @@ class SirenEngine(FitEngine):
                  min_lr: float = 1e-6, factor: float = 0.8, patience: int = 200,
                  n_total: int | None = None, micro_batch: int = 1 << 20, hist_cap: int = 20000,
                  splits: int | None = None, device=None, loss_mode: str = "mse", encoding=None,
-                 alpha: float = 0.0, stft_loss: str = "stft"):
+                 alpha: float = 0.0, stft_loss: str = "stft", split_spectral: bool = False):
         """`encoding` (encoding.GaussianEncoding, run.py:141-144): `coords` stay the raw [N][1]
         coordinates and model.in_features must be 2 * encoded_size -- the first layer's kernel
         builds the encoded input itself (training and infer()).
@@ -523,7 +523,14 @@ class SirenEngine(FitEngine):
 
         `stft_loss` (run.py:127-128): 'stft' is the single 1024 / 256 transform, 'mrstft' the mean of the
         three of auraloss's MultiResolutionSTFTLoss() defaults (csrc/stft.hip), which needs more than
-        1024 samples when alpha > 0."""
+        1024 samples when alpha > 0.
+
+        `split_spectral`: the spectral step in phases -- every micro-batch of every rank runs
+        its forward into a signal-length `out_sig`, the loss runs once on the gathered signal (each rank
+        the frame blocks of its own samples), then every micro-batch runs its backward from its slice of
+        g = dLoss/dout.  Only then does such an engine take more than one micro-batch or rank; each rank
+        holds the whole target and a whole-signal loss workspace, so the caller passes the whole signal
+        (no n_total)."""
         if loss_mode not in LOSS_MODES:
             raise NotImplementedError(f"loss_mode={loss_mode!r}: the HIP path has {sorted(LOSS_MODES)}")
         if stft_loss not in STFT_LOSSES:
@@ -533,16 +540,19 @@ class SirenEngine(FitEngine):
         if not 0.0 <= self.alpha <= 1.0:
             raise ValueError(f"alpha={alpha!r} must be in [0, 1] (run.py:161-169 mixes (1 - alpha) and alpha)")
         self.spectral = self.alpha != 0.0 or loss_mode == "snr"
+        self.split_spectral = split = self.spectral and bool(split_spectral)
         if self.spectral:
             n_sig = int(target.numel())
-            if _dist() is not None:
+            if _dist() is not None and not split:
                 raise NotImplementedError("the STFT / SNR losses need the whole signal on one rank (frames and the "
-                                          "sums cross shard boundaries): no process group of more than one rank")
-            if n_total is not None and int(n_total) != n_sig:
+                                          "sums cross shard boundaries): no process group of more than one rank "
+                                          "(split_spectral=True gathers the signal)")
+            if n_total is not None and (int(n_total) != n_sig or _dist() is not None):
                 raise NotImplementedError("the STFT / SNR losses need the whole signal (n_total == len(target))")
-            if n_sig > round_up(int(micro_batch), 2 * ROW_TILE):
+            if n_sig > round_up(int(micro_batch), 2 * ROW_TILE) and not split:
                 raise NotImplementedError(f"the STFT / SNR losses need the whole signal in one micro-batch: "
-                                          f"{n_sig} samples > micro_batch={micro_batch}")
+                                          f"{n_sig} samples > micro_batch={micro_batch} (split_spectral=True "
+                                          f"runs the loss between the micro-batches' forwards and backwards)")
             if self.alpha != 0.0 and n_sig <= 512:
                 raise ValueError(f"the STFT loss needs more than 512 samples (reflect padding of a 1024-point "
                                  f"frame is undefined for {n_sig}; torch.stft refuses it too)")
@@ -582,6 +592,12 @@ class SirenEngine(FitEngine):
         self._setup_opt(lr, min_lr, factor, patience, hist_cap)
 
         # data: this rank's contiguous shard, padded per micro-batch
+        if split:   # the loss sees the whole target on every rank; [_sig_lo, _sig_hi) are this rank's samples
+            self.target_sig = target.reshape(-1).to(dev, torch.float32).contiguous()
+            n_sig = self.target_sig.numel()
+            self._sig_lo, self._sig_hi = 0, n_sig
+            if d is not None:
+                self._sig_lo, self._sig_hi = shard_range(n_sig, d.get_rank(), d.get_world_size())
         coords, target = self._shard(coords, target, spec.in_dim, n_total)
         n, n_global = self.n_local, self.n_total
         # rows padded to 256 (pad rows carry g = 0): the 256x256 GEMM tiles need M % 256 == 0,
@@ -607,7 +623,8 @@ class SirenEngine(FitEngine):
             lo = k * mb
             c = self.coords[lo:lo + mb]
             t = self.target[lo:lo + mb]
-            b = self.ws.batch(c, t, min(mb, n - lo), n_global, zero_grads=(k == 0),
+            # the split step clears the gradients itself, before the loss lands in their tail slot
+            b = self.ws.batch(c, t, min(mb, n - lo), n_global, zero_grads=(k == 0 and not split),
                               guard=self.guard, loss_mode=LOSS_MODES[loss_mode])
             b.gmax_part = ptr(self._gmax[k])
             self.batches.append(b)
@@ -622,8 +639,10 @@ class SirenEngine(FitEngine):
         """The STFT / SNR loss workspace of the (single) batch, the transform's tables and -- computed
         once, they never change -- the target's magnitudes, their logs and Sy."""
         lib, b, n, dev = self.lib, self.batches[0], self.n_local, self.device
-        assert self.n_micro == 1 and n == self.n_total
         struct, (f_alpha, f_basis, f_ws), prefix, _ = _SPECTRAL[self.stft_loss]   # run.py:127-128
+        if self.split_spectral:
+            return self._setup_split(prefix)
+        assert self.n_micro == 1 and n == self.n_total
         self.stft_ws = torch.zeros(int(getattr(lib, prefix + "_workspace_floats")(n, self.rows)),
                                    dtype=torch.float32, device=dev)
         self.spectral_struct = sp = struct()
@@ -634,6 +653,88 @@ class SirenEngine(FitEngine):
             setattr(sp, f_basis, ptr(self.stft_basis))
             check(getattr(lib, prefix + "_forward")(ptr(self.target), n, self.rows, ptr(self.stft_basis),
                                                     ptr(self.stft_ws), 1, self._stream()), prefix + "_forward")
+
+    def _setup_split(self, prefix):
+        """The split step's buffers: out_sig / g_sig [N], the whole-signal loss workspace with
+        the target's side set once, this rank's windows of frame blocks and, in a process group, where
+        the transforms' partials live and which of them this rank owns."""
+        lib, dev, N, d = self.lib, self.device, self.n_total, _dist()
+        lo, hi = self._sig_lo, self._sig_hi
+        fn = lambda name: getattr(lib, f"{prefix}_{name}")  # noqa: E731
+        mr = self.stft_loss == "mrstft"
+        rr = lambda r: (r,) if mr else ()   # mrstft's calls name the resolution  # noqa: E731
+        self.out_sig = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.g_sig = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.stft_ws = torch.zeros(int(fn("workspace_floats")(N, N)), dtype=torch.float32, device=dev)
+        self._sig_win = (ctypes.c_int32 * 6)()
+        self._parts = []   # per transform (ws offset, npart, frame blocks, grid.y, owned lo, owned hi, pack offset)
+        # the finished loss: the gradients' tail slot on rank 0 alone, so that the SUM all-reduce leaves it once
+        self._loss_scratch = torch.zeros(4, dtype=torch.float32, device=dev)
+        own = d is None or d.get_rank() == 0
+        self._loss_ptr = self.grads.data_ptr() + 4 * self.layout.sse_offset if own else ptr(self._loss_scratch)
+        if self.alpha == 0.0:
+            return
+        self.stft_basis = _basis(self.stft_loss, dev)
+        check(fn("forward")(ptr(self.target_sig), N, N, ptr(self.stft_basis), ptr(self.stft_ws), 1, self._stream()),
+              prefix + "_forward")
+        pack = 0
+        for r in range(3 if mr else 1):
+            blocks = (ctypes.c_int32 * 4)()
+            check(fn("window")(N, *rr(r), lo, hi, blocks), prefix + "_window")
+            self._sig_win[2 * r], self._sig_win[2 * r + 1] = blocks[0], blocks[1]
+            off, npart, nblk, gy = (int(fn("signal_parts")(N, N, *rr(r), k)) for k in range(4))
+            self._parts.append((off, npart, nblk, gy, blocks[2], blocks[3], pack))
+            pack += 2 * npart
+        self._part_pack = torch.zeros(pack, dtype=torch.float32, device=dev) if d is not None else None
+
+    def _reduce_partials(self, d):
+        """Every rank's complete partial arrays: the ones of the blocks this rank owns, zeros elsewhere,
+        summed over the ranks (x + 0 = x: the arrays are the one-rank launch's, bit for bit)."""
+        pk, ws = self._part_pack, self.stft_ws
+        pk.zero_()
+        for off, npart, nblk, gy, olo, ohi, po in self._parts:
+            for row in range(2):
+                for y in range(gy):
+                    a = row * npart + y * nblk
+                    pk[po + a + olo:po + a + ohi] = ws[off + a + olo:off + a + ohi]
+        d.all_reduce(pk)
+        for off, npart, _, _, _, _, po in self._parts:
+            ws[off:off + 2 * npart] = pk[po:po + 2 * npart]
+
+    def _launch_grads_split(self):
+        """run.py:160-169 across micro-batches and ranks: forwards into out_sig, the loss on the
+        gathered signal, backwards from the slices of g_sig.  No host synchronisation on one rank."""
+        lib, s, N, mb = self.lib, self._stream(), self.n_total, self.rows
+        net, gr = ctypes.byref(self.net), ctypes.byref(self.grad_struct)
+        prefix = _SPECTRAL[self.stft_loss][2]
+        mode, alpha = self.batches[0].loss_mode, self.alpha
+        d = _dist()
+        x, y, basis, ws = ptr(self.out_sig), ptr(self.target_sig), ptr(self.stft_basis), ptr(self.stft_ws)
+        self.grads.zero_()
+        if d is not None:
+            self.out_sig.zero_()   # zero outside the own shard: the SUM all-reduce is the gather
+        for k, b in enumerate(self.batches):
+            check(lib.siren_forward(net, ctypes.byref(b), s), "siren_forward")
+            lo = self._sig_lo + k * mb
+            self.out_sig[lo:lo + b.n_valid] = self.ws.out[:b.n_valid]
+        if d is not None:
+            d.all_reduce(self.out_sig)
+        check(getattr(lib, prefix + "_signal_forward")(x, y, N, N, mode, alpha, basis, ws, self._sig_win, s),
+              prefix + "_signal_forward")
+        if d is not None and alpha != 0.0:
+            self._reduce_partials(d)
+        check(getattr(lib, prefix + "_signal_finish")(N, N, mode, alpha, ws, self._loss_ptr, s),
+              prefix + "_signal_finish")
+        check(getattr(lib, prefix + "_signal_backward")(x, y, N, N, mode, alpha, basis, ws, self._sig_win,
+                                                        self._sig_lo, self._sig_hi, ptr(self.g_sig), s),
+              prefix + "_signal_backward")
+        for k, b in enumerate(self.batches):
+            if self.n_micro > 1:   # the workspace holds the last micro-batch's activations
+                check(lib.siren_forward(net, ctypes.byref(b), s), "siren_forward")
+            lo = self._sig_lo + k * mb
+            self.ws.g[:b.n_valid] = self.g_sig[lo:lo + b.n_valid]
+            self.ws.g[b.n_valid:].zero_()
+            check(lib.siren_backward(net, gr, ctypes.byref(b), s), "siren_backward")
 
     def _setup_buckets(self):
         """One bucket per layer (contiguous in the flat layout): the head (+ the SSE tail slot),
@@ -663,6 +764,8 @@ class SirenEngine(FitEngine):
         cast_shadows(self.spec, self.W, self.Wh, self.WTh, self._stream())
 
     def _launch_grads(self):
+        if self.split_spectral:
+            return self._launch_grads_split()
         s = self._stream()
         for b in self.batches:
             if self.spectral:   # run.py:127-128, :160-169: the STFT / SNR step (one batch: the whole signal)

@@ -83,7 +83,7 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
           min_learning_rate=1e-6, alpha=0.0, prev_ckpt_path=None, visualization=False, *,
           filename=None, data_dir="data", seed=None, micro_batch=1 << 20, use_graph=True,
           device=None, verbose=False, multichannel=False, patience=200, restated_losses=False,
-          stft_loss="stft"):
+          stft_loss="stft", split_spectral=False):
     """Fit one clip; returns the checkpoint path (run.py:400).  Extra keyword-only knobs:
     ``filename`` (default ``{data_dir}/{inst}.wav`` as run.py:33), ``seed`` (torch.manual_seed
     before model construction), ``micro_batch`` (rows per fused micro-batch), ``use_graph``
@@ -96,7 +96,9 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     the loss is negative, so the dB history is NaN as in the reference, run.py:180),
     ``stft_loss`` (with ``restated_losses``: 'stft', the single STFTLoss() of run.py:128, or 'mrstft',
     the MultiResolutionSTFTLoss() of run.py:127 -- more than 1024 samples; recorded in parameters.json
-    only when it is not 'stft')."""
+    only when it is not 'stft'), ``split_spectral`` (with ``restated_losses``: SirenEngine's split step,
+    which fits with these losses across micro-batches and data-parallel ranks -- a clip longer than
+    ``micro_batch``, or more than one GPU; recorded in parameters.json only when true)."""
     if method not in ("wave", "mdct"):
         raise ValueError("specify the correct fitting method as wave or mdct (run.py:77-78)")
     if method == "mdct" and bwe:
@@ -186,6 +188,10 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         if arch == "kan":
             raise NotImplementedError("stft_loss='mrstft' fits the MLP (arch='kan' is fitted with MSELoss only)")
         kw["stft_loss"] = stft_loss
+    if split_spectral:
+        if not restated_losses or arch == "kan":
+            raise NotImplementedError("split_spectral is the MLP's restated_losses step across micro-batches and ranks")
+        kw["split_spectral"] = True
     engine = Engine(model, model_input, ground_truth, lr=learning_rate, min_lr=min_learning_rate,
                     patience=patience, micro_batch=micro_batch, hist_cap=total_steps, device=dev, **kw)
     if ckpt is not None:
@@ -279,6 +285,8 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         }
         if stft_loss != "stft":
             params["stft_loss"] = stft_loss
+        if split_spectral:
+            params["split_spectral"] = True
         save_parameters(experiment_folder, **params)
         if verbose:
             print(json.dumps({"SNR": snr_final, "SNR_target": snr_target, "time_min": total_time}))
