@@ -227,6 +227,28 @@ int siren_apply_update(const siren_net* net, float* params, const float* grads_f
 /* (siren_apply_update: `sse` is siren_grads.sse after any all-reduce -- sse[1] != 0 marks the guard
  * stalled, so every rank skips a step any rank's fused hand-off voided) */
 
+/* ---- the loss-landscape plane ---------------------------------------------------------
+ * run.py:192-198 (visualization=True): the MSE at steps x steps weight settings
+ * theta_ij = theta + a_i d1 + b_j d2 around the fitted weights.
+ * siren_plane_point: run.py:192-198  one grid point's weights, one launch.  `theta`, `d1`, `d2` and
+ *   `out` are flat fp32 vectors of n_flat floats (n_flat % 4 == 0, 16-B aligned, out != theta) in one
+ *   layout; out = fma(b, d2, fma(a, d1, theta)) element by element (fp32, two roundings).  W_out
+ *   [n_inner] are the square hidden weights' positions inside `out` (as siren_apply_update's W_fp32
+ *   are inside params; float offsets % 4 == 0, no overlap); Wh / WTh receive their fp16 shadows, bit
+ *   for bit siren_cast_weight of the fp32 values written to `out`.  Directions are zero in pad entries
+ *   and alignment gaps, which therefore keep theta's value.
+ * siren_plane_eval:  run.py:192-198  (the metric is run.py:195's MSELoss whatever the fit's loss_mode)
+ *   siren_forward's launches on `batch`, the squared error of batch->out against batch->target over
+ *   the first n_valid rows, and sse_slot[0] += that sum (fp64, the 256-row partials added in a fixed
+ *   order; the caller zeroes the slot and divides by N).  Of the batch it writes the activations, out,
+ *   g, head_part, sse_part and gsum_part -- nothing a later training step reads before writing it: not
+ *   gmax_part, not siren_grads, not the guard. */
+int siren_plane_point(const float* theta, const float* d1, const float* d2, float a, float b, float* out,
+                      int64_t n_flat, int32_t hidden, int32_t n_inner,
+                      float* const* W_out /* [n_inner] views into out */,
+                      uint16_t* const* Wh, uint16_t* const* WTh, void* stream);
+int siren_plane_eval(const siren_net* net, siren_batch* batch, double* sse_slot, void* stream);
+
 /* ---- individual kernels (parity tests call these one by one) ------------------------ */
 /* utils.py:99-109 get_coord: torch.linspace(-1,1,n_total) at [offset, offset+rows) */
 int siren_coords_fill(float* t, int64_t rows, int64_t offset, int64_t n_total, void* stream);

@@ -142,6 +142,10 @@ _SIGS = {
     "siren_apply_update": (ctypes.c_int, [ctypes.POINTER(SirenNet), _p, _p, _p, _p, _i64,
                                           ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_p),
                                           _p, _p, ctypes.c_double, _p, _p, _i64, _p, _p]),
+    # the loss-landscape plane (run.py:192-198)
+    "siren_plane_point": (ctypes.c_int, [_p, _p, _p, ctypes.c_float, ctypes.c_float, _p, _i64, _i32, _i32,
+                                         ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_p), _p]),
+    "siren_plane_eval": (ctypes.c_int, [ctypes.POINTER(SirenNet), ctypes.POINTER(SirenBatch), _p, _p]),
     "siren_coords_fill": (ctypes.c_int, [_p, _i64, _i64, _i64, _p]),
     "siren_coords_fill_grid": (ctypes.c_int, [_p, _i64, _i64, _i64, _i32, _p]),
     "siren_first_fwd": (ctypes.c_int, [_p, _i32, _p, _p, ctypes.c_float, _i32, _i32, _p, _p, _p]),

@@ -600,6 +600,61 @@ int siren_apply_update(const siren_net* net, float* params, const float* grads_f
   return SIREN_OK;
 }
 
+// ---- the loss-landscape plane (run.py:192-198) ------------------------------------------
+
+int siren_plane_point(const float* theta, const float* d1, const float* d2, float a, float b, float* out,
+                      int64_t n_flat, int32_t hidden, int32_t n_inner, float* const* W_out, uint16_t* const* Wh,
+                      uint16_t* const* WTh, void* stream) {
+  if (!theta || !d1 || !d2 || !out || !W_out || !Wh || !WTh) return SIREN_ERR_NULL;
+  if (!hidden_ok(hidden) || n_flat < 4 || n_flat % 4) return SIREN_ERR_SHAPE;
+  if (n_inner < 1 || n_inner > SIREN_MAX_INNER || out == theta) return SIREN_ERR_CONFIG;
+  // 16-B accesses outside the hidden weights
+  if (((uintptr_t)theta | (uintptr_t)d1 | (uintptr_t)d2 | (uintptr_t)out) & 15) return SIREN_ERR_SHAPE;
+  const int64_t hh = (int64_t)hidden * hidden;
+  PlaneSet ps = {};
+  ps.n = n_inner;
+  int order[SIREN_MAX_INNER];
+  for (int i = 0; i < n_inner; ++i) {
+    if (!W_out[i] || !Wh[i] || !WTh[i]) return SIREN_ERR_NULL;
+    const int64_t off = W_out[i] - out;
+    if (off < 0 || off % 4 || off + hh > n_flat) return SIREN_ERR_SHAPE;
+    ps.w_off[i] = off;
+    ps.Wb[i] = B(Wh[i]);
+    ps.WTb[i] = B(WTh[i]);
+    int k = i;  // the layers by offset (insertion sort): the rest of the vector is the gaps between them
+    for (; k > 0 && ps.w_off[order[k - 1]] > off; --k) order[k] = order[k - 1];
+    order[k] = i;
+  }
+  int64_t at = 0;
+  for (int k = 0; k <= n_inner; ++k) {
+    const int64_t lo = k < n_inner ? ps.w_off[order[k]] : n_flat;
+    if (lo < at) return SIREN_ERR_SHAPE;  // two hidden weights overlap
+    if (lo > at) {
+      ps.lo[ps.nrest] = at / 4;
+      ps.hi[ps.nrest] = lo / 4;
+      ++ps.nrest;
+    }
+    at = lo + hh;
+  }
+  return (int)plane_point(theta, d1, d2, a, b, out, ps, hidden, S(stream));
+}
+
+int siren_plane_eval(const siren_net* net, siren_batch* b, double* sse_slot, void* stream) {
+  int st = check_net(net);
+  if (st) return st;
+  if ((st = check_batch(net, b, false))) return st;
+  if (!sse_slot || (b->n_valid > 0 && !b->target)) return SIREN_ERR_NULL;
+  hipStream_t s = S(stream);
+  // siren_forward's unfused launches, then MSE (run.py:195) over the valid rows: out, g (gfac 0), sse_part and
+  // gsum_part are rewritten by every training step before it reads them; gmax_part (a fused Snake last layer's
+  // scale source), the gradients and the guard are not touched
+  SIREN_TRY(run_forward(net, b, s));
+  SIREN_TRY(head_loss(b->head_part, head_parts(b->rows, net->hidden), b->rows, net->b_head, b->target, b->n_valid,
+                      0.f, b->out, b->g, b->sse_part, b->gsum_part, nullptr, s, net->head_omega, 0));
+  SIREN_TRY(plane_loss(b->sse_part, bands(b->rows), sse_slot, s));
+  return SIREN_OK;
+}
+
 // ---- individual kernels ----------------------------------------------------------------
 
 int siren_coords_fill(float* t, int64_t rows, int64_t offset, int64_t n_total, void* stream) {

@@ -679,18 +679,11 @@ hipError_t plateau_step(OptState* st, const float* sse, double n_total, float* l
 // ---------------------------------------------------------------------------------
 // h16 shadows of a hidden weight W[o][k] (fp32 master): Wb = W, WTb = W^T, through a
 // 64x64 LDS transpose so both stores are coalesced.
+// (the tile body is cast_tile64, siren_common.h: plane.hip's plane_point builds its shadows with it too)
 __global__ void cast_weight_kernel(const float* __restrict__ W, int H_out, int H_in,
                                    h16* __restrict__ Wb, h16* __restrict__ WTb) {
   __shared__ float tile[64][65];
-  const int o0 = blockIdx.y * 64, k0 = blockIdx.x * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;  // 256 threads: 64 x 4
-  for (int r = ty; r < 64; r += 4) {
-    const float w = W[(size_t)(o0 + r) * H_in + k0 + tx];
-    tile[r][tx] = w;
-    Wb[(size_t)(o0 + r) * H_in + k0 + tx] = (h16)w;
-  }
-  __syncthreads();
-  for (int r = ty; r < 64; r += 4) WTb[(size_t)(k0 + r) * H_out + o0 + tx] = (h16)tile[tx][r];
+  cast_tile64([W](size_t i) { return W[i]; }, H_out, H_in, blockIdx.y * 64, blockIdx.x * 64, Wb, WTb, tile);
 }
 
 hipError_t cast_weight(const float* W, int H_out, int H_in, h16* Wb, h16* WTb, hipStream_t s) {
@@ -707,15 +700,7 @@ __global__ void cast_weights_kernel(CastSet cs, int H) {
   const float* __restrict__ W = cs.W[l];
   h16* __restrict__ Wb = cs.Wb[l];
   h16* __restrict__ WTb = cs.WTb[l];
-  const int o0 = blockIdx.y * 64, k0 = blockIdx.x * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  for (int r = ty; r < 64; r += 4) {
-    const float w = W[(size_t)(o0 + r) * H + k0 + tx];
-    tile[r][tx] = w;
-    Wb[(size_t)(o0 + r) * H + k0 + tx] = (h16)w;
-  }
-  __syncthreads();
-  for (int r = ty; r < 64; r += 4) WTb[(size_t)(k0 + r) * H + o0 + tx] = (h16)tile[tx][r];
+  cast_tile64([W](size_t i) { return W[i]; }, H, H, blockIdx.y * 64, blockIdx.x * 64, Wb, WTb, tile);
 }
 
 hipError_t cast_weights(const CastSet& cs, int H, hipStream_t s) {

@@ -314,4 +314,24 @@ __device__ __forceinline__ float block_max(float v, float* scratch) {
   return m;
 }
 
+// The h16 shadows Wb = W and WTb = W^T of one 64x64 tile (rows o0.., columns k0..) of a row-major
+// [H_out][H_in] fp32 weight, through an LDS transpose so both stores are coalesced.  256 threads
+// (64 x 4); `load(i)` gives the fp32 value of flat element i = o * H_in + k, each element asked for
+// once (cast_weight reads it; plane_point forms and stores it), so every caller's shadows are the
+// same conversion of the same fp32 value.  tile: the block's float [64][65] (65: the transposed
+// read tile[tx][r] walks a column, which the odd pitch spreads over the banks).
+template <class Load>
+__device__ __forceinline__ void cast_tile64(Load load, int H_out, int H_in, int o0, int k0, h16* __restrict__ Wb,
+                                            h16* __restrict__ WTb, float (&tile)[64][65]) {
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  for (int r = ty; r < 64; r += 4) {
+    const size_t i = (size_t)(o0 + r) * H_in + k0 + tx;
+    const float w = load(i);
+    tile[r][tx] = w;
+    Wb[i] = (h16)w;
+  }
+  __syncthreads();
+  for (int r = ty; r < 64; r += 4) WTb[(size_t)(k0 + r) * H_out + o0 + tx] = (h16)tile[tx][r];
+}
+
 }  // namespace siren

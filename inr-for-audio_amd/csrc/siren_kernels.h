@@ -335,6 +335,22 @@ struct CastSet {
   int n;
 };
 hipError_t cast_weights(const CastSet& cs, int H, hipStream_t s);
+
+// The loss-landscape plane (plane.hip; run.py:192-198): one grid point's parameters and shadows.
+// A flat fp32 parameter vector of n4 float4 holds n square H x H hidden weights at float offsets
+// w_off[l]; [lo[r], hi[r]) (float4 units, nrest of them) are the pieces of the vector outside them
+struct PlaneSet {
+  int64_t w_off[kMaxInner];
+  h16* Wb[kMaxInner];
+  h16* WTb[kMaxInner];
+  int64_t lo[kMaxInner + 1], hi[kMaxInner + 1];
+  int n, nrest;
+};
+// out = fma(b, d2, fma(a, d1, theta)) over the whole vector; Wb / WTb = cast_weight of out's hidden weights
+hipError_t plane_point(const float* theta, const float* d1, const float* d2, float a, float b, float* out,
+                       const PlaneSet& ps, int H, hipStream_t s);
+// slot[0] += sum of sse_part[0 .. nparts) in fp64, in a fixed order
+hipError_t plane_loss(const float* sse_part, int nparts, double* slot, hipStream_t s);
 hipError_t sum_to(const float* x, int n, float* out, int accumulate, hipStream_t s);
 // sum_to(x0 -> out0) and sum_to(x1 -> out1) in one launch; flag_src non-null: also
 // flag_dst[0] (+)= (flag_src[0] != 0)

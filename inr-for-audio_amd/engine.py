@@ -813,6 +813,101 @@ class SirenEngine(FitEngine):
         return forward_net(self.spec, self.net, coords.reshape(-1, self.spec.in_dim), self.device,
                            chunk, shadows_ready=True, ws=ws)
 
+    # ------------------------------------------------------------------ loss-landscape plane
+    def _plane_scratch(self):
+        """The scratch network of the plane (run.py:192-198; built on first use): a flat parameter
+        vector in the live one's layout, Wh / WTh shadows and a siren_net whose pointers view those.
+        The plane's launches write only these and the workspace."""
+        sc = getattr(self, "_plane", None)
+        if sc is not None:
+            return sc
+        spec, lay, dev, ix = self.spec, self.layout, self.device, self.ix
+        L, H = spec.n_inner, spec.hidden
+        theta = torch.zeros(lay.flat_len, dtype=torch.float32, device=dev)
+        pv = lambda i: lay.view(theta, i)  # noqa: E731
+        Wh = [torch.empty(H, H, dtype=STORE16, device=dev) for _ in range(L)]
+        WTh = [torch.empty(H, H, dtype=STORE16, device=dev) for _ in range(L)]
+        net = make_net(spec, pv(ix["W0"]), pv(ix["b0"]), [pv(k) for k in ix["b"]], Wh, WTh, pv(ix["wh"]),
+                       pv(ix["bh"]), [None if k is None else pv(k) for k in ix["a"]],
+                       None if ix["a0"] is None else pv(ix["a0"]), rff_B=self.rff_B)
+        arr = lambda ts: (ctypes.c_void_p * L)(*[ptr(t) for t in ts])  # noqa: E731
+        self._plane = sc = {"theta": theta, "Wh": Wh, "WTh": WTh, "net": net,
+                            "Wp": arr([pv(k) for k in ix["W"]]), "Whp": arr(Wh), "WThp": arr(WTh)}
+        return sc
+
+    def _plane_upload(self, d):
+        """A direction (one tensor per parameter, true shapes) as a flat padded device vector: zero in
+        pad entries and alignment gaps.  Rank 0's in a process group, as rff_B is."""
+        lay = self.layout
+        if len(d) != len(lay.names):
+            raise ValueError(f"a direction has one tensor per parameter ({len(lay.names)}), got {len(d)}")
+        flat = torch.zeros(lay.flat_len, dtype=torch.float32, device=self.device)
+        for i, x in enumerate(d):
+            if tuple(x.shape) != lay.true_shapes[i]:
+                raise ValueError(f"direction of {lay.names[i]}: shape {tuple(x.shape)} != {lay.true_shapes[i]}")
+            lay.true_view(flat, i).copy_(x.detach().to(self.device, torch.float32))
+        dist = _dist()
+        if dist is not None:
+            dist.broadcast(flat, src=0)
+        return flat
+
+    def _plane_point(self, sc, D1, D2, a: float, b: float, s):
+        check(self.lib.siren_plane_point(ptr(self.params), ptr(D1), ptr(D2), a, b, ptr(sc["theta"]),
+                                         self.layout.n_params, self.spec.hidden, self.spec.n_inner, sc["Wp"],
+                                         sc["Whp"], sc["WThp"], s), "siren_plane_point")
+
+    @torch.no_grad()
+    def loss_plane(self, d1, d2, steps: int = 30) -> torch.Tensor:
+        """The loss-landscape plane of run.py:192-198 on the training data: plane[i][j] = the MSE (whatever
+        loss the fit used, run.py:195) of theta_ij = fma(b_j, d2, fma(a_i, d1, theta)), a_i = i - steps / 2,
+        b_j = j - steps / 2.  `d1`, `d2`: one grid step each (landscape.plane_directions), one tensor per
+        parameter in true shapes.  Returns [steps][steps] fp64 on the host.
+
+        Per cell one siren_plane_point launch builds the scratch network's weights and shadows and
+        siren_plane_eval runs every micro-batch in the training workspace (as infer() does) into the
+        cell's fp64 slot; the live parameters, shadows, Adam state, history and guard are never written.
+        All on the current stream with no host synchronisation until the one copy at the end; in a
+        process group each rank sums its shard and one SUM all-reduce of the slots follows.  An engine
+        that replays a captured step captures it again afterwards (_recapture)."""
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError(f"steps={steps!r} must be at least 1")
+        sc = self._plane_scratch()
+        D1, D2 = self._plane_upload(d1), self._plane_upload(d2)
+        sse = torch.zeros(steps * steps, dtype=torch.float64, device=self.device)
+        s, net = self._stream(), ctypes.byref(sc["net"])
+        for i in range(steps):
+            for j in range(steps):
+                self._plane_point(sc, D1, D2, i - steps / 2, j - steps / 2, s)
+                slot = sse.data_ptr() + 8 * (i * steps + j)
+                for b in self.batches:
+                    check(self.lib.siren_plane_eval(net, ctypes.byref(b), slot, s), "siren_plane_eval")
+        dist = _dist()
+        if dist is not None:
+            dist.all_reduce(sse)
+        plane = (sse / float(self.n_total)).cpu().reshape(steps, steps)
+        if self.graph is not None:
+            self._recapture()
+        return plane
+
+    def _recapture(self):
+        """Capture the step again after eager launches ran between two replays of it.  Measured:
+        the first replay of the old graph after a plane's launches left a stray word in the gradients' stall
+        slot, which voids the step; a graph captured after them replays as the first one did.  Capturing
+        runs nothing: parameters, optimizer state, history and guard stay as they are."""
+        self.graph = None
+        self.capture_graph()
+
+    @torch.no_grad()
+    def plane_state_dict(self, d1, d2, steps: int, i: int, j: int) -> dict:
+        """theta_ij of loss_plane(d1, d2, steps) as {parameter name: fp32 host tensor in its true shape},
+        read back from the scratch vector siren_plane_point wrote."""
+        sc = self._plane_scratch()
+        D1, D2 = self._plane_upload(d1), self._plane_upload(d2)
+        self._plane_point(sc, D1, D2, i - steps / 2, j - steps / 2, self._stream())
+        lay = self.layout
+        return {name: lay.true_view(sc["theta"], k).cpu().clone() for k, name in enumerate(lay.names)}
+
 
 def forward_net(spec: NetSpec, net: SirenNet, coords: torch.Tensor, device, chunk: int,
                 shadows_ready: bool = True, ws: Workspace | None = None) -> torch.Tensor:

@@ -1,7 +1,11 @@
 """``train()`` with the reference's keyword API (run.py:30-400) on the HIP engine.
 
 Differences from the reference are limited to what the hot-path scope excludes: no plots
-(matplotlib figures), no loss-landscape.  loss_mode 'mse' and 'mae' (L1Loss, run.py:161-163) at
+(matplotlib figures) other than the loss landscape's.  ``visualization=True`` (run.py:192-208) evaluates
+the loss-landscape plane after the fit on the device (engine.SirenEngine.loss_plane; the directions are
+landscape.plane_directions, restated from the published filter-normalised definition because
+loss_landscapes is not a dependency) and writes landscape.npy and, with matplotlib, landscape.png.
+loss_mode 'mse' and 'mae' (L1Loss, run.py:161-163) at
 alpha=0 are fused on device (at alpha=0 the reference's STFT term contributes exactly zero, SURVEY
 §8 a8).  The reference's other loss options -- ``alpha > 0`` (auraloss.freq.STFTLoss, run.py:128,
 :160) and ``loss_mode='snr'`` (auraloss.time.SNRLoss, run.py:126, :165) -- are refused unless
@@ -123,8 +127,9 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         # the reference's own code cannot run these: b is [num_freq][1] against 2-D coordinates
         # (run.py:142-143), and KAN is built with input width 1 (run.py:93)
         raise NotImplementedError("num_freq encodes the 1-D waveform coordinate of the MLP (run.py:141-144)")
-    if visualization:
-        raise NotImplementedError("loss-landscape visualization is out of scope")
+    if visualization and arch == "kan":
+        raise NotImplementedError("visualization=True (the loss-landscape plane, run.py:192-208) runs on the MLP's "
+                                  "kernels: arch='kan' has no plane")
 
     filename = filename or f"{data_dir}/{inst}.wav"
     rank0 = _rank0()
@@ -216,6 +221,19 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     end_time = time.time()
     total_time = (end_time - start_time) / 60
 
+    # run.py:192-208: the loss-landscape plane around the fitted weights, after the timed fit.  The
+    # directions are drawn on rank 0 (loss_plane broadcasts them) from the run's seed when it has one
+    landscape_time = None
+    if visualization:
+        from .landscape import plane_directions, save_plane
+        gen = None if seed is None else torch.Generator().manual_seed(seed)
+        t0 = time.time()
+        d1, d2 = plane_directions([p for _, p in model.named_parameters()], distance=2.0, steps=30, generator=gen)
+        plane = engine.loss_plane(d1, d2, steps=30)   # synchronises: the plane comes back to the host
+        landscape_time = time.time() - t0
+        if rank0:
+            save_plane(plane.numpy(), experiment_folder)
+
     raw_losses, raw_lrs = engine.history()
     with np.errstate(invalid="ignore"):  # 'snr': a negative loss gives NaN, as in the reference
         losses = 10 * np.log10(raw_losses.astype(np.float64) + 1e-10)   # run.py:180
@@ -287,6 +305,8 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
             params["stft_loss"] = stft_loss
         if split_spectral:
             params["split_spectral"] = True
+        if visualization:
+            params["landscape_time_s"] = landscape_time
         save_parameters(experiment_folder, **params)
         if verbose:
             print(json.dumps({"SNR": snr_final, "SNR_target": snr_target, "time_min": total_time}))
