@@ -1285,8 +1285,6 @@ int siren_profile_read(int32_t kind, double* total_ms, int64_t* count) {
 // ---- KAN variant (kan.py, run.py:92-93) -----------------------------------
 namespace {
 
-constexpr int KAN_K1 = 9;  // A-columns per input feature: SiLU + 8 B-spline bases
-
 int check_kan(const siren_kan_net* n) {
   if (!n) return SIREN_ERR_NULL;
   if (n->n_layers < 1 || n->n_layers > SIREN_KAN_MAX_LAYERS) return SIREN_ERR_CONFIG;

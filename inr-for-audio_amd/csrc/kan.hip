@@ -4,13 +4,18 @@
 // and its autograd: dW = G^T A, dA = G W, dX = SiLU'(X) dA_base + sum_c B'_c(X) dA_spline_c.
 //
 // A and dA are never materialised (round 2; the first design wrote and re-read A / dA, 2.3 KB
-// per coordinate each at width 64, ~26 KB of HBM per coordinate-step).  Three fused kernels
-// recompute the bases of a (16-input x 64-row) chunk into LDS where they are consumed:
+// per coordinate each at width 64, ~26 KB of HBM per coordinate-step).  The fused kernels
+// recompute the bases of a (16-input x 64-row) chunk (KfChunk) into LDS where they are consumed:
 //   kan_fwd_fused  Out tile [64 rows][64 outs] = sum over input chunks of A_chunk W_chunk^T
 //   kan_dw_fused   dW chunk [out][144] += G[rows]^T A_chunk[rows]   (split-K over rows, slabs)
 //   kan_dx_fused   dA_chunk = G W_chunk (in LDS), contracted at once with the bases' derivatives
 //   kan_bwd_fused  both backward products of a chunk in one pass (out <= 64)
-//   kan_head_train the last layer (out = 1): forward, MSE gradient and backward in one pass
+//   kan_head_fwd / kan_head_train  the last layer (out = 1): inference; forward, MSE gradient and
+//                  backward in one pass (one row evaluation for both: kan_head_row)
+// The three backward kernels are put together from one set of tile helpers: kf_fill_a (A tile;
+// kan_bwd_fused keeps its own, with the derivatives in registers),
+// kf_g_load / kf_g_store / kf_g_scalar (G tile), kf_load_wt (W^T chunk), kf_da_to_gin (dA -> Gin),
+// kf_split_block / kf_store_slab / kf_plan_splits (row splits and their slabs).
 // Everything is fp32 like the reference.  The bases follow kan.py:94-104's Cox-de Boor
 // recursion op for op (sub, div, mul, add; fp-contract off) on the layer's own `grid` buffer,
 // so they are bit-identical to torch's CPU result; the derivative differentiates the same
@@ -33,9 +38,7 @@
 
 namespace siren {
 
-constexpr int KAN_NB = 8;       // grid_size + spline_order bases per input
-constexpr int KAN_NG = 12;      // grid knots per input: grid_size + 2 * spline_order + 1
-constexpr int KAN_K1 = 1 + KAN_NB;  // columns of A per input feature
+constexpr int KAN_NG = 12;  // grid knots per input: grid_size + 2 * spline_order + 1 (KAN_NB, KAN_K1: siren_kernels.h)
 
 // Cox-de Boor recursion of kan.py:94-104 for one x on one input's knots g[0..11]: order-0
 // bases B[j] = (g[j] <= x < g[j+1]), then for k = 1..3
@@ -73,17 +76,16 @@ __device__ __forceinline__ int kan_bases_window(float x, const float* __restrict
                                                 const float* __restrict__ inv) {
   int s = -1;
   float kw[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-if constexpr (GATHER) {
-  // span by counting: for non-decreasing knots, g[s] <= x < g[s+1] holds exactly for
-  // s = #{j : g[j] <= x} - 1 when that count is 1 .. NG-1 (x below the first knot, at or past the
-  // last one, or NaN: no span), the same s as the per-span predicate below.  The window is then
-  // one gather of 8 knots from the LDS row g (indices clamped into the array; the entries a clamp
-  // touches belong to terms the recursion discards)
-  int cnt = 0;
+  if constexpr (GATHER) {
+    // span by counting: for non-decreasing knots, g[s] <= x < g[s+1] holds exactly for
+    // s = #{j : g[j] <= x} - 1 when that count is 1 .. NG-1 (x below the first knot, at or past the
+    // last one, or NaN: no span), the same s as the per-span predicate below.  The window is then
+    // one gather of 8 knots from the LDS row g (indices clamped into the array; the entries a clamp
+    // touches belong to terms the recursion discards)
+    int cnt = 0;
 #pragma unroll
-  for (int j = 0; j < KAN_NG; ++j) cnt += (x >= g[j]) ? 1 : 0;
-  s = (cnt >= 1 && cnt <= KAN_NG - 1) ? cnt - 1 : -1;
-  {
+    for (int j = 0; j < KAN_NG; ++j) cnt += (x >= g[j]) ? 1 : 0;
+    s = (cnt >= 1 && cnt <= KAN_NG - 1) ? cnt - 1 : -1;
     const int s0 = s < 0 ? 0 : s;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -91,21 +93,20 @@ if constexpr (GATHER) {
       t = t < 0 ? 0 : (t > KAN_NG - 1 ? KAN_NG - 1 : t);
       kw[e] = g[t];
     }
-  }
   } else {
-  float kn[KAN_NG];
+    float kn[KAN_NG];
 #pragma unroll
-  for (int j = 0; j < KAN_NG; ++j) kn[j] = g[j];
+    for (int j = 0; j < KAN_NG; ++j) kn[j] = g[j];
 #pragma unroll
-  for (int j = 0; j < KAN_NG - 1; ++j) {
-    const bool hit = x >= kn[j] && x < kn[j + 1];
-    s = hit ? j : s;
+    for (int j = 0; j < KAN_NG - 1; ++j) {
+      const bool hit = x >= kn[j] && x < kn[j + 1];
+      s = hit ? j : s;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int t = j - 3 + e;
-      if (t >= 0 && t < KAN_NG) kw[e] = hit ? kn[t] : kw[e];
+      for (int e = 0; e < 8; ++e) {
+        const int t = j - 3 + e;
+        if (t >= 0 && t < KAN_NG) kw[e] = hit ? kn[t] : kw[e];
+      }
     }
-  }
   }
   // window w[q] = B[s - 3 + q], q = 0..3, plus w[4] = B[s + 1] = 0
   float ww[5] = {0.0f, 0.0f, 0.0f, 1.0f, 0.0f}, dd[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
@@ -171,12 +172,7 @@ __device__ __forceinline__ void kan_bases_local(float x, const float* __restrict
 }
 
 __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
-__device__ __forceinline__ float silu_grad(float x) {
-  const float s = 1.0f / (1.0f + expf(-x));
-  return s * (1.0f + x * (1.0f - s));
-}
-// silu(x) and silu_grad(x) on one exp: the same values as the two calls (same operations on the
-// same 1 + exp(-x))
+// silu(x) and its derivative on one exp (a caller that needs the derivative alone drops sl)
 __device__ __forceinline__ void silu_and_grad(float x, float& sl, float& dsl) {
   const float d = 1.0f + expf(-x);
   sl = x / d;
@@ -195,8 +191,14 @@ constexpr int KF_IC = 16, KF_KC = 9 * KF_IC, KF_R = 64, KF_O = 64;
 constexpr int64_t kKanResidentBlocks = 512;     // 256 CUs x 2 (LDS-limited) for the fused kernels
 constexpr int64_t kKanBwdResidentBlocks = 256;  // kan_bwd_fused: one 512-thread block per CU
 
-__device__ __forceinline__ int kf_col(int kk, int ic, int i0, int in) {
-  return kk < ic ? i0 + kk : in + 8 * i0 + (kk - ic);
+struct KfChunk {
+  int i0, ic, kc, kpad, nkt;  // first input, inputs, columns, columns padded to 16, 16-column tiles
+  // combined-weight column of local column kk < kc
+  __device__ __forceinline__ int col(int kk, int in) const { return kk < ic ? i0 + kk : in + 8 * i0 + (kk - ic); }
+};
+__device__ __forceinline__ KfChunk kf_chunk(int i0, int in) {
+  const int ic = in - i0 < KF_IC ? in - i0 : KF_IC, kc = KAN_K1 * ic, kpad = (kc + 15) & ~15;
+  return KfChunk{i0, ic, kc, kpad, kpad >> 4};
 }
 
 __device__ __forceinline__ f32x4 kf_mfma(float a, float b, f32x4 c) {
@@ -247,33 +249,6 @@ __device__ __forceinline__ void kf_fill_inv(float (*inv)[KF_VST], const float* _
   }
 }
 
-// As[kk][r] (pad 4) = A columns of the chunk for rows r0 + r (zero past re, and rows kc .. kpad-1
-// zero).  A wave takes one input ii and 64 consecutive rows: its knots / reciprocals are uniform
-// and the LDS writes are conflict-free.
-template <bool RCP = false>
-__device__ __forceinline__ void kf_fill_a(float (*As)[KF_R + 4], const float (*Xs)[KF_IC + 1],
-                                          const float (*gk)[KF_GST], int64_t re, int64_t r0, int i0, int ic,
-                                          int kpad) {
-  for (int p = threadIdx.x; p < KF_R * ic; p += blockDim.x) {
-    const int r = p & (KF_R - 1), ii = p >> 6;
-    float b[KAN_NB], unused[KAN_NB], sl = 0.f;
-    if (r0 + r < re) {
-      const float x = Xs[r][ii];
-      static_assert(RCP, "the exact forward bases need the reciprocal table (kf_put_pair)");
-      kan_bases_local<false, RCP>(x, gk[ii], b, unused);
-      sl = silu(x);
-    } else {
-#pragma unroll
-      for (int c = 0; c < KAN_NB; ++c) b[c] = 0.f;
-    }
-    As[ii][r] = sl;
-#pragma unroll
-    for (int c = 0; c < KAN_NB; ++c) As[ic + 8 * ii + c][r] = b[c];
-  }
-  const int kc = 9 * ic;
-  for (int e = threadIdx.x; e < (kpad - kc) * KF_R; e += blockDim.x) As[kc + e / KF_R][e % KF_R] = 0.f;
-}
-
 // Operand tiles are read with one ds_read_b128 per lane per 16-k group: lane group lk = l>>4
 // supplies k = 16 g + 4 lk + t to the t-th MFMA of group g (a permutation of the summation index
 // applied to both operands alike).  Row strides are 4 mod 32 floats, so each 8-lane phase of a
@@ -281,6 +256,189 @@ __device__ __forceinline__ void kf_fill_a(float (*As)[KF_R + 4], const float (*X
 // group's MFMAs issue.
 constexpr int KF_AST = KF_KC + 4;  // [row][kk] tiles of the forward
 constexpr int KF_CST = KF_R + 4;   // [*][row] / [*][o] tiles of the backward
+constexpr int KF_DST = KF_KC + 1;  // dA rows [r][kk] of the backward
+
+// ---- tile helpers of the backward kernels (blocks of T = 256 or 512 threads) ------------------
+// As[kk][r] (stride KF_CST) = A columns of the chunk for rows r0 + r (zero past re, and rows
+// kc .. kpad-1 zero), v_rcp_f32 quotients.  A wave takes one input ii and 64 consecutive rows: its
+// knots are uniform and the LDS writes are conflict-free.  The pair p of a block is (r, ii) =
+// (p & 63, p >> 6): kf_da_to_gin numbers them alike.  (kan_bwd_fused fills its A tile itself, with
+// the derivatives kept in registers: through this helper its products measured 0.9 % slower.)
+__device__ __forceinline__ void kf_fill_a(float (*As)[KF_CST], const float (*Xs)[KF_IC + 1], const float (*gk)[KF_GST],
+                                          int64_t re, int64_t r0, const KfChunk& ch) {
+  for (int p = threadIdx.x; p < KF_R * ch.ic; p += blockDim.x) {
+    const int r = p & (KF_R - 1), ii = p >> 6;
+    float b[KAN_NB], unused[KAN_NB], sl = 0.f;
+    if (r0 + r < re) {
+      const float x = Xs[r][ii];
+      kan_bases_local<false, true>(x, gk[ii], b, unused);
+      sl = silu(x);
+    } else {
+#pragma unroll
+      for (int c = 0; c < KAN_NB; ++c) b[c] = 0.f;
+    }
+    As[ii][r] = sl;
+#pragma unroll
+    for (int c = 0; c < KAN_NB; ++c) As[ch.ic + 8 * ii + c][r] = b[c];
+  }
+  for (int e = threadIdx.x; e < (ch.kpad - ch.kc) * KF_R; e += blockDim.x) As[ch.kc + e / KF_R][e % KF_R] = 0.f;
+}
+
+// G tile: 64 rows from r0 (zero past re) x 64 outs from oc of G[N][out], as Gl[r][o] or, TRANSPOSED,
+// Gl[o][r] (stride KF_CST).  In float4 pieces when out % 4 == 0 and the 64 outs exist: the thread's
+// piece q is idx = tid + T q; BY_ROW: lanes take consecutive rows (r = idx & 63, outs 4 (idx >> 6):
+// conflict-free transposed stores), else consecutive pieces of a row (r = idx >> 4, outs 4 (idx & 15)).
+// Loading to registers and storing to LDS are separate calls, so a tile costs one memory latency
+// and the next tile's loads can go out under the current tile's products.
+template <int T>
+using KfGRegs = float4[KF_R * KF_O / 4 / T];
+
+template <int T, bool BY_ROW>
+__device__ __forceinline__ void kf_g_piece(int q, int& r, int& o4) {
+  const int idx = threadIdx.x + T * q;
+  r = BY_ROW ? idx & 63 : idx >> 4;
+  o4 = BY_ROW ? idx >> 6 : idx & 15;
+}
+
+template <int T, bool BY_ROW>
+__device__ __forceinline__ void kf_g_load(KfGRegs<T>& v, const float* __restrict__ G, int64_t re, int out, int64_t r0,
+                                          int oc) {
+#pragma unroll
+  for (int q = 0; q < KF_R * KF_O / 4 / T; ++q) {
+    int r, o4;
+    kf_g_piece<T, BY_ROW>(q, r, o4);
+    v[q] = r0 + r < re ? ldg4(G + (r0 + r) * out + oc + 4 * o4) : float4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+
+template <int T, bool BY_ROW, bool TRANSPOSED>
+__device__ __forceinline__ void kf_g_store(float* Gl, const KfGRegs<T>& v) {
+#pragma unroll
+  for (int q = 0; q < KF_R * KF_O / 4 / T; ++q) {
+    int r, o4;
+    kf_g_piece<T, BY_ROW>(q, r, o4);
+    if constexpr (TRANSPOSED) {
+      Gl[(4 * o4) * KF_CST + r] = v[q].x;
+      Gl[(4 * o4 + 1) * KF_CST + r] = v[q].y;
+      Gl[(4 * o4 + 2) * KF_CST + r] = v[q].z;
+      Gl[(4 * o4 + 3) * KF_CST + r] = v[q].w;
+    } else {
+      *reinterpret_cast<float4*>(Gl + r * KF_CST + 4 * o4) = v[q];
+    }
+  }
+}
+
+// any out and oc: element by element, bounds-checked (lanes along the rows or along the outs)
+template <int T, bool BY_ROW, bool TRANSPOSED>
+__device__ __forceinline__ void kf_g_scalar(float* Gl, const float* __restrict__ G, int64_t re, int out, int64_t r0,
+                                            int oc) {
+  for (int e = threadIdx.x; e < KF_R * KF_O; e += T) {
+    const int r = BY_ROW ? e % KF_R : e / KF_O, o = BY_ROW ? e / KF_R : e % KF_O;
+    Gl[TRANSPOSED ? o * KF_CST + r : r * KF_CST + o] = (r0 + r < re && oc + o < out) ? G[(r0 + r) * out + oc + o] : 0.f;
+  }
+}
+
+// Wl[kk][o] (stride KF_CST) = W[oc + o][col(kk)] through the transposed copy WT[9 in][out] (rows
+// along o: coalesced, no conflicts); rows kc .. kpad-1 and the outs past `out` are zero.  vec (256
+// threads, a full chunk with in % 4 == 0, out % 4 == 0 and the 64 outs exist): 9 float4 pieces a thread.
+template <int T>
+__device__ __forceinline__ void kf_load_wt(float* Wl, const float* __restrict__ WT, const KfChunk& ch, int in, int out,
+                                           int oc, bool vec) {
+  if constexpr (T * 9 == KF_KC * KF_O / 4) {
+    if (vec) {
+      float4 v[9];
+#pragma unroll
+      for (int q = 0; q < 9; ++q) {
+        const int idx = threadIdx.x + T * q, kk = idx >> 4, o4 = idx & 15;
+        v[q] = ldg4(WT + (int64_t)ch.col(kk, in) * out + oc + 4 * o4);
+      }
+#pragma unroll
+      for (int q = 0; q < 9; ++q) {
+        const int idx = threadIdx.x + T * q, kk = idx >> 4, o4 = idx & 15;
+        *reinterpret_cast<float4*>(Wl + kk * KF_CST + 4 * o4) = v[q];
+      }
+      return;
+    }
+  }
+  for (int e = threadIdx.x; e < ch.kpad * KF_O; e += T) {
+    const int kk = e / KF_O, o = e % KF_O;
+    Wl[kk * KF_CST + o] = (kk < ch.kc && oc + o < out) ? WT[(int64_t)ch.col(kk, in) * out + oc + o] : 0.f;
+  }
+}
+
+// dA -> Gin.  The wave's dA accumulators (acc[j][q]: row `row` + q, column `col` + 16 j, j < nj) go
+// to LDS as dAs[r][kk] (stride KF_DST) over the operand tile they came from, whose reads the
+// caller's barrier has ended (columns past kc hold products of zero-padded W rows and are never
+// read); the thread's pair h, p = tid + T h in kf_fill_a's numbering, contracts its row,
+//   Gin[n][i] = SiLU'(x) dA[n][i] + sum_c B'_c(x) dA[n][in + 8 i + c],
+// with the caller's dsl[h] = SiLU' and db[h][] = B' (REGS: kan_bwd_fused, the pair loop unrolled)
+// or with the derivatives recomputed from Xs and gk, into Xs[r][ii] -- the element that thread
+// alone reads -- and the X tile leaves as coalesced row segments.  The caller's next barrier frees
+// Xs and dAs for refilling.
+template <int T, bool REGS, int NA>
+__device__ __forceinline__ void kf_da_to_gin(float* dAs, float (*Xs)[KF_IC + 1], const float (*gk)[KF_GST],
+                                             const f32x4 (&acc)[NA], int nj, int row, int col, int64_t re, int64_t r0,
+                                             int in, const KfChunk& ch, const float* dsl, const float (*db)[KAN_NB],
+                                             float* __restrict__ Gin) {
+#pragma unroll
+  for (int j = 0; j < NA; ++j)
+    if (j < nj)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) dAs[(row + q) * KF_DST + col + 16 * j] = acc[j][q];
+  __syncthreads();
+  constexpr int NH = KF_R * KF_IC / T;
+#pragma unroll REGS ? NH : 1
+  for (int h = 0; h < NH; ++h) {
+    const int p = threadIdx.x + T * h, r = p & (KF_R - 1), ii = p >> 6;
+    if (ii >= ch.ic || r0 + r >= re) continue;
+    float b[KAN_NB], dbl[KAN_NB], sl, ds;
+    if constexpr (REGS) {
+      ds = dsl[h];
+    } else {
+      const float x = Xs[r][ii];
+      kan_bases_local<true, true>(x, gk[ii], b, dbl);
+      silu_and_grad(x, sl, ds);
+    }
+    const float* dA = dAs + r * KF_DST;
+    float v = ds * dA[ii];
+#pragma unroll
+    for (int c = 0; c < KAN_NB; ++c) v += (REGS ? db[h][c] : dbl[c]) * dA[ch.ic + 8 * ii + c];
+    Xs[r][ii] = v;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e < KF_R * ch.ic; e += T) {
+    const int r = e / ch.ic, ii = e - r * ch.ic;
+    if (r0 + r < re) Gin[(r0 + r) * in + ch.i0 + ii] = Xs[r][ii];
+  }
+}
+
+// The 1-D grids of the split-K kernels hold per * zpad blocks (per chunk tiles, zpad = splits
+// rounded up to 8), numbered so that the blocks of one split (which read the same rows of G and X)
+// share an XCD: block L runs on XCD L % 8.  -> the block's chunk tile cid and split z (>= splits
+// for the padding blocks, which leave at once).
+__device__ __forceinline__ void kf_split_block(int per, int& cid, int& z) {
+  const int L = blockIdx.x, q8 = L >> 3;
+  cid = q8 % per;
+  z = (q8 / per) * 8 + (L & 7);
+}
+
+// slab[z][o + q][col(kk)] = acc[j][q] for the wave's dW accumulators: outs o .. o + 3, local
+// columns kk = kk0 + 16 j (j < nj)
+template <int NA>
+__device__ __forceinline__ void kf_store_slab(float* __restrict__ slab, int z, const f32x4 (&acc)[NA], int nj, int kk0,
+                                              int o, const KfChunk& ch, int in, int out) {
+  const int64_t K = (int64_t)KAN_K1 * in;
+  float* out_slab = slab + (int64_t)z * out * K;
+#pragma unroll
+  for (int j = 0; j < NA; ++j) {
+    const int kk = kk0 + 16 * j;
+    if (j >= nj || kk >= ch.kc) continue;
+    const int64_t col = ch.col(kk, in);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (o + q < out) out_slab[(int64_t)(o + q) * K + col] = acc[j][q];
+  }
+}
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float f4(const float4& v, int t) { return t == 0 ? v.x : t == 1 ? v.y : t == 2 ? v.z : v.w; }
@@ -395,9 +553,11 @@ __global__ __launch_bounds__(256) void kan_fwd_fused_kernel(const float* __restr
   };
   if (vec) load_chunk(0);
   for (int i0 = 0; i0 < in; i0 += KF_IC) {
-    const int ic = in - i0 < KF_IC ? in - i0 : KF_IC, kc = 9 * ic, kpad = (kc + 15) & ~15;
+    const KfChunk ch = kf_chunk(i0, in);
+    const int ic = ch.ic, kc = ch.kc, kpad = ch.kpad;
     kf_fill_knots(gk, grid, i0, ic);
     kf_fill_inv(inv, grid, i0, ic);
+    // W chunk as Ws[o][kk]: from W's rows, unlike the backward's kf_load_wt
     if (vec) {
 #pragma unroll
       for (int q = 0; q < 9; ++q) {
@@ -407,7 +567,7 @@ __global__ __launch_bounds__(256) void kan_fwd_fused_kernel(const float* __restr
     } else {
       for (int e = tid; e < KF_O * kpad; e += blockDim.x) {
         const int o = e / kpad, kk = e - o * kpad;
-        Ws[o][kk] = (o0 + o < out && kk < kc) ? W[(int64_t)(o0 + o) * K + kf_col(kk, ic, i0, in)] : 0.f;
+        Ws[o][kk] = (o0 + o < out && kk < kc) ? W[(int64_t)(o0 + o) * K + ch.col(kk, in)] : 0.f;
       }
       for (int e = tid; e < (kpad - kc) * KF_R; e += blockDim.x) As[e % KF_R][kc + e / KF_R] = 0.f;
     }
@@ -444,42 +604,66 @@ __global__ __launch_bounds__(256) void kan_fwd_fused_kernel(const float* __restr
 
 // ---- the last layer (out = 1, in <= 64): one wave per row, lane = input ----------------------
 // out[n] = SiLU(x_lane) W[lane] + sum_c B_c(x_lane) W[in + 8 lane + c], summed over the wave in a
-// fixed butterfly order.
+// fixed butterfly order.  kan_head_fwd and kan_head_train share the set-up and the row evaluation,
+// so the training pass's out is the inference's bit for bit.
+struct KanHeadLane {  // lane i's weights: W[i] and W[in + 8 i + c] (zero for the lanes past in)
+  float wb, ws[KAN_NB];
+};
+
+// the block's knots and reciprocals into LDS, and the lane's weights
+__device__ __forceinline__ KanHeadLane kan_head_setup(float (*gk)[KF_GST], float (*inv)[KF_VST],
+                                                      const float* __restrict__ grid, const float* __restrict__ W,
+                                                      int in) {
+  kf_fill_knots(gk, grid, 0, in);
+  kf_fill_inv(inv, grid, 0, in);
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  KanHeadLane w = {};
+  if (lane < in) {
+    w.wb = W[lane];
+#pragma unroll
+    for (int c = 0; c < KAN_NB; ++c) w.ws[c] = W[in + KAN_NB * lane + c];
+  }
+  return w;
+}
+
+// the row's output on every lane, from lane i's input x (read when `on`: i < in); on those lanes
+// also sl = SiLU(x), b[] = B(x) and, with DERIV, dsl = SiLU'(x) and db[] = B'(x)
+template <bool DERIV>
+__device__ __forceinline__ float kan_head_row(bool on, float x, const float* g, const float* inv, const KanHeadLane& w,
+                                              float& sl, float& dsl, float* b, float* db) {
+  float v = 0.f;
+  if (on) {
+    kan_bases_local<DERIV, false, false>(x, g, b, db, inv);  // lane-fixed knots: selects
+    if constexpr (DERIV) silu_and_grad(x, sl, dsl);
+    else sl = silu(x);
+    v = sl * w.wb;
+#pragma unroll
+    for (int c = 0; c < KAN_NB; ++c) v += b[c] * w.ws[c];
+  }
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
 __global__ __launch_bounds__(256) void kan_head_fwd_kernel(const float* __restrict__ X, const float* __restrict__ grid,
                                                            const float* __restrict__ W, int64_t N, int in,
                                                            float* __restrict__ Y) {
   __shared__ float gk[64][KF_GST];
   __shared__ float inv[64][KF_VST];
-  kf_fill_knots(gk, grid, 0, in);
-  kf_fill_inv(inv, grid, 0, in);
-  __syncthreads();
+  const KanHeadLane w = kan_head_setup(gk, inv, grid, W, in);
   const int lane = threadIdx.x & 63;
   const bool on = lane < in;
-  float wb = 0.f, ws[KAN_NB] = {};
-  if (on) {
-    wb = W[lane];
-#pragma unroll
-    for (int c = 0; c < KAN_NB; ++c) ws[c] = W[in + KAN_NB * lane + c];
-  }
   const int64_t nw = (int64_t)gridDim.x * (blockDim.x >> 6);
   for (int64_t n = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); n < N; n += nw) {
-    float v = 0.f;
-    if (on) {
-      const float x = X[n * in + lane];
-      float b[KAN_NB], unused[KAN_NB];
-      kan_bases_local<false, false, false>(x, gk[lane], b, unused, inv[lane]);  // lane-fixed knots: selects
-      v = silu(x) * wb;
-#pragma unroll
-      for (int c = 0; c < KAN_NB; ++c) v += b[c] * ws[c];
-    }
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    float sl, unused, b[KAN_NB], db[KAN_NB];
+    const float v = kan_head_row<false>(on, on ? X[n * in + lane] : 0.f, gk[lane], inv[lane], w, sl, unused, b, db);
     if (lane == 0) Y[n] = v;
   }
 }
 
 // Training step of the last layer (out = 1, in <= 64) in one pass over its rows.  Per row: the
-// forward out = SiLU(x) W[i] + sum_c B_c(x) W[in + 8 i + c] with kan_head_fwd's exact bases and
-// butterfly (so out is bit-identical to inference), the MSE gradient g = 2 (out - y) / N and the
+// forward out = SiLU(x) W[i] + sum_c B_c(x) W[in + 8 i + c] through kan_head_row like
+// kan_head_fwd (so out is bit-identical to inference), the MSE gradient g = 2 (out - y) / N and the
 // squared error (run.py:160-168; rows >= n_valid contribute nothing), then the backward: Gin[n][i]
 // = g_n (SiLU'(x) W[i] + sum_c B'_c(x) W[in + 8 i + c]) (dA = g W is a rank-1 product, never
 // formed) and the weight-gradient partials -- one basis evaluation per (row, input) for the
@@ -495,19 +679,11 @@ __global__ __launch_bounds__(256) void kan_head_train_kernel(const float* __rest
   __shared__ float inv[64][KF_VST];
   __shared__ float part[4][KAN_K1][64];
   __shared__ float sse_w[4];
-  kf_fill_knots(gk, grid, 0, in);
-  kf_fill_inv(inv, grid, 0, in);
-  __syncthreads();
+  const KanHeadLane w = kan_head_setup(gk, inv, grid, W, in);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t nb = (int64_t)blockIdx.x * rows_per_block;
   const int64_t ne = nb + rows_per_block < N ? nb + rows_per_block : N;
   const bool on = lane < in;
-  float wb = 0.f, ws[KAN_NB] = {};
-  if (on) {
-    wb = W[lane];
-#pragma unroll
-    for (int c = 0; c < KAN_NB; ++c) ws[c] = W[in + KAN_NB * lane + c];
-  }
   float ab = 0.f, as[KAN_NB] = {}, sse = 0.f;
   // the next row's x and y are loaded before this row's stores: vmcnt retires loads and stores in
   // issue order, so a load issued after the stores would wait for them too
@@ -523,16 +699,8 @@ __global__ __launch_bounds__(256) void kan_head_train_kernel(const float* __rest
       if (on) xn = X[(n + 4) * in + lane];
       if (n + 4 < n_valid) yn = y[n + 4];
     }
-    float x = 0.f, v = 0.f, sl = 0.f, b[KAN_NB], db[KAN_NB];
-    if (on) {
-      x = xc;
-      kan_bases_local<true, false, false>(x, gk[lane], b, db, inv[lane]);  // lane-fixed knots: selects
-      sl = silu(x);
-      v = sl * wb;
-#pragma unroll
-      for (int c = 0; c < KAN_NB; ++c) v += b[c] * ws[c];
-    }
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    float sl, dsl, b[KAN_NB], db[KAN_NB];
+    const float v = kan_head_row<true>(on, xc, gk[lane], inv[lane], w, sl, dsl, b, db);
     const float o = (0.f + v) + 0.f;  // head_loss's accumulation of the one partial and the zero bias
     float gn = 0.f;
     if (n < n_valid) {
@@ -546,11 +714,11 @@ __global__ __launch_bounds__(256) void kan_head_train_kernel(const float* __rest
     }
     if (on) {
       ab += gn * sl;
-      float d = silu_grad(x) * wb;
+      float d = dsl * w.wb;
 #pragma unroll
       for (int c = 0; c < KAN_NB; ++c) {
         as[c] += gn * b[c];
-        d += db[c] * ws[c];
+        d += db[c] * w.ws[c];
       }
       Gin[n * in + lane] = gn * d;
     }
@@ -574,9 +742,8 @@ __global__ __launch_bounds__(256) void kan_head_train_kernel(const float* __rest
 }
 
 // slab[z][o][k] = sum over rows of split z of G[n][o] A[n][k], for the chunk's columns k.
-// 1-D grid of nchunk * nout * zpad blocks (zpad = splits rounded up to 8), numbered so that the
-// blocks of one split (which read the same rows of G and X) share an XCD: block L runs on XCD
-// L % 8.  Wave w: outs 16w .. 16w+15 x the chunk's kpad columns (kpad/16 accumulators), K = rows.
+// 1-D grid of nchunk * nout * zpad blocks (kf_split_block).  Wave w: outs 16w .. 16w+15 x the
+// chunk's kpad columns (kpad/16 accumulators), K = rows.
 __global__ __launch_bounds__(256) void kan_dw_fused_kernel(const float* __restrict__ X, const float* __restrict__ grid,
                                                            const float* __restrict__ G, int64_t N, int in, int out,
                                                            int64_t rows_per_split, int nchunk, int nout, int splits,
@@ -585,62 +752,35 @@ __global__ __launch_bounds__(256) void kan_dw_fused_kernel(const float* __restri
   __shared__ __attribute__((aligned(16))) float Gt[KF_O][KF_CST];   // [o][r]
   __shared__ float Xs[KF_R][KF_IC + 1];
   __shared__ float gk[KF_IC][KF_GST];
-  const int per = nchunk * nout, L = blockIdx.x, q8 = L >> 3;
-  const int cid = q8 % per, z = (q8 / per) * 8 + (L & 7);
+  int cid, z;
+  kf_split_block(nchunk * nout, cid, z);
   if (z >= splits) return;  // whole block, before any barrier
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, lk = lane >> 4;
-  const int i0 = (cid % nchunk) * KF_IC, o0 = (cid / nchunk) * KF_O;
-  const int ic = in - i0 < KF_IC ? in - i0 : KF_IC, kc = 9 * ic, kpad = (kc + 15) & ~15, nkt = kpad >> 4;
-  kf_fill_knots(gk, grid, i0, ic);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
+  const int o0 = (cid / nchunk) * KF_O;
+  const KfChunk ch = kf_chunk((cid % nchunk) * KF_IC, in);
+  kf_fill_knots(gk, grid, ch.i0, ch.ic);
   const int64_t rb = (int64_t)z * rows_per_split;
   const int64_t re = rb + rows_per_split < N ? rb + rows_per_split : N;
   f32x4 acc[9];
 #pragma unroll
   for (int j = 0; j < 9; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
   for (int64_t r0 = rb; r0 < re; r0 += KF_R) {
-    kf_stage_x(Xs, X, re, in, r0, i0, ic);
+    kf_stage_x(Xs, X, re, in, r0, ch.i0, ch.ic);
     if ((out & 3) == 0 && o0 + KF_O <= out) {
-      // lanes take consecutive rows (conflict-free transposed stores), 16 bytes of outs each
-      float4 v[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int idx = tid + 256 * q, o4 = idx >> 6, r = idx & 63;
-        v[q] = r0 + r < re ? ldg4(G + (r0 + r) * out + o0 + 4 * o4) : float4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int idx = tid + 256 * q, o4 = idx >> 6, r = idx & 63;
-        Gt[4 * o4][r] = v[q].x;
-        Gt[4 * o4 + 1][r] = v[q].y;
-        Gt[4 * o4 + 2][r] = v[q].z;
-        Gt[4 * o4 + 3][r] = v[q].w;
-      }
+      KfGRegs<256> v;
+      kf_g_load<256, true>(v, G, re, out, r0, o0);
+      kf_g_store<256, true, true>(&Gt[0][0], v);
     } else {
-      for (int e = tid; e < KF_R * KF_O; e += blockDim.x) {
-        const int r = e / KF_O, o = e % KF_O;
-        Gt[o][r] = (r0 + r < re && o0 + o < out) ? G[(r0 + r) * out + o0 + o] : 0.f;
-      }
+      kf_g_scalar<256, false, true>(&Gt[0][0], G, re, out, r0, o0);
     }
     __syncthreads();
-    kf_fill_a<true>(As, Xs, gk, re, r0, i0, ic, kpad);
+    kf_fill_a(As, Xs, gk, re, r0, ch);
     __syncthreads();
     if ((KAN_ABL & 2) == 0)
-      kf_mfma_groups_n(nkt, &Gt[16 * wv + li][4 * lk], &As[li][4 * lk], 16 * KF_CST, KF_R / 16, acc);
+      kf_mfma_groups_n(ch.nkt, &Gt[16 * wv + li][4 * lk], &As[li][4 * lk], 16 * KF_CST, KF_R / 16, acc);
     __syncthreads();
   }
-  const int64_t K = (int64_t)KAN_K1 * in;
-  float* out_slab = slab + (int64_t)z * out * K;
-#pragma unroll
-  for (int j = 0; j < 9; ++j) {
-    const int kk = 16 * j + li;
-    if (j >= nkt || kk >= kc) continue;
-    const int64_t col = kf_col(kk, ic, i0, in);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int o = o0 + 16 * wv + 4 * lk + q;
-      if (o < out) out_slab[(int64_t)o * K + col] = acc[j][q];
-    }
-  }
+  kf_store_slab(slab, z, acc, ch.nkt, li, o0 + 16 * wv + 4 * lk, ch, in, out);
 }
 
 // Gin[n][i] = SiLU'(x) dA[n][i] + sum_c B'_c(x) dA[n][in + 8 i + c], dA = Gout W (never stored;
@@ -648,9 +788,7 @@ __global__ __launch_bounds__(256) void kan_dw_fused_kernel(const float* __restri
 // grid ceil(N/64): a block takes 64 rows through every input chunk (its Gout rows stay in LDS
 // when out <= 64).  Wave w: rows 16w .. 16w+15 x the chunk's columns (kpad/16 accumulators),
 // K = outs; the dA tile then goes to LDS (over the W chunk) for the contraction with the bases'
-// derivatives, whose results leave through the X tile as coalesced row segments.
-constexpr int KF_DST = KF_KC + 1;  // dA row stride
-
+// derivatives, whose results leave through the X tile as coalesced row segments (kf_da_to_gin).
 __global__ __launch_bounds__(256) void kan_dx_fused_kernel(const float* __restrict__ X, const float* __restrict__ grid,
                                                            const float* __restrict__ Gout, const float* __restrict__ WT,
                                                            int64_t N, int in, int out, float* __restrict__ Gin) {
@@ -658,88 +796,35 @@ __global__ __launch_bounds__(256) void kan_dx_fused_kernel(const float* __restri
   __shared__ __attribute__((aligned(16))) float WD[KF_KC * KF_CST];  // Wt[kk][o], then dAs[r][kk]
   __shared__ float Xs[KF_R][KF_IC + 1];
   __shared__ float gk[KF_IC][KF_GST];
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, lk = lane >> 4;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, li = lane & 15, lk = lane >> 4;
   const int64_t r0 = (int64_t)blockIdx.x * KF_R;
-  const int64_t K = (int64_t)KAN_K1 * in;
   const bool g_once = out <= KF_O;
   for (int i0 = 0; i0 < in; i0 += KF_IC) {
-    const int ic = in - i0 < KF_IC ? in - i0 : KF_IC, kc = 9 * ic, nkt = (kc + 15) >> 4;
+    const KfChunk ch = kf_chunk(i0, in);
     f32x4 acc[9];
 #pragma unroll
     for (int j = 0; j < 9; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    kf_fill_knots(gk, grid, i0, ic);
-    kf_stage_x(Xs, X, N, in, r0, i0, ic);
+    kf_fill_knots(gk, grid, i0, ch.ic);
+    kf_stage_x(Xs, X, N, in, r0, i0, ch.ic);
     for (int oc = 0; oc < out; oc += KF_O) {
       const int on = out - oc < KF_O ? out - oc : KF_O, opad = (on + 15) & ~15;
       const bool vec = (out & 3) == 0 && on == KF_O;
       if (!g_once || i0 == 0) {
         if (vec) {
-          float4 v[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int idx = tid + 256 * q, r = idx >> 4, o4 = idx & 15;
-            v[q] = r0 + r < N ? ldg4(Gout + (r0 + r) * out + oc + 4 * o4) : float4{0.f, 0.f, 0.f, 0.f};
-          }
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int idx = tid + 256 * q, r = idx >> 4, o4 = idx & 15;
-            *reinterpret_cast<float4*>(&Gs[r][4 * o4]) = v[q];
-          }
+          KfGRegs<256> v;
+          kf_g_load<256, false>(v, Gout, N, out, r0, oc);
+          kf_g_store<256, false, false>(&Gs[0][0], v);
         } else {
-          for (int e = tid; e < KF_R * KF_O; e += blockDim.x) {
-            const int r = e / KF_O, o = e % KF_O;
-            Gs[r][o] = (r0 + r < N && o < on) ? Gout[(r0 + r) * out + oc + o] : 0.f;
-          }
+          kf_g_scalar<256, false, false>(&Gs[0][0], Gout, N, out, r0, oc);
         }
       }
-      // Wt[kk][o] = W[oc + o][col(kk)] from the transposed copy (rows along o: coalesced, no conflicts)
-      if (vec && ic == KF_IC && (in & 3) == 0) {
-        float4 v[9];
-#pragma unroll
-        for (int q = 0; q < 9; ++q) {
-          const int idx = tid + 256 * q, kk = idx >> 4, o4 = idx & 15;
-          v[q] = ldg4(WT + (int64_t)kf_col(kk, ic, i0, in) * out + oc + 4 * o4);
-        }
-#pragma unroll
-        for (int q = 0; q < 9; ++q) {
-          const int idx = tid + 256 * q, kk = idx >> 4, o4 = idx & 15;
-          *reinterpret_cast<float4*>(&WD[kk * KF_CST + 4 * o4]) = v[q];
-        }
-      } else {
-        for (int e = tid; e < kc * KF_O; e += blockDim.x) {
-          const int kk = e / KF_O, o = e % KF_O;
-          WD[kk * KF_CST + o] = o < on ? WT[(int64_t)kf_col(kk, ic, i0, in) * out + oc + o] : 0.f;
-        }
-      }
+      kf_load_wt<256>(WD, WT, ch, in, out, oc, vec && ch.ic == KF_IC && (in & 3) == 0);
       __syncthreads();
       if ((KAN_ABL & 2) == 0)
-        kf_mfma_groups_n(nkt, &Gs[16 * wv + li][4 * lk], &WD[li * KF_CST + 4 * lk], 16 * KF_CST, opad >> 4, acc);
+        kf_mfma_groups_n(ch.nkt, &Gs[16 * wv + li][4 * lk], &WD[li * KF_CST + 4 * lk], 16 * KF_CST, opad >> 4, acc);
       __syncthreads();
     }
-    // columns kc .. 16 nkt - 1 of dA hold products with stale LDS: never read below
-#pragma unroll
-    for (int j = 0; j < 9; ++j)
-      if (j < nkt)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) WD[(16 * wv + 4 * lk + q) * KF_DST + 16 * j + li] = acc[j][q];
-    __syncthreads();
-    for (int p = tid; p < KF_R * ic; p += blockDim.x) {
-      const int r = p & (KF_R - 1), ii = p >> 6;
-      if (r0 + r >= N) continue;
-      const float x = Xs[r][ii];
-      float b[KAN_NB], db[KAN_NB];
-      kan_bases_local<true, true>(x, gk[ii], b, db);
-      const float* dA = WD + r * KF_DST;
-      float v = silu_grad(x) * dA[ii];
-#pragma unroll
-      for (int c = 0; c < KAN_NB; ++c) v += db[c] * dA[ic + 8 * ii + c];
-      Xs[r][ii] = v;  // same element this thread read: no barrier needed before the write
-    }
-    __syncthreads();
-    for (int e = tid; e < KF_R * ic; e += blockDim.x) {
-      const int r = e / ic, ii = e - r * ic;
-      if (r0 + r < N) Gin[(r0 + r) * in + i0 + ii] = Xs[r][ii];
-    }
+    kf_da_to_gin<256, false>(WD, Xs, gk, acc, ch.nkt, 16 * wv + 4 * lk, li, N, r0, in, ch, nullptr, nullptr, Gin);
     __syncthreads();  // Xs / gk / WD are refilled by the next chunk
   }
 }
@@ -768,23 +853,18 @@ __global__ __launch_bounds__(KB_THREADS) void kan_bwd_fused_kernel(const float* 
   __shared__ __attribute__((aligned(16))) float Wt[KF_KC * KF_CST];  // W chunk [kk][o]
   __shared__ float Xs[KF_R][KF_IC + 1];
   __shared__ float gk[KF_IC][KF_GST];
-  const int L = blockIdx.x, q8 = L >> 3;
-  const int cid = q8 % nchunk, z = (q8 / nchunk) * 8 + (L & 7);
+  int cid, z;
+  kf_split_block(nchunk, cid, z);
   if (z >= splits) return;  // whole block, before any barrier
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, li = lane & 15, lk = lane >> 4;
   const int wr = wv & 3, wh = wv >> 2;  // 16-row (or 16-out) group, column half
-  const int i0 = cid * KF_IC;
-  const int ic = in - i0 < KF_IC ? in - i0 : KF_IC, kc = 9 * ic, kpad = (kc + 15) & ~15, nkt = kpad >> 4;
-  const int j0 = 5 * wh, nj = nkt - j0 < 0 ? 0 : (nkt - j0 > 5 ? 5 : nkt - j0);
+  const KfChunk ch = kf_chunk(cid * KF_IC, in);
+  const int j0 = 5 * wh, nj = ch.nkt - j0 < 0 ? 0 : (ch.nkt - j0 > 5 ? 5 : ch.nkt - j0);
   const int opad = (out + 15) & ~15;
-  const int64_t K = (int64_t)KAN_K1 * in;
-  const bool vec = ic == KF_IC && (in & 3) == 0 && out == KF_O;
-  kf_fill_knots(gk, grid, i0, ic);
+  const bool vec = ch.ic == KF_IC && (in & 3) == 0 && out == KF_O;
+  kf_fill_knots(gk, grid, ch.i0, ch.ic);
   // the chunk's W^T [kk][o] stays in LDS for the whole split
-  for (int e = tid; e < kpad * KF_O; e += KB_THREADS) {
-    const int kk = e / KF_O, o = e % KF_O;
-    Wt[kk * KF_CST + o] = (kk < kc && o < out) ? WT[(int64_t)kf_col(kk, ic, i0, in) * out + o] : 0.f;
-  }
+  kf_load_wt<KB_THREADS>(Wt, WT, ch, in, out, 0, false);
   const int64_t rb = (int64_t)z * rows_per_split;
   const int64_t re = rb + rows_per_split < N ? rb + rows_per_split : N;
   f32x4 accw[5];
@@ -794,20 +874,14 @@ __global__ __launch_bounds__(KB_THREADS) void kan_bwd_fused_kernel(const float* 
   const int xr = tid >> 2, xi = (tid & 3) * 4;
   auto load_x = [&](int64_t r0) {
     float4 v = float4{0.f, 0.f, 0.f, 0.f};
-    if (tid < 256 && r0 + xr < re) v = ldg4(X + (r0 + xr) * in + i0 + xi);
+    if (tid < 256 && r0 + xr < re) v = ldg4(X + (r0 + xr) * in + ch.i0 + xi);
     return v;
   };
-  auto load_g = [&](int64_t r0, int q) {  // piece q: rows (tid + 512 q) & 63, outs 4 * ((tid + 512 q) >> 6)
-    const int idx = tid + KB_THREADS * q, r = idx & 63, o4 = idx >> 6;
-    float4 v = float4{0.f, 0.f, 0.f, 0.f};
-    if (r0 + r < re) v = ldg4(G + (r0 + r) * out + 4 * o4);
-    return v;
-  };
-  float4 xv = float4{0.f, 0.f, 0.f, 0.f}, gv0 = xv, gv1 = xv;
+  float4 xv = float4{0.f, 0.f, 0.f, 0.f};
+  KfGRegs<KB_THREADS> gv = {xv, xv};
   if (vec && rb < re) {
     xv = load_x(rb);
-    gv0 = load_g(rb, 0);
-    gv1 = load_g(rb, 1);
+    kf_g_load<KB_THREADS, true>(gv, G, re, out, rb, 0);
   }
   for (int64_t r0 = rb; r0 < re; r0 += KF_R) {
     // ---- X and G^T tiles into LDS
@@ -818,24 +892,13 @@ __global__ __launch_bounds__(KB_THREADS) void kan_bwd_fused_kernel(const float* 
         Xs[xr][xi + 2] = xv.z;
         Xs[xr][xi + 3] = xv.w;
       }
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const float4 v = q ? gv1 : gv0;
-        const int idx = tid + KB_THREADS * q, r = idx & 63, o4 = idx >> 6;
-        GG[(4 * o4) * KF_CST + r] = v.x;
-        GG[(4 * o4 + 1) * KF_CST + r] = v.y;
-        GG[(4 * o4 + 2) * KF_CST + r] = v.z;
-        GG[(4 * o4 + 3) * KF_CST + r] = v.w;
-      }
+      kf_g_store<KB_THREADS, true, true>(GG, gv);
     } else {
-      kf_stage_x(Xs, X, re, in, r0, i0, ic);
-      for (int e = tid; e < KF_R * KF_O; e += KB_THREADS) {
-        const int o = e / KF_R, r = e % KF_R;
-        GG[o * KF_CST + r] = (r0 + r < re && o < out) ? G[(r0 + r) * out + o] : 0.f;
-      }
+      kf_stage_x(Xs, X, re, in, r0, ch.i0, ch.ic);
+      kf_g_scalar<KB_THREADS, true, true>(GG, G, re, out, r0, 0);
     }
     __syncthreads();
-    // ---- bases (As) and derivatives (registers) of the pairs (r, ii) = (p & 63, p >> 6)
+    // ---- bases (As) and derivatives (registers) of the thread's pairs
     float dsl[2], dbs[2][KAN_NB];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -843,7 +906,7 @@ __global__ __launch_bounds__(KB_THREADS) void kan_bwd_fused_kernel(const float* 
       dsl[h] = 0.f;
 #pragma unroll
       for (int c = 0; c < KAN_NB; ++c) dbs[h][c] = 0.f;
-      if (ii < ic) {
+      if (ii < ch.ic) {
         float b[KAN_NB], sl = 0.f;
 #pragma unroll
         for (int c = 0; c < KAN_NB; ++c) b[c] = 0.f;
@@ -854,17 +917,17 @@ __global__ __launch_bounds__(KB_THREADS) void kan_bwd_fused_kernel(const float* 
         }
         AD[ii * KF_CST + r] = sl;
 #pragma unroll
-        for (int c = 0; c < KAN_NB; ++c) AD[(ic + 8 * ii + c) * KF_CST + r] = b[c];
+        for (int c = 0; c < KAN_NB; ++c) AD[(ch.ic + 8 * ii + c) * KF_CST + r] = b[c];
       }
     }
-    for (int e = tid; e < (kpad - kc) * KF_R; e += KB_THREADS) AD[(kc + e / KF_R) * KF_CST + e % KF_R] = 0.f;
+    for (int e = tid; e < (ch.kpad - ch.kc) * KF_R; e += KB_THREADS) AD[(ch.kc + e / KF_R) * KF_CST + e % KF_R] = 0.f;
     __syncthreads();
     // ---- the next tile's loads go out under this tile's products
-    float4 nxv = xv, ngv0 = gv0, ngv1 = gv1;
+    float4 nxv = xv;
+    KfGRegs<KB_THREADS> ngv = {gv[0], gv[1]};
     if (vec && r0 + KF_R < re) {
       nxv = load_x(r0 + KF_R);
-      ngv0 = load_g(r0 + KF_R, 0);
-      ngv1 = load_g(r0 + KF_R, 1);
+      kf_g_load<KB_THREADS, true>(ngv, G, re, out, r0 + KF_R, 0);
     }
     // ---- dW chunk += G^T A over the tile's rows
     if ((KAN_ABL & 2) == 0)
@@ -872,18 +935,8 @@ __global__ __launch_bounds__(KB_THREADS) void kan_bwd_fused_kernel(const float* 
                        KF_R / 16, accw);
     __syncthreads();
     // ---- G rows [r][o] over G^T, then dA = G W_chunk
-    if (vec) {
-#pragma unroll
-      for (int q = 0; q < 2; ++q) {
-        const int idx = tid + KB_THREADS * q, r = idx & 63, o4 = idx >> 6;
-        *reinterpret_cast<float4*>(&GG[r * KF_CST + 4 * o4]) = q ? gv1 : gv0;
-      }
-    } else {
-      for (int e = tid; e < KF_R * KF_O; e += KB_THREADS) {
-        const int r = e / KF_O, o = e % KF_O;
-        GG[r * KF_CST + o] = (r0 + r < re && o < out) ? G[(r0 + r) * out + o] : 0.f;
-      }
-    }
+    if (vec) kf_g_store<KB_THREADS, true, false>(GG, gv);
+    else kf_g_scalar<KB_THREADS, false, false>(GG, G, re, out, r0, 0);
     __syncthreads();
     f32x4 accx[5];
 #pragma unroll
@@ -891,48 +944,14 @@ __global__ __launch_bounds__(KB_THREADS) void kan_bwd_fused_kernel(const float* 
     if ((KAN_ABL & 2) == 0)
       kf_mfma_groups_n(nj, &GG[(16 * wr + li) * KF_CST + 4 * lk], &Wt[(16 * j0 + li) * KF_CST + 4 * lk], 16 * KF_CST,
                        opad >> 4, accx);
-    // dA tile over As (last read by the dW products, before the barrier above); columns past kc
-    // hold products of zero-padded W rows and are never read
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-      if (j < nj)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) AD[(16 * wr + 4 * lk + q) * KF_DST + 16 * (j0 + j) + li] = accx[j][q];
-    __syncthreads();
-    // ---- Gin through the X tile
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int p = tid + KB_THREADS * h, r = p & 63, ii = p >> 6;
-      if (ii < ic && r0 + r < re) {
-        const float* dA = AD + r * KF_DST;
-        float v = dsl[h] * dA[ii];
-#pragma unroll
-        for (int c = 0; c < KAN_NB; ++c) v += dbs[h][c] * dA[ic + 8 * ii + c];
-        Xs[r][ii] = v;
-      }
-    }
-    __syncthreads();
-    for (int e = tid; e < KF_R * ic; e += KB_THREADS) {
-      const int r = e / ic, ii = e - r * ic;
-      if (r0 + r < re) Gin[(r0 + r) * in + i0 + ii] = Xs[r][ii];
-    }
+    // ---- dA over As (last read by the dW products, before the barrier above), Gin through the X tile
+    kf_da_to_gin<KB_THREADS, true>(AD, Xs, gk, accx, nj, 16 * wr + 4 * lk, 16 * j0 + li, re, r0, in, ch, dsl, dbs, Gin);
     xv = nxv;
-    gv0 = ngv0;
-    gv1 = ngv1;
+    gv[0] = ngv[0];
+    gv[1] = ngv[1];
     __syncthreads();  // Xs / GG / AD are refilled by the next tile
   }
-  float* out_slab = slab + (int64_t)z * out * K;
-#pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    const int kk = 16 * (j0 + j) + li;
-    if (j >= nj || kk >= kc) continue;
-    const int64_t col = kf_col(kk, ic, i0, in);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int o = 16 * wr + 4 * lk + q;
-      if (o < out) out_slab[(int64_t)o * K + col] = accw[j][q];
-    }
-  }
+  kf_store_slab(slab, z, accw, nj, 16 * j0 + li, 16 * wr + 4 * lk, ch, in, out);
 }
 
 // W[o][i] = base_w[o][i];  W[o][in + 8 i + c] = spline_w[o][i][c] * scaler[o][i]  (kan.py:145-151)
@@ -1092,8 +1111,6 @@ hipError_t kan_fwd_fused(const float* X, const float* grid, const float* W, int6
   return hipGetLastError();
 }
 
-int64_t kan_dw_slab_floats(int in, int out, int splits) { return (int64_t)splits * out * KAN_K1 * in; }
-
 hipError_t kan_head_fwd(const float* X, const float* grid, const float* W, int64_t N, int in, float* Y, hipStream_t s) {
   if (N <= 0 || in <= 0 || in > 64) return hipErrorInvalidValue;
   const int64_t blocks = (N + 3) / 4;
@@ -1119,24 +1136,35 @@ hipError_t kan_head_train(const float* X, const float* grid, const float* W, con
   return slab_reduce(slab, (int)blocks, (int64_t)KAN_K1 * in, dW, s);
 }
 
-// dW[o][k] = sum_n G[n][o] A[n][k]: `splits` row slices into slabs, then the fixed-order slab sum
-hipError_t kan_dw_fused(const float* X, const float* grid, const float* G, int64_t N, int in, int out,
-                        int64_t max_splits, float* slab, float* dW, hipStream_t s) {
-  if (N <= 0 || in <= 0 || out <= 0 || max_splits < 1) return hipErrorInvalidValue;
-  const int nchunk = (in + KF_IC - 1) / KF_IC, nout = (out + KF_O - 1) / KF_O;
-  // one round of resident blocks (2 per CU x 256 CUs): every CU busy, no tail
-  int64_t splits = kKanResidentBlocks / ((int64_t)nchunk * nout);
+// Row splits of a split-K backward kernel with `per` chunk tiles: one round of `resident` blocks
+// (every CU busy, no tail), at most max_splits, each a multiple of 64 rows; the grid pads the
+// splits to a multiple of 8 (kf_split_block).  blocks = 0: too many for a 1-D grid.
+struct KfSplitPlan {
+  int64_t rows_per_split;
+  int z;            // splits that hold rows = slabs written
+  unsigned blocks;
+};
+static KfSplitPlan kf_plan_splits(int64_t N, int64_t resident, int64_t per, int64_t max_splits) {
+  int64_t splits = resident / per;
   if (splits < 1) splits = 1;
   if (splits > max_splits) splits = max_splits;
   int64_t rps = (N + splits - 1) / splits;
   rps = (rps + KF_R - 1) / KF_R * KF_R;
   const int z = (int)((N + rps - 1) / rps);
-  const int64_t blocks = (int64_t)nchunk * nout * ((z + 7) / 8 * 8);
-  if (blocks > 0x7fffffff) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kan_dw_fused_kernel, dim3((unsigned)blocks), dim3(256), 0, s, X, grid, G, N, in, out, rps, nchunk,
-                     nout, z, slab);
-  const int64_t mn = (int64_t)out * KAN_K1 * in;
-  return slab_reduce(slab, z, mn, dW, s);
+  const int64_t blocks = per * ((z + 7) / 8 * 8);
+  return KfSplitPlan{rps, z, blocks > 0x7fffffff ? 0u : (unsigned)blocks};
+}
+
+// dW[o][k] = sum_n G[n][o] A[n][k]: `splits` row slices into slabs, then the fixed-order slab sum
+hipError_t kan_dw_fused(const float* X, const float* grid, const float* G, int64_t N, int in, int out,
+                        int64_t max_splits, float* slab, float* dW, hipStream_t s) {
+  if (N <= 0 || in <= 0 || out <= 0 || max_splits < 1) return hipErrorInvalidValue;
+  const int nchunk = (in + KF_IC - 1) / KF_IC, nout = (out + KF_O - 1) / KF_O;
+  const KfSplitPlan p = kf_plan_splits(N, kKanResidentBlocks, (int64_t)nchunk * nout, max_splits);
+  if (!p.blocks) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kan_dw_fused_kernel, dim3(p.blocks), dim3(256), 0, s, X, grid, G, N, in, out, p.rows_per_split,
+                     nchunk, nout, p.z, slab);
+  return slab_reduce(slab, p.z, (int64_t)out * KAN_K1 * in, dW, s);
 }
 
 hipError_t kan_dx_fused(const float* X, const float* grid, const float* Gout, const float* WT, int64_t N, int in,
@@ -1152,17 +1180,11 @@ hipError_t kan_bwd_fused(const float* X, const float* grid, const float* G, cons
                          int64_t max_splits, float* slab, float* dW, float* Gin, hipStream_t s) {
   if (N <= 0 || in <= 0 || out <= 0 || out > KF_O || max_splits < 1) return hipErrorInvalidValue;
   const int nchunk = (in + KF_IC - 1) / KF_IC;
-  int64_t splits = kKanBwdResidentBlocks / nchunk;  // one block per CU (LDS), one round
-  if (splits < 1) splits = 1;
-  if (splits > max_splits) splits = max_splits;
-  int64_t rps = (N + splits - 1) / splits;
-  rps = (rps + KF_R - 1) / KF_R * KF_R;
-  const int z = (int)((N + rps - 1) / rps);
-  const int64_t blocks = (int64_t)nchunk * ((z + 7) / 8 * 8);
-  if (blocks > 0x7fffffff) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kan_bwd_fused_kernel, dim3((unsigned)blocks), dim3(KB_THREADS), 0, s, X, grid, G, WT, N, in, out,
-                     rps, nchunk, z, slab, Gin);
-  return slab_reduce(slab, z, (int64_t)out * KAN_K1 * in, dW, s);
+  const KfSplitPlan p = kf_plan_splits(N, kKanBwdResidentBlocks, nchunk, max_splits);
+  if (!p.blocks) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kan_bwd_fused_kernel, dim3(p.blocks), dim3(KB_THREADS), 0, s, X, grid, G, WT, N, in, out,
+                     p.rows_per_split, nchunk, p.z, slab, Gin);
+  return slab_reduce(slab, p.z, (int64_t)out * KAN_K1 * in, dW, s);
 }
 
 hipError_t kan_combine(const float* base_w, const float* spline_w, const float* scaler, int out, int in, float* W,

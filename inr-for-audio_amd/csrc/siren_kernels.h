@@ -282,11 +282,12 @@ hipError_t spec_gather(int n, const SpecWs& w, float* g, hipStream_t s);        
 hipError_t loss_mix(const float* out, const float* y, int n, int rows, const SpecWs& w, int loss_mode, double alpha,
                     float gfac, float* g, hipStream_t s, int lo = 0);
 
-// KAN (kan.hip): fp32, grid_size 5, spline_order 3 (9 A-columns per input)
+// KAN (kan.hip): fp32, grid_size 5, spline_order 3
+constexpr int KAN_NB = 8;           // grid_size + spline_order bases per input
+constexpr int KAN_K1 = 1 + KAN_NB;  // A-columns per input feature: SiLU + the bases
 // fused layer kernels (the bases are recomputed in LDS; A and dA never reach HBM)
 hipError_t kan_fwd_fused(const float* X, const float* grid, const float* W, int64_t N, int in, int out, float* Y,
                          hipStream_t s);
-int64_t kan_dw_slab_floats(int in, int out, int splits);
 // split-K over the rows: at most max_splits slabs of out x 9 in floats
 hipError_t kan_dw_fused(const float* X, const float* grid, const float* G, int64_t N, int in, int out,
                         int64_t max_splits, float* slab, float* dW, hipStream_t s);
