@@ -281,3 +281,24 @@ def test_bench_dump_outputs_keeps_small_arrays_whole_and_samples_the_rest(tmp_pa
     assert a.size == 1000 and np.array_equal(a, b) and np.isin(a, eng.params[:n].numpy()).all()
     assert np.load(tmp_path / "a" / "grads.npy").size == 1000
     assert np.array_equal(np.load(tmp_path / "a" / "loss_history.npy"), np.arange(3, dtype=np.float32))
+
+
+def test_oracle_adam_is_torch_fused_cpu_adam():
+    """The reference of the GPU Adam test (tests/adam_ref.py: torch.optim.Adam(fused=True) on the CPU)
+    and oracle.adam_step are the same function on that test's input: 0 mismatching words in p, exp_avg
+    and exp_avg_sq over all five steps, on both ends (the edge lattice) of the 2^20 + 773 vector."""
+    import adam_ref
+    from oracle import siren_oracle as orc
+    p0, gs = adam_ref.adam_case(adam_ref.N_BIG)
+    half = 1 << 15
+    cut = lambda a: np.concatenate([a[:half], a[-(half + 5):]])  # noqa: E731
+    p0, gs = cut(p0), [cut(g) for g in gs]
+    assert p0.size == (1 << 16) + 5 and np.array_equal(gs[0][-16:], adam_ref.LATTICE[::-1])
+    ref = adam_ref.torch_fused_adam(p0, gs)
+    p, m, v = p0, np.zeros_like(p0), np.zeros_like(p0)
+    for step, g in enumerate(gs, 1):
+        with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+            p, m, v = orc.adam_step(p, g, m, v, step, adam_ref.lr_at(step))
+        for name, a, b in zip("pmv", (p, m, v), ref[step - 1]):
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (step, name)
+    assert np.isinf(v).sum() == 4 and not np.isnan(p).any()   # 3e20^2 (1 - beta2) summed past FLT_MAX
