@@ -46,13 +46,9 @@
 #define SIREN_SNAKE0_EB 2
 #endif
 
-// ping-pong NT kernels: the two-segment K-step (gemm_pipeline.h pingpong2_tiles, 4 barriers per K-step;
-// round 5: forward 2.269 -> 2.201 ms, fused last layer 2.401 -> 2.338, dX0 1.963 -> 1.924, dX 2.168 ->
-// 2.156, bit-identical; profiles/r18/ab_seg2.json); 0 = the four-phase K-step (pingpong_tiles)
-#ifndef SIREN_NT_SEG2
-#define SIREN_NT_SEG2 1
-#endif
-
+// The ping-pong NT kernels run the two-segment K-step (gemm_pipeline.h pingpong2_tiles, 4 barriers per K-step;
+// round 5 against the four-phase pingpong_tiles: forward 2.269 -> 2.201 ms, fused last layer 2.401 -> 2.338,
+// dX0 1.963 -> 1.924, dX 2.168 -> 2.156, bit-identical; profiles/r18/ab_seg2.json)
 #ifndef SIREN_NT_EARLY  // gemm_pipeline.h pingpong2_tiles EARLY for every mode (measurement; the fused
 #define SIREN_NT_EARLY 0  // last layer and dX0 always take it: dX0 -0.7% cfg2, -5.3% cfg4, dX +0.1% / +2.2%,
 #endif                    // profiles/r20/ab_early_dx.json)
@@ -60,11 +56,6 @@
 // within 0.2% (profiles/r19/ab_full_lines.json u26); 0 = plain stores
 #ifndef SIREN_NT_STNT
 #define SIREN_NT_STNT 1
-#endif
-// lines_out: 0 = each lane's MFMA-layout 8-B halves straight into the line scratch; 1 = paired into 16-B row
-// pieces by v_permlane16_swap first (round 5; measurement builds)
-#ifndef SIREN_LINES_SWAP
-#define SIREN_LINES_SWAP 0
 #endif
 
 #ifdef SIREN_DIAG
@@ -86,7 +77,7 @@ __device__ __forceinline__ int stage_swz(int r, int c) {
 template <int BM_, int BN_, int WM_, int WN_, int BK_, int S_, bool PP_ = false>
 struct NtCfg {
   static constexpr int BM = BM_, BN = BN_, BK = BK_, S = S_;
-  static constexpr bool PP = PP_;  // ping-pong K-loop (gemm_pipeline.h pingpong2_tiles / pingpong_tiles)
+  static constexpr bool PP = PP_;  // ping-pong K-loop (gemm_pipeline.h pingpong2_tiles)
   static constexpr int WM = WM_, WN = WN_, NWAVES = WM_ * WN_, THREADS = 64 * NWAVES;
   static constexpr int TM = BM / WM, TN = BN / WN;  // wave tile
   static constexpr int SM = TM / 16, SN = TN / 16;  // 16x16 MFMA tiles per wave
@@ -202,6 +193,889 @@ constexpr int epilogue_stores() {
                                                   : 0;
 }
 
+// ---- what an epilogue needs of its wave ------------------------------------------------
+// Set once per kernel; every epilogue and helper below takes it explicitly.
+//   acc[i][j][r] = out[m][n] with m = m0 + wm*TM + j*16 + (lane&15),
+//                                n = n0 + wn*TN + i*16 + 4*(lane>>4) + r.
+// Global traffic goes in 16-B row pieces: column subtiles (2p, 2p+1) are exchanged with
+// swap16_pair, this lane's piece starting at column ncol + 32p + swap16_col(lane).
+template <class Cfg_, int MODE_, bool HEAD_, bool ACTL_>
+struct NtWave {
+  using Cfg = Cfg_;
+  using Lay = NtLds<Cfg_, MODE_, HEAD_, ACTL_>;
+  static constexpr int MODE = MODE_;
+  static constexpr bool HEAD = HEAD_;
+  int tid, lane, wave, wm, wn;
+  // the row stride of every [M][*] operand and output (the layer's full width; the host offsets the pointers)
+  int LD;
+  // this lane's 16-B piece of a row piece (row lane & 15, columns swap16_col(lane) ..): byte offset in [*][LD] fp16
+  unsigned lane_piece;
+  int diag;  // measurement-only ablation bits (SIREN_DIAG builds)
+  // dZ carries the backward storage scale S; the fp32 column partials leave unscaled
+  float inv_scale;
+  // the fused last layer's S, 1/S and head bias, loaded once per kernel: loaded in the epilogue, each
+  // tile's phase 2 waited at vmcnt(0) for them, i.e. for the next tile's stages issued before it
+  float hb_S, hb_invS, hb_bias;
+
+  // the LDS regions of NtLds, as pointers the kernel computes once: handed down as the block's base alone
+  // (each region's offset added at its use), the dX kernels' scratch stores lost their immediate offsets --
+  // 4-8 VGPRs more, NT_DX0 and NT_DX0_SNAKE spilled (gfx950 listing)
+  char* smem;       // the block's LDS: the line scratch (Lay::ST, Lay::DM) is addressed from it
+  float* red;       // epilogue reduction scratch (Cfg::RING)
+  float* bias_lds;  // bias (x omega / 2 pi for the sine kinds), head weights
+  float* hw_lds;
+  float* a_lds;     // Snake: a
+  float* ia_lds;    // Snake: 1/a (the same IEEE quotient the epilogue used per element)
+  // a wave-uniform row base (SGPRs) for at_lane
+  __device__ __forceinline__ const char* rowp(const h16* base, int row_u, int col_u) const {
+    return (const char*)(base + (size_t)row_u * LD + col_u);
+  }
+};
+
+// Row-piece accesses of the epilogues: a wave-uniform row base (SGPRs) plus a 32-bit lane byte offset kept
+// 32-bit at the access by an opaque copy, so that hipcc emits the saddr form (one SGPR pair, one VGPR)
+// instead of per-lane 64-bit address arithmetic (v_mad_i64_i32, v_lshl_add_u64: lines_out)
+__device__ __forceinline__ char* at_lane(const void* ub, unsigned lo) {
+  asm("" : "+v"(lo));
+  return (char*)ub + lo;
+}
+__device__ __forceinline__ void st16(h16* dst, uint4 v) { *(uint4*)dst = v; }
+// the whole-line stores (plain forward, dX): non-temporal (SIREN_NT_STNT)
+__device__ __forceinline__ void stl(h16* dst, uint4 v) {
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+  if constexpr (SIREN_NT_STNT != 0) __builtin_nontemporal_store(__builtin_bit_cast(u32x4, v), (u32x4*)dst);
+  else *(uint4*)dst = v;
+}
+
+// ---- whole-line stores ------------------------------------------------------------------
+// Whole 128-B lines per store (Lay::LINES): the wave's 16-row x 64-column fp16 piece of one
+// output (lane: row lane & 15, 16-B chunks 4 pp + swap16_col(lane) / 8) goes through its 2-KiB LDS
+// scratch, 16-B chunks XOR-swizzled by row (conflict-free both ways), and each store writes rows
+// 8q .. 8q+7 as 8 lanes x 16 B per row.  Same bytes and store count as 16 rows x 64 B, but no
+// half-line writes.  Same-wave LDS accesses complete in order, so the reads see this
+// wave's writes and the next output's writes follow the reads.  row = the piece's first row and
+// col = the wave's first column, both wave-uniform: each store is then a wave-uniform 64-bit base in
+// SGPRs plus a 32-bit lane offset that is the same for every piece (the saddr form), where per-lane
+// 64-bit addresses cost 10 64-bit VALU per row piece (v_mad_i64_i32, v_lshl_add_u64; gfx950 listing)
+// v[i]: this lane's 4 columns of column subtile i in the MFMA layout (row lane & 15, columns 16 i + 4 g ..
+// + 3, g = lane >> 4), packed fp16: 8 B at byte 32 i + 8 g of the row's line.  Each goes into the scratch as
+// one 8-B half of its swizzled 16-B chunk 2 i + (g >> 1) (pairing them into 16-B row pieces across 16-lane
+// groups by v_permlane16_swap first, as round 5 did, cost 4 VALU per row piece more).
+// lines_get exchanges one row piece through the wave's scratch into this lane's two 16-B line chunks,
+// lines_put stores them.
+template <class W>
+__device__ __forceinline__ void lines_get(const W& w, const uint2 (&v)[W::Cfg::SN], uint4 (&line)[2]) {
+  static_assert(W::Cfg::SN == 4, "a wave's row piece is one 128-B line");
+  const int pr = w.lane & 15;               // this lane's piece: row
+  const int g = w.lane >> 4;                // MFMA layout: 16-lane group
+  const int qr = w.lane >> 3, qc = w.lane & 7;  // line layout: row (+ 8 q), chunk
+  char* sc = w.smem + W::Lay::ST + w.wave * 2048;
+#pragma unroll
+  for (int i = 0; i < W::Cfg::SN; ++i) {
+    const int c = 2 * i + (g >> 1);
+    *(uint2*)(sc + pr * 128 + ((c ^ (pr & 7)) << 4) + ((g & 1) << 3)) = v[i];
+  }
+  __builtin_amdgcn_wave_barrier();  // cross-lane exchange: the reads stay after every lane's writes
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int r = qr + 8 * q;
+    line[q] = *(const uint4*)(sc + r * 128 + ((qc ^ (r & 7)) << 4));
+  }
+  __builtin_amdgcn_wave_barrier();  // ... and the next output's writes after these reads
+}
+template <class W>
+__device__ __forceinline__ void lines_put(const W& w, h16* out, int row, int col, const uint4 (&line)[2]) {
+  const int qr = w.lane >> 3, qc = w.lane & 7;
+  const char* ub = (const char*)(out + (size_t)row * w.LD + col);
+  unsigned lo = (unsigned)((qr * w.LD + qc * 8) * 2);
+  asm("" : "+v"(lo));  // kept 32-bit at the stores (a hoisted 64-bit zext defeats the saddr form)
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    unsigned lq = lo;
+    asm("" : "+v"(lq));  // one opaque copy per store: no store's address is derived from another's
+    stl((h16*)(ub + (size_t)(16 * q) * w.LD + lq), line[q]);
+  }
+}
+// One row piece out at once: lines_get + lines_put, or (Lay::HALF, the Snake forward: no 16 KiB left) two
+// 8-row passes through 1 KiB per wave in the RED region
+template <class W>
+__device__ __forceinline__ void lines_out(const W& w, h16* out, int row, int col, const uint2 (&v)[W::Cfg::SN]) {
+  using Cfg = typename W::Cfg;
+  static_assert(Cfg::SN == 4, "a wave's row piece is one 128-B line");
+  if constexpr (W::Lay::HALF) {
+    const int pr = w.lane & 15, g = w.lane >> 4;
+    const int qr = w.lane >> 3, qc = w.lane & 7;
+    const char* ub = (const char*)(out + (size_t)row * w.LD + col);
+    unsigned lo = (unsigned)((qr * w.LD + qc * 8) * 2);
+    asm("" : "+v"(lo));  // kept 32-bit at the stores (a hoisted 64-bit zext defeats the saddr form)
+    // rows 8h .. 8h+7 per pass.  No lane may skip a pass's write: the compiler treats the scratch
+    // per lane, and a write under a divergent branch was moved past the other lanes' reads (wrong
+    // rows, gfx950 listing; a DPP exchange that avoids it spilled).  So every lane writes both its
+    // chunks in both passes, those of the other pass's rows to slots nobody reads (Lay::DM,
+    // shared by the block's waves: garbage by design).
+    char* sh = w.smem + Cfg::RING + w.wave * 1024;
+    char* dm = w.smem + W::Lay::DM + w.lane * 32;
+    const int r8 = pr & 7;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const bool mine = (pr >> 3) == h;
+#pragma unroll
+      for (int i = 0; i < Cfg::SN; ++i) {
+        const int c = 2 * i + (g >> 1);
+        *(uint2*)(mine ? sh + r8 * 128 + ((c ^ r8) << 4) + ((g & 1) << 3) : dm + i * 8) = v[i];
+      }
+      // the exchange is across lanes: no LDS access moves over these (LDS is in order within a
+      // wave, so they cost no wait; the ordering no longer rests on how the select is written)
+      __builtin_amdgcn_wave_barrier();
+      const uint4 line = *(const uint4*)(sh + qr * 128 + ((qc ^ qr) << 4));
+      __builtin_amdgcn_wave_barrier();
+      unsigned lh = lo;
+      asm("" : "+v"(lh));  // one opaque copy per store: no store's address is derived from another's
+      stl((h16*)(ub + (size_t)(16 * h) * w.LD + lh), line);
+    }
+  } else {
+    uint4 line[2];
+    lines_get(w, v, line);
+    lines_put(w, out, row, col, line);
+  }
+}
+// One output's row piece for lines_row_apart: where it goes, its MFMA-layout halves, its line chunks in flight
+template <int SN>
+struct LineRow {
+  h16* out;
+  const uint2 (&v)[SN];
+  uint4 (&line)[2];
+};
+// The outputs of row subtile j a row apart: row j-1's stores after row j's arithmetic, row j's exchange now
+// (a row's LDS round trip completes under the next row's arithmetic), the last row's stores at once
+template <class W, class... Rows>
+__device__ __forceinline__ void lines_row_apart(const W& w, int row0, int col, int j, Rows&&... o) {
+  if (j > 0) (lines_put(w, o.out, row0 + (j - 1) * 16, col, o.line), ...);
+  (lines_get(w, o.v, o.line), ...);
+  if (j == W::Cfg::SM - 1) (lines_put(w, o.out, row0 + j * 16, col, o.line), ...);
+}
+
+// ---- arithmetic shared by the epilogues ---------------------------------------------------
+constexpr bool nt_is_sine_fwd(int m) { return m == NT_FWD || m == NT_FWD_HB; }
+
+// The activation outputs of one 16x16 subtile from its accumulators a (this lane's 4 columns of one row):
+// s = Y in fp32 (the head partial sums it) and Y, C (, Snake: E) rounded to fp16 as they are stored.  One
+// definition for the plain forwards and phase 1 of the fused last layer, whose head partials and dZ_L are
+// therefore those of the unfused launches.  b: the bias (x xs for sine), a_col / ia_col: the subtile's
+// Snake a and 1/a in LDS (read by the Snake kinds only).
+template <int MODE>
+__device__ __forceinline__ void act_subtile(const f32x4& a, float xs, const float4& b, const float* a_col,
+                                            const float* ia_col, float (&s)[4], uint2& y, uint2& c, uint2& e) {
+  const float bb[4] = {b.x, b.y, b.z, b.w};
+  float cv[4], ev[4];
+  if constexpr (nt_is_sine_fwd(MODE)) {
+    // revolutions: sin(2*pi*x) with x = omega*(z + b)/(2*pi) (packed fmas); fract keeps
+    // the hardware sin/cos inside their reduced domain for any magnitude.
+    float xa[4];
+    fma4_pk(a, xs, b, xa);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float x = __builtin_amdgcn_fractf(xa[r]);
+      s[r] = __builtin_amdgcn_sinf(x);
+      cv[r] = __builtin_amdgcn_cosf(x);
+    }
+  } else if constexpr (nt_is_snake_fwd(MODE)) {
+    const float4 a4 = *(const float4*)a_col;
+    const float4 ia4 = *(const float4*)ia_col;
+    const float av[4] = {a4.x, a4.y, a4.z, a4.w}, iav[4] = {ia4.x, ia4.y, ia4.z, ia4.w};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      snake_epi(a[r] + bb[r], av[r], iav[r], s[r], cv[r], ev[r]);
+    }
+  } else {  // Tanh
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float yv = tanh_epi(a[r] + bb[r]);
+      s[r] = yv;
+      cv[r] = 1.0f - yv * yv;
+    }
+  }
+  y = as_u2(pack4(s[0], s[1], s[2], s[3]));
+  c = as_u2(pack4(cv[0], cv[1], cv[2], cv[3]));
+  if constexpr (nt_is_snake_fwd(MODE)) e = as_u2(pack4(ev[0], ev[1], ev[2], ev[3]));
+}
+
+// The head partial of the tile's rows over this column tile, hp[j] = this lane's part of row subtile j:
+// lanes l, l^16, l^32, l^48 hold the same row: fold them, then red[wn][row] for the WN column waves ...
+template <class W>
+__device__ __forceinline__ void head_fold(const W& w, float (&hp)[W::Cfg::SM]) {
+  using Cfg = typename W::Cfg;
+#pragma unroll
+  for (int j = 0; j < Cfg::SM; ++j) {
+    hp[j] += __shfl_xor(hp[j], 16, 64);
+    hp[j] += __shfl_xor(hp[j], 32, 64);
+  }
+  if (w.lane < 16) {
+#pragma unroll
+    for (int j = 0; j < Cfg::SM; ++j) w.red[w.wn * Cfg::BM + w.wm * Cfg::TM + j * 16 + w.lane] = hp[j];
+  }
+  lds_barrier();
+}
+// ... whose sum, in wave order, is the partial of tile row `row` (after head_fold)
+template <class W>
+__device__ __forceinline__ float head_rowsum(const W& w, int row) {
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < W::Cfg::WN; ++k) s += w.red[k * W::Cfg::BM + row];
+  return s;
+}
+
+// Column sums over the tile's BM rows (db / dW0 / da / dw_head partials): per lane over its SM row tiles
+// (the caller), over the 16 row lanes by DPP into partial row q of the LDS scratch (colsum_flush: column
+// subtile i of this wave's rows), then over the WM row waves (colsum_store)
+template <class W>
+__device__ __forceinline__ void colsum_flush(const W& w, int q, int i, const float (&part)[4]) {
+  using Cfg = typename W::Cfg;
+  float v[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = part[r];
+  row16_sum4(v);
+  if ((w.lane & 15) == 0)
+    *(float4*)(w.red + (q * Cfg::WM + w.wm) * Cfg::BN + w.wn * Cfg::TN + i * 16 + 4 * (w.lane >> 4)) =
+        float4{v[0], v[1], v[2], v[3]};
+}
+// partial layout [tm][nrows][N], each sum x scale on its way out (1/S: sums of x S are exact)
+template <class W>
+__device__ __forceinline__ void colsum_store(const W& w, const NtParams& p, int tm, int n0, int nrows, float scale) {
+  using Cfg = typename W::Cfg;
+  lds_barrier();
+  if (w.tid < Cfg::BN) {
+    for (int q = 0; q < nrows; ++q) {
+      float s = 0.f;
+#pragma unroll
+      for (int k = 0; k < Cfg::WM; ++k) s += w.red[(q * Cfg::WM + k) * Cfg::BN + w.tid];
+      p.colsum_part[((size_t)tm * nrows + q) * w.LD + n0 + w.tid] = s * scale;
+    }
+  }
+}
+
+// dZ of one 16x16 subtile (column subtile i) from its accumulators a and its half cph of the Cprev piece,
+// packed fp16, with the column partials it feeds: cs[0] db, cs[1..2] dW0 (t0, t1: NT_DX0*), cs[1] / cs[3] da
+// from the Eprev half eph (NT_DX_SNAKE / NT_DX0_SNAKE).  (acc C) omega: the fp16 product in v_fma_mix_f32,
+// the rest in pairs (v_pk_mul_f32, v_pk_add_f32, v_pk_fma_f32: per element the rounding of the scalar
+// instruction)
+template <int MODE, int SN>
+__device__ __forceinline__ uint2 dz_subtile(const f32x4& a, uint2 cph, uint2 eph, float om, float t0, float t1,
+                                            float (&cs)[4][SN][4], int i) {
+  f32x2 d01 = f32x2{mul_mix<0>(a[0], cph), mul_mix<1>(a[1], cph)} * f32x2{om, om};
+  f32x2 d23 = f32x2{mul_mix<2>(a[2], cph), mul_mix<3>(a[3], cph)} * f32x2{om, om};
+  asm volatile("" : "+v"(d01), "+v"(d23));  // rounded to fp32 before the fp16 store (fp32_first)
+  set4(cs[0][i], f32x2{cs[0][i][0], cs[0][i][1]} + d01, f32x2{cs[0][i][2], cs[0][i][3]} + d23);
+  if constexpr (nt_is_dx0(MODE)) {
+    set4(cs[1][i], __builtin_elementwise_fma(d01, f32x2{t0, t0}, f32x2{cs[1][i][0], cs[1][i][1]}),
+         __builtin_elementwise_fma(d23, f32x2{t0, t0}, f32x2{cs[1][i][2], cs[1][i][3]}));
+    set4(cs[2][i], __builtin_elementwise_fma(d01, f32x2{t1, t1}, f32x2{cs[2][i][0], cs[2][i][1]}),
+         __builtin_elementwise_fma(d23, f32x2{t1, t1}, f32x2{cs[2][i][2], cs[2][i][3]}));
+  }
+  static_for<0, 4>([&](auto rc) {
+    constexpr int r = decltype(rc)::value;
+    if constexpr (MODE == NT_DX_SNAKE) cs[1][i][r] = fma_mix<r>(a[r], eph, cs[1][i][r]);
+    if constexpr (MODE == NT_DX0_SNAKE) cs[3][i][r] = fma_mix<r>(a[r], eph, cs[3][i][r]);
+  });
+  return as_u2(pack4(d01.x, d01.y, d23.x, d23.y));
+}
+
+// ---- epilogues (per tile) -------------------------------------------------------------
+// NT_DX / NT_DX0 epilogue operands loaded by nt_pre (before the next tile's early prefetch).  The
+// rest are loaded by the epilogue in one batch once earlier pieces are consumed (their
+// accumulators free the registers), so a batch waits once, not once per piece behind the
+// in-order vmcnt (which also covers the next tile's stages and this tile's stores).  NT_DX and
+// NT_DX0 preload every row (NT_DX0 has room for it since its products use v_fma_mix and its
+// row sums v_add_f32_dpp: 229 VGPRs, against 235 with half the rows before).  The Snake modes
+// (Cprev AND Eprev per piece) go in batches of EB rows with both column pairs of a row
+// together: nt_pre loads pair 0 of the first batch, and each batch loads the next one before
+// its own dZ stores.
+template <class Cfg, int MODE>
+struct NtPre {
+  static constexpr bool HAS_E = (MODE == NT_DX_SNAKE || MODE == NT_DX0_SNAKE);
+  static constexpr int PRE_J = (nt_is_fwd(MODE) || HAS_E) ? 0 : Cfg::SM;
+  // Snake modes: EB = 2 rows per batch, two batches in flight (gfx950 listing: 238 / 247 VGPRs
+  // for NT_DX_SNAKE / NT_DX0_SNAKE, no spills; 4 rows spill 164-196 B): dX Snake 2.559 -> 2.530 ms
+  // against 4-row batches loaded at use (profiles/r16c/ab_snake_dx_pipelined.json)
+  static constexpr int EB0 = (MODE == NT_DX0_SNAKE) ? SIREN_SNAKE0_EB : SIREN_SNAKE_EB;
+  static constexpr int EB = EB0 < Cfg::SM ? EB0 : Cfg::SM;
+  static_assert(Cfg::SM % EB == 0, "Snake epilogue batches");
+  uint4 cp_in[PRE_J > 0 ? PRE_J : 1][Cfg::SN / 2];
+  uint4 ce_in[HAS_E ? EB : 1][2];
+  float t_in[Cfg::SM][2];
+};
+
+template <class W>
+__device__ __forceinline__ void nt_pre(int m0, int n0, const W& w, const NtParams& p,
+                                       NtPre<typename W::Cfg, W::MODE>& in) {
+  using Cfg = typename W::Cfg;
+  using Pre = NtPre<Cfg, W::MODE>;
+  constexpr int MODE = W::MODE, SM = Cfg::SM, SN = Cfg::SN;
+  const int mrowu = m0 + w.wm * Cfg::TM, ncu = n0 + w.wn * Cfg::TN;  // the wave's first row and column (wave-uniform)
+  if constexpr (!nt_is_fwd(MODE)) {
+#pragma unroll
+    for (int j = 0; j < Pre::PRE_J; ++j)
+#pragma unroll
+      for (int pp = 0; pp < SN / 2; ++pp)
+        in.cp_in[j][pp] = *(const uint4*)at_lane(w.rowp(p.Cprev, mrowu + j * 16, ncu), w.lane_piece + pp * 64);
+    if constexpr (Pre::HAS_E) {
+#pragma unroll
+      for (int j = 0; j < Pre::EB; ++j) {
+        in.ce_in[j][0] = *(const uint4*)at_lane(w.rowp(p.Cprev, mrowu + j * 16, ncu), w.lane_piece);
+        in.ce_in[j][1] = *(const uint4*)at_lane(w.rowp(p.Eprev, mrowu + j * 16, ncu), w.lane_piece);
+      }
+    }
+    if constexpr (nt_is_dx0(MODE)) {
+#pragma unroll
+      for (int j = 0; j < SM; ++j) {
+        const float* tb = p.t + (size_t)(mrowu + j * 16) * p.in_dim;
+        const unsigned lt = (unsigned)((w.lane & 15) * p.in_dim * 4);
+        in.t_in[j][0] = *(const float*)at_lane(tb, lt);
+        // no branch around the second coordinate's load (in_dim 1 reads the first again; nt_epi_dx takes 0
+        // for it): as "in_dim > 1 ? load : 0" through NtPre, half the rows' loads were followed by
+        // s_waitcnt vmcnt(0) and a copy, behind the Cprev pieces and the K-loop's stages (gfx950 listing;
+        // dX0 at in_dim 2, 220160 x 512: 0.1545 -> 0.1676 ms)
+        in.t_in[j][1] = *(const float*)at_lane(tb, lt + (p.in_dim > 1 ? 4u : 0u));
+      }
+    }
+  }
+}
+
+// The forward family: NT_FWD, NT_FWD_SNAKE, NT_FWD_TANH, with or without the HEAD partial
+template <class W>
+__device__ __forceinline__ void nt_epi_fwd(f32x4 (&acc)[W::Cfg::SN][W::Cfg::SM], int m0, int n0, const W& w,
+                                           const NtParams& p) {
+  using Cfg = typename W::Cfg;
+  using Lay = typename W::Lay;
+  constexpr int MODE = W::MODE, TM = Cfg::TM, TN = Cfg::TN, SM = Cfg::SM, SN = Cfg::SN;
+  constexpr bool HEAD = W::HEAD;
+  const int lane = w.lane, LD = w.LD;
+  const int tn = n0 / Cfg::BN;
+  const int ncu = n0 + w.wn * TN;                // the wave's first column (wave-uniform)
+  const int npc = ncu + swap16_col(lane);        // swapped layout: this lane's piece
+  const int mrowu = m0 + w.wm * TM;              // the wave's first row (wave-uniform)
+  const int mrow0 = mrowu + (lane & 15);
+  const int nq = ncu + 4 * (lane >> 4);          // natural layout: this lane's columns
+  const float xs = (MODE == NT_FWD) ? p.omega * kInv2Pi : 1.0f;
+  // bias / head weights through LDS -- the epilogue then issues no global load whose
+  // compiler-counted vmcnt wait would also cover the asm-issued stage prefetch.
+  float4 bias[SN], hw[SN];  // (bias_lds holds b * xs)
+#pragma unroll
+  for (int i = 0; i < SN; ++i) {
+    bias[i] = *(const float4*)(w.bias_lds + nq + i * 16);
+    if constexpr (HEAD) hw[i] = *(const float4*)(w.hw_lds + nq + i * 16);
+  }
+  float hp[SM];
+#pragma unroll
+  for (int j = 0; j < SM; ++j) hp[j] = 0.f;
+  uint4 ly[2], lc[2];  // NT_FWD: row j-1's Y / C line chunks, stored after row j's arithmetic
+#pragma unroll
+  for (int j = 0; j < SM; ++j) {
+    const size_t rowoff = (size_t)(mrow0 + j * 16) * LD;
+    uint4 yp[SN / 2], cpk[SN / 2], epk[SN / 2];  // 16-B row pieces (the per-lane stores)
+    uint2 yh[SN], chh[SN], eh[SN];                // MFMA-layout halves (lines_out)
+#pragma unroll
+    for (int q = 0; q < SN / 2; ++q) {
+      // ping-pong tiles: the lower row half takes its column pairs in reverse, the order of
+      // the K-loop's serpentine phases (a: pair 0 / rows 0-3, b: 1 / 0-3, c: 1 / 4-7, d: 0 /
+      // 4-7) -- the head partial sums keep that summation order
+      const int pp = (Cfg::PP && j >= SM / 2) ? SN / 2 - 1 - q : q;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int i = 2 * pp + h;
+        float s[4];
+        act_subtile<MODE>(acc[i][j], xs, bias[i], w.a_lds + nq + i * 16, w.ia_lds + nq + i * 16, s, yh[i], chh[i],
+                          eh[i]);
+        if constexpr (HEAD) hp[j] += dot4_pk(s, hw[i]);
+        // opaque (Snake with the head partial, at the 256-VGPR limit): Y is packed here, once the head
+        // partial has taken its fp32 form -- left to itself the compiler keeps fp32 Y live beside the three
+        // packed outputs and spills (28-44 B per lane against the 0-20 B of the lambda form; with the pin
+        // 228-232 VGPRs and no scratch, gfx950 listing)
+        if constexpr (HEAD && MODE == NT_FWD_SNAKE) asm volatile("" : "+v"(yh[i].x), "+v"(yh[i].y));
+      }
+      if constexpr (!(Lay::LINES || Lay::HALF)) {
+        yp[pp] = swap16_pair(yh[2 * pp], yh[2 * pp + 1]);
+        cpk[pp] = swap16_pair(chh[2 * pp], chh[2 * pp + 1]);
+        if constexpr (MODE == NT_FWD_SNAKE) epk[pp] = swap16_pair(eh[2 * pp], eh[2 * pp + 1]);
+      }
+    }
+    if (SIREN_DIAG_ON && (w.diag & 2048)) {  // diag bit 11: the epilogue without its stores (timing only)
+      unsigned keep = 0;
+#pragma unroll
+      for (int i = 0; i < SN; ++i) keep ^= yh[i].x ^ yh[i].y ^ chh[i].x ^ chh[i].y;
+      asm volatile("" ::"v"(keep));
+      continue;
+    }
+    if constexpr (Lay::LINES && MODE == NT_FWD && !HEAD) {
+      // a row's LDS round trip completes under the next row's sin / cos
+      lines_row_apart(w, mrowu, ncu, j, LineRow<SN>{p.Y, yh, ly}, LineRow<SN>{p.C, chh, lc});
+      continue;
+    }
+    if constexpr (Lay::LINES || Lay::HALF) {
+      // whole-line stores (lines_out): forward -4.6%, cfg4 -6.5% (static walk,
+      // profiles/r19/ab_full_lines.json)
+      lines_out(w, p.Y, mrowu + j * 16, ncu, yh);
+      lines_out(w, p.C, mrowu + j * 16, ncu, chh);
+      if constexpr (MODE == NT_FWD_SNAKE) lines_out(w, p.E, mrowu + j * 16, ncu, eh);
+      continue;
+    }
+#pragma unroll
+    for (int pp = 0; pp < SN / 2; ++pp) {
+      // (per-lane addresses here: the head forward has no registers for at_lane's copies -- Snake spilled)
+      st16(p.Y + rowoff + npc + pp * 32, yp[pp]);
+      st16(p.C + rowoff + npc + pp * 32, cpk[pp]);
+      if constexpr (MODE == NT_FWD_SNAKE) st16(p.E + rowoff + npc + pp * 32, epk[pp]);
+    }
+  }
+  if constexpr (HEAD) {
+    head_fold(w, hp);
+    if (w.tid < Cfg::BM) p.head_part[(size_t)tn * p.M + m0 + w.tid] = head_rowsum(w, w.tid);
+  }
+}
+
+// The last hidden layer fused with the head, the loss gradient and the head backward, for
+// the three last-layer kinds NT_FWD_HB, NT_FWD_HB_SNAKE, NT_FWD_HB_TANH (SURVEY §8 a6/a8/a9 and f3;
+// models.py:114-115, 235-241, 366-372).
+template <class W>
+__device__ __forceinline__ void nt_epi_hb(f32x4 (&acc)[W::Cfg::SN][W::Cfg::SM], int m0, int n0, const W& w,
+                                          const NtParams& p) {
+  using Cfg = typename W::Cfg;
+  using Lay = typename W::Lay;
+  constexpr int MODE = W::MODE, BM = Cfg::BM, BN = Cfg::BN, TM = Cfg::TM, TN = Cfg::TN, SM = Cfg::SM, SN = Cfg::SN;
+  const int tid = w.tid, lane = w.lane, wm = w.wm;
+  const int tm = m0 / BM, tn = n0 / BN;
+  const int tiles_n = p.N / BN;
+  const int mrowu = m0 + wm * TM, ncu = n0 + w.wn * TN;  // the wave's first row and column (wave-uniform)
+  float* red = w.red;
+  const float* hw_lds = w.hw_lds;
+  // ---- phase 1: the layer's outputs for the head partial of the band's rows over this column
+  // tile, summed exactly as NT_FWD(_SNAKE/_TANH) + HEAD sums them (act_subtile, head_fold).  Sine / Tanh:
+  // Y and C (= cos, or 1 - Y^2) rounded to fp16 as the unfused forward stores them, packed IN PLACE of their
+  // accumulators (4 fp32 -> 4 + 4 fp16: the same 4 VGPRs, so nothing more is live across the
+  // hand-off than the accumulators).  Snake has three fp16 outputs (Y, D, E): Y and D go in
+  // place of the accumulators, E to the layer's E buffer, read back during phase 2.
+  constexpr bool SNK = MODE == NT_FWD_HB_SNAKE;
+  const int nq = ncu + 4 * (lane >> 4);
+  const float xs = (MODE == NT_FWD_HB) ? p.omega * kInv2Pi : 1.0f;
+  float4 bias[SN], hw[SN];  // (bias_lds holds b * xs)
+#pragma unroll
+  for (int i = 0; i < SN; ++i) {
+    bias[i] = *(const float4*)(w.bias_lds + nq + i * 16);
+    hw[i] = *(const float4*)(hw_lds + nq + i * 16);
+  }
+  float hp[SM];
+  uint2 epair[2];  // Snake: fp16 E of one row piece's two column subtiles
+#pragma unroll
+  for (int j = 0; j < SM; ++j) {
+    hp[j] = 0.f;
+#pragma unroll
+    for (int q = 0; q < SN / 2; ++q) {
+      const int pp = (Cfg::PP && j >= SM / 2) ? SN / 2 - 1 - q : q;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int i = 2 * pp + h;
+        float sv[4];
+        uint2 yv, cw;
+        act_subtile<MODE>(acc[i][j], xs, bias[i], w.a_lds + nq + i * 16, w.ia_lds + nq + i * 16, sv, yv, cw,
+                          epair[h]);
+        // Snake: Y and D packed in place of the accumulators; E goes to HBM (p.E, the layer's E
+        // buffer) in 16-B row pieces once both subtiles of the pair have it, and phase 3 reads
+        // it back (held in registers, 64 more VGPRs across the hand-off spilled 400 B per lane)
+        acc[i][j] = __builtin_bit_cast(f32x4, uint4{yv.x, yv.y, cw.x, cw.y});
+        // opaque: the packing happens here (left to itself the compiler sinks the cos past the
+        // hand-off into phase 2, keeping the fp32 arguments live across it: 372 B of spills)
+        asm volatile("" : "+v"(acc[i][j]));
+        hp[j] += dot4_pk(sv, hw[i]);
+      }
+      if constexpr (SNK)
+        st16((h16*)at_lane(w.rowp(p.E, mrowu + j * 16, ncu), w.lane_piece + pp * 64), swap16_pair(epair[0], epair[1]));
+    }
+  }
+  head_fold(w, hp);
+  // ---- the band hand-off: publish this column tile's partial of each row, take the other
+  // column tiles' partials as their blocks publish them (the band's tiles_n tiles run in
+  // lockstep on tiles_n consecutive blocks of one XCD; DESIGN §4 "fused head backward"), then
+  // head_loss for the band's rows.  The partial itself is the flag: head_part is filled with
+  // kHeadPending before the launch and a published value is never that pattern (NaN is
+  // stored canonical), so no fence orders it -- one agent-scope atomic word each way.
+  // g_lds sits past the column-partial scratch of phase 2 (3 partial rows with Snake)
+  float* g_lds = red + (SNK ? 3 * Cfg::WM * BN : Cfg::WN * BM);
+  float e2 = 0.f, gv = 0.f;
+  if (tid < BM) {
+    const float own = head_rowsum(w, tid);
+    const int m = m0 + tid;
+    unsigned* hpu = (unsigned*)p.head_part;
+    // SIREN_OPT_HB_FAULT bit 0 (SIREN_DIAG builds): column tile 1 never publishes (test hook)
+    if (!(SIREN_DIAG_ON && (p.hb_fault & 1) && tn == 1))
+      __hip_atomic_store(hpu + (size_t)tn * p.M + m, own == own ? __float_as_uint(own) : 0x7fc00000u,
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the row's target, loaded before the partners are polled: its latency runs under the polls (loaded
+    // after them, the block waited one more memory round trip per tile)
+    // (unconditional, the row clamped into [0, n_valid), and retired unconditionally below: a load or a use
+    // under `m < n_valid` left the register's reuse in phase 2 behind a vmcnt(0), i.e. behind the dZ_L stores)
+    // (the empty asm keeps hipcc from hoisting the now always-valid load above `tid < BM`, into the waves
+    // that never consume it)
+    asm volatile("" ::: "memory");
+    const float tgt = p.target[min(m, p.n_valid > 0 ? p.n_valid - 1 : 0)];
+    float o = 0.f;  // head_loss_kernel's order: partials j = 0, 1, ..., then the bias
+    for (int jt = 0; jt < tiles_n; ++jt) {
+      float v = own;
+      if (jt != tn) {
+        unsigned u;
+        int polls = 0;
+        while ((u = __hip_atomic_load(hpu + (size_t)jt * p.M + m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) ==
+               kHeadPending) {
+          // bounded: a partner kept off the chip (CUs held by another process) voids the step
+          // instead of hanging the launch -- the band's partial becomes NaN and the wait is
+          // counted in the guard's stall word, which makes the update skip the step and the
+          // engine raise (a NaN alone would pass guard_skip and reach the weights)
+          if (++polls > p.spin_limit) {
+            u = 0x7fc00000u;
+            if (p.stall) __hip_atomic_fetch_add(p.stall, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+          }
+          // fail fast: once any wait of this step (this launch or an earlier micro-batch's) has given
+          // up, the step is void already -- every other wait stops within kStallCheck polls instead
+          // of spending its own whole limit (the stall word is sticky until the host clears it)
+          if ((polls & (kStallCheck - 1)) == 0 && p.stall &&
+              __hip_atomic_load(p.stall, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+            u = 0x7fc00000u;
+            break;
+          }
+          __builtin_amdgcn_s_sleep(1);
+        }
+        v = __uint_as_float(u);
+      }
+      o += v;
+    }
+    o += w.hb_bias;
+    const float a = p.head_omega * o;
+    const float ov = p.head_omega > 0.f ? sinf(a) : o;
+    asm volatile("" ::"v"(tgt));  // consumed here on every path (the use below is under m < n_valid)
+    if (m < p.n_valid) {
+      const float err = ov - tgt;
+      if (p.loss_mode == 1) {
+        e2 = fabsf(err);
+        gv = (err > 0.f ? 1.0f : (err < 0.f ? -1.0f : 0.f)) * p.gfac;
+      } else {
+        e2 = err * err;
+        gv = err * p.gfac;
+      }
+      if (p.head_omega > 0.f) gv = (gv * cosf(a)) * p.head_omega;
+    }
+    g_lds[tid] = gv;
+    if (tn == 0) {
+      p.out[m] = ov;
+      p.g[m] = gv;
+    }
+  }
+  // the band's loss and bias-gradient partials (head_loss_kernel's 256-row blocks and sums;
+  // threads >= BM add zeros); the block sums' barriers also publish g_lds.  max|g| of the band
+  // (head_loss_kernel's gmax partial): the next launch's backward scale for a Snake last layer
+  float se = e2, gs = gv, gx = fabsf(gv);
+  block_sum2_max(se, gs, gx, g_lds + BM);
+  if (tn == 0 && tid == 0) {
+    p.sse_part[tm] = se;
+    p.gsum_part[tm] = gs;
+    if (p.gmax_part) p.gmax_part[tm] = gx;
+  }
+  // ---- phase 2: head_bwd_kernel on the registers: dz = ((g w) C) omega stored x S (omega 1 for
+  // Snake / Tanh: C is their derivative), column partials of dz (db_L) and of g Y (dw_head) over
+  // the tile's rows
+  constexpr int NQ = 2;  // db_L, dw_head here; a Snake's da_L in phase 3
+  // g x S per row: S is a power of two, so ((g S) w) C = ((g w) C) S exactly and the stored dz x S
+  // needs no multiply of its own; the column partials sum dz S, g S Y (and g S w E) and leave
+  // multiplied by 1/S -- power-of-two scalings commute with every rounding, so dZ_L and the
+  // partials are bit for bit those of the unscaled order (head_bwd_kernel's ((g w) C) omega)
+  const float om = (MODE == NT_FWD_HB) ? p.omega : 1.0f, S = w.hb_S, invS = w.hb_invS;
+  float gm[SM];
+#pragma unroll
+  for (int j = 0; j < SM; ++j) gm[j] = g_lds[wm * TM + j * 16 + (lane & 15)] * S;
+  // rows outermost, both column pairs of a row piece back to back: each 128-B row segment of
+  // dZ_L is then written whole by two consecutive stores (column pairs outermost wrote each
+  // line's halves a pass apart: the HBM writes came to 2.63 GB for the 2.15 GB of dZ_L, PMC)
+  float cs[SN / 2][NQ][2][4];  // [column pair][db_L, dw_head][subtile h][column r]
+#pragma unroll
+  for (int pp = 0; pp < SN / 2; ++pp)
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) cs[pp][q][h][r] = 0.f;
+  // Snake: row j's E pieces are loaded as phase 2 reaches row j, ahead of its dZ_L stores (the
+  // registers of row j's accumulators free up as it goes); phase 3 reads them from registers
+  uint4 eall[SNK ? SM : 1][SNK ? SN / 2 : 1];
+  uint4 ldz[2];  // row j-1's dZ_L line chunks
+#pragma unroll
+  for (int j = 0; j < SM; ++j) {
+    if constexpr (SNK) {
+#pragma unroll
+      for (int pp = 0; pp < SN / 2; ++pp)
+        eall[j][pp] = *(const uint4*)at_lane(w.rowp(p.E, mrowu + j * 16, ncu), w.lane_piece + pp * 64);
+    }
+    uint2 dzq[SN];  // whole-line stores (Lay::LINES): this row piece's MFMA-layout halves
+#pragma unroll
+    for (int pp = 0; pp < SN / 2; ++pp) {
+      uint2 dzp[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int i = 2 * pp + h;
+        // the sine kind keeps phase 1's head weights in registers (same 239 VGPRs); the Snake / Tanh
+        // kinds re-read them from LDS per row (in registers they reach 255-256 VGPRs and spill)
+        const float4 w4 = (MODE == NT_FWD_HB) ? hw[i] : *(const float4*)(hw_lds + nq + i * 16);
+        const uint4 pk = __builtin_bit_cast(uint4, acc[i][j]);
+        const uint2 yh = uint2{pk.x, pk.y}, ch = uint2{pk.z, pk.w};
+        // head_bwd_kernel's dz, ((g w) C) omega (bit-identical), times S (gm carries it; omega
+        // is exactly 1 for a Snake / Tanh layer).  The fp32 x fp32 products and the db_L sums go
+        // in pairs (v_pk_mul_f32 / v_pk_add_f32: per element the same rounding as the scalar
+        // instruction); the products by an fp16 operand stay v_fma_mix_f32 (no packed form)
+        const f32x2 gw01 = f32x2{gm[j], gm[j]} * f32x2{w4.x, w4.y};
+        const f32x2 gw23 = f32x2{gm[j], gm[j]} * f32x2{w4.z, w4.w};
+        f32x2 d01 = f32x2{mul_mix<0>(gw01.x, ch), mul_mix<1>(gw01.y, ch)};
+        f32x2 d23 = f32x2{mul_mix<2>(gw23.x, ch), mul_mix<3>(gw23.y, ch)};
+        if constexpr (MODE == NT_FWD_HB) {
+          d01 *= f32x2{om, om};
+          d23 *= f32x2{om, om};
+          asm volatile("" : "+v"(d01), "+v"(d23));  // rounded to fp32 before the fp16 store (fp32_first)
+        }
+        const f32x2 c01 = f32x2{cs[pp][0][h][0], cs[pp][0][h][1]} + d01;
+        const f32x2 c23 = f32x2{cs[pp][0][h][2], cs[pp][0][h][3]} + d23;
+        cs[pp][0][h][0] = c01.x; cs[pp][0][h][1] = c01.y; cs[pp][0][h][2] = c23.x; cs[pp][0][h][3] = c23.y;
+        static_for<0, 4>([&](auto rc) {
+          constexpr int r = decltype(rc)::value;
+          cs[pp][1][h][r] = fma_mix<r>(gm[j], yh, cs[pp][1][h][r]);
+        });
+        dzp[h] = as_u2(pack4(d01.x, d01.y, d23.x, d23.y));
+      }
+      if constexpr (Lay::LINES) {
+        dzq[2 * pp] = dzp[0];
+        dzq[2 * pp + 1] = dzp[1];
+      }
+      else st16((h16*)at_lane(w.rowp(p.dZ, mrowu + j * 16, ncu), w.lane_piece + pp * 64), swap16_pair(dzp[0], dzp[1]));
+    }
+    // a row apart, as the forward: row j-1's dZ_L stores after row j's arithmetic
+    if constexpr (Lay::LINES) lines_row_apart(w, mrowu, ncu, j, LineRow<SN>{p.dZ, dzq, ldz});
+  }
+#pragma unroll
+  for (int pp = 0; pp < SN / 2; ++pp)
+#pragma unroll
+    for (int q = 0; q < NQ; ++q)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) colsum_flush(w, q, 2 * pp + h, cs[pp][q][h]);
+  if constexpr (SNK) {
+    // ---- phase 3 (Snake): da_L partials, sum over the tile's rows of (g w) E, with E read back
+    // from where phase 1 stored it (L2: written a hand-off earlier) during phase 2
+#pragma unroll
+    for (int pp = 0; pp < SN / 2; ++pp) {
+      uint4 eq[SM];
+#pragma unroll
+      for (int j = 0; j < SM; ++j) eq[j] = eall[j][pp];
+      float da[2][4];
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) da[h][r] = 0.f;
+#pragma unroll
+      for (int j = 0; j < SM; ++j) {
+        uint2 eu[2];
+        unswap16_pair(eq[j], eu[0], eu[1]);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const float4 w4 = *(const float4*)(hw_lds + nq + (2 * pp + h) * 16);
+          const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
+          static_for<0, 4>([&](auto rc) {
+            constexpr int r = decltype(rc)::value;
+            da[h][r] = fma_mix<r>(gm[j] * wv[r], eu[h], da[h][r]);
+          });
+        }
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) colsum_flush(w, 2, 2 * pp + h, da[h]);
+    }
+  }
+  // partial rows: db_L, dw_head (, da_L)
+  colsum_store(w, p, tm, n0, SNK ? 3 : 2, invS);
+}
+
+// The dX family: NT_DX, NT_DX0, NT_DX_SNAKE, NT_DX0_SNAKE (operands of the first rows from nt_pre)
+template <class W>
+__device__ __forceinline__ void nt_epi_dx(f32x4 (&acc)[W::Cfg::SN][W::Cfg::SM], int m0, int n0, const W& w,
+                                          const NtParams& p, const NtPre<typename W::Cfg, W::MODE>& in) {
+  using Cfg = typename W::Cfg;
+  using Lay = typename W::Lay;
+  using Pre = NtPre<Cfg, W::MODE>;
+  constexpr int MODE = W::MODE, TM = Cfg::TM, TN = Cfg::TN, SM = Cfg::SM, SN = Cfg::SN;
+  constexpr bool HAS_E = Pre::HAS_E;
+  constexpr int PRE_J = Pre::PRE_J, EB = Pre::EB;
+  const int tm = m0 / Cfg::BM;
+  const int mrowu = m0 + w.wm * TM, ncu = n0 + w.wn * TN;  // the wave's first row and column (wave-uniform)
+  const int in_dim = nt_is_dx0(MODE) ? p.in_dim : 0;
+  const int nred = (MODE == NT_DX_SNAKE) ? 2 : (MODE == NT_DX0_SNAKE ? 2 + in_dim : 1 + in_dim);
+  // slots: 0 db; 1..in dW0 (NT_DX0*); 1 da (NT_DX_SNAKE); 3 da0 (NT_DX0_SNAKE, written as 1+in)
+  float cs[4][SN][4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int i = 0; i < SN; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) cs[q][i][r] = 0.f;
+
+  const float om = p.omega;
+  // partial layout: NT_DX [tm][N]; NT_DX0 [tm][1+in][N] with q=0 -> db0, q=1+j -> dW0[:, j];
+  // NT_DX_SNAKE [tm][2][N] with q=0 -> db, q=1 -> da.
+  if constexpr (HAS_E) {
+    // flush(i): column subtile i's partials over this wave's rows into the LDS scratch
+    auto flush = [&](auto ic) {
+      constexpr int i = decltype(ic)::value;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (q >= nred) break;
+        // NT_DX0_SNAKE: da0 (slot 3) goes out as partial row 1 + in
+        const bool da0 = (MODE == NT_DX0_SNAKE) && q == nred - 1;
+        float v[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = da0 ? cs[3][i][r] : cs[q][i][r];
+        colsum_flush(w, q, i, v);
+      }
+    };
+    // the 16-B piece (row subtile j, column pair pp) from its Cprev and Eprev piece.  Each column
+    // partial sums its rows in order 0 .. SM-1 whatever order the pieces go in
+    // NT_DX_SNAKE with whole-line stores (Lay::LINES): a row piece's MFMA-layout halves (the batches
+    // below take both column pairs of a row back to back, pair 1 last)
+    uint2 dzrow[SN];
+    auto piece = [&](auto jc, auto ppc, const uint4& cpv, const uint4& epv) {
+      constexpr int j = decltype(jc)::value, pp = decltype(ppc)::value;
+      float t0 = 0.f, t1 = 0.f;
+      if constexpr (nt_is_dx0(MODE)) {
+        t0 = in.t_in[j][0];
+        t1 = p.in_dim > 1 ? in.t_in[j][1] : 0.f;
+      }
+      uint2 cpu[2], epu[2];
+      unswap16_pair(cpv, cpu[0], cpu[1]);
+      unswap16_pair(epv, epu[0], epu[1]);
+      uint2 dzp[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        dzp[h] = dz_subtile<MODE>(acc[2 * pp + h][j], cpu[h], epu[h], om, t0, t1, cs, 2 * pp + h);
+      if constexpr (MODE == NT_DX_SNAKE && Lay::LINES) {
+        dzrow[2 * pp] = dzp[0];
+        dzrow[2 * pp + 1] = dzp[1];
+        if constexpr (pp == SN / 2 - 1) lines_out(w, p.dZ, mrowu + j * 16, ncu, dzrow);
+      } else if constexpr (MODE == NT_DX_SNAKE) {
+        st16((h16*)at_lane(w.rowp(p.dZ, mrowu + j * 16, ncu), w.lane_piece + pp * 64), swap16_pair(dzp[0], dzp[1]));
+      }
+    };
+    // batches of EB rows, both column pairs of a row back to back: the two 64-B halves of each
+    // row's 128-B Cprev / Eprev / dZ segments are read and written together (pair 0 of the
+    // first EB rows comes from nt_pre)
+    static_assert(SN == 4, "two column pairs");
+    // software-pipelined: batch bq+1 is loaded before batch bq's dZ stores go out, so waiting
+    // for a batch never waits for earlier stores (vmcnt retires in issue order)
+    uint4 cq[2][EB][2], eq[2][EB][2];  // [buffer][row][column pair]
+    auto load_batch = [&](auto bqc) {
+      constexpr int bq = decltype(bqc)::value, bf = bq & 1;
+#pragma unroll
+      for (int jj = 0; jj < EB; ++jj)
+#pragma unroll
+        for (int pp = 0; pp < 2; ++pp) {
+          if (bq == 0 && pp == 0) {
+            cq[bf][jj][pp] = in.ce_in[jj][0];
+            eq[bf][jj][pp] = in.ce_in[jj][1];
+          } else {
+            const int ru = mrowu + (bq * EB + jj) * 16;
+            cq[bf][jj][pp] = *(const uint4*)at_lane(w.rowp(p.Cprev, ru, ncu), w.lane_piece + pp * 64);
+            eq[bf][jj][pp] = *(const uint4*)at_lane(w.rowp(p.Eprev, ru, ncu), w.lane_piece + pp * 64);
+          }
+        }
+    };
+    load_batch(std::integral_constant<int, 0>{});
+    static_for<0, SM / EB>([&](auto bqc) {
+      constexpr int bq = decltype(bqc)::value, bf = bq & 1;
+      if constexpr (bq + 1 < SM / EB) load_batch(std::integral_constant<int, bq + 1>{});
+      static_for<0, EB>([&](auto jc) {
+        constexpr int jj = decltype(jc)::value;
+        piece(std::integral_constant<int, bq * EB + jj>{}, std::integral_constant<int, 0>{}, cq[bf][jj][0], eq[bf][jj][0]);
+        piece(std::integral_constant<int, bq * EB + jj>{}, std::integral_constant<int, 1>{}, cq[bf][jj][1], eq[bf][jj][1]);
+      });
+    });
+    static_for<0, SN>([&](auto ic) { flush(ic); });
+  } else {
+    // NT_DX / NT_DX0: rows in order, both column pairs of a row together (rows >= PRE_J loaded
+    // at use), then the column partials.  A plain loop over dz_subtile: written through a per-piece
+    // lambda as the Snake modes', NT_DX0 takes 252-256 VGPRs instead of 239-244 (gfx950 listing)
+    uint4 ldz[2];  // NT_DX: row j-1's dZ line chunks
+#pragma unroll
+    for (int j = 0; j < SM; ++j) {
+      float t0 = 0.f, t1 = 0.f;
+      if constexpr (nt_is_dx0(MODE)) {
+        t0 = in.t_in[j][0];
+        t1 = p.in_dim > 1 ? in.t_in[j][1] : 0.f;
+      }
+      uint2 dzq[SN];  // NT_DX with whole-line stores: this row piece's MFMA-layout halves
+#pragma unroll
+      for (int pp = 0; pp < SN / 2; ++pp) {
+        uint2 cpu[2];
+        const uint4 cpv =
+            (j < PRE_J) ? in.cp_in[j < PRE_J ? j : 0][pp]
+                        : *(const uint4*)at_lane(w.rowp(p.Cprev, mrowu + j * 16, ncu), w.lane_piece + pp * 64);
+        unswap16_pair(cpv, cpu[0], cpu[1]);
+        uint2 dzp[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          dzp[h] = dz_subtile<MODE>(acc[2 * pp + h][j], cpu[h], uint2{}, om, t0, t1, cs, 2 * pp + h);
+        if constexpr (Lay::LINES && MODE == NT_DX) {
+          dzq[2 * pp] = dzp[0];
+          dzq[2 * pp + 1] = dzp[1];
+        }
+        else if constexpr (MODE == NT_DX)
+          st16((h16*)at_lane(w.rowp(p.dZ, mrowu + j * 16, ncu), w.lane_piece + pp * 64), swap16_pair(dzp[0], dzp[1]));
+      }
+      // a row apart, as the forward: row j-1's stores after row j's arithmetic
+      if constexpr (Lay::LINES && MODE == NT_DX) lines_row_apart(w, mrowu, ncu, j, LineRow<SN>{p.dZ, dzq, ldz});
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (q >= nred) break;
+#pragma unroll
+      for (int i = 0; i < SN; ++i) colsum_flush(w, q, i, cs[q][i]);
+    }
+  }
+  colsum_store(w, p, tm, n0, nred, w.inv_scale);
+}
+
+// One tile's epilogue by MODE
+template <class W>
+__device__ __forceinline__ void nt_epilogue(f32x4 (&acc)[W::Cfg::SN][W::Cfg::SM], int m0, int n0, const W& w,
+                                            const NtParams& p, const NtPre<typename W::Cfg, W::MODE>& in) {
+  if constexpr (nt_is_hb(W::MODE)) nt_epi_hb(acc, m0, n0, w, p);
+  else if constexpr (nt_is_fwd(W::MODE)) nt_epi_fwd(acc, m0, n0, w, p);
+  else nt_epi_dx(acc, m0, n0, w, p, in);
+}
+
+// The per-column vectors the forward epilogues read from LDS, staged once per block (visible to the other
+// waves after the pipeline's first barrier)
+template <class W>
+__device__ __forceinline__ void nt_stage_vectors(const W& w, const NtParams& p) {
+  constexpr int MODE = W::MODE;
+  if constexpr (nt_is_fwd(MODE)) {
+    // the sine modes' bias in revolutions, b * omega / (2 pi), once per block (the same fp32 product the
+    // epilogues formed per tile); 1 for Snake / Tanh
+    const float xb = nt_is_sine_fwd(MODE) ? p.omega * kInv2Pi : 1.0f;
+    for (int c = w.tid * 4; c < p.N; c += W::Cfg::THREADS * 4) {
+      const float4 b4 = *(const float4*)(p.bias + c);
+      *(float4*)(w.bias_lds + c) = float4{b4.x * xb, b4.y * xb, b4.z * xb, b4.w * xb};
+      if constexpr (W::HEAD) *(float4*)(w.hw_lds + c) = *(const float4*)(p.head_w + c);
+      if constexpr (nt_is_snake_fwd(MODE)) {
+        const float4 a4 = *(const float4*)(p.act_a + c);
+        *(float4*)(w.a_lds + c) = a4;
+        *(float4*)(w.ia_lds + c) = float4{1.0f / a4.x, 1.0f / a4.y, 1.0f / a4.z, 1.0f / a4.w};
+      }
+    }
+  }
+}
+
+// ---- the kernel: setup, the tile walk, the K-loop wiring, one nt_epilogue per tile ---------------
 // QUEUE (ping-pong K-loop only): tiles from the dynamic queue p.tileq instead of the static walk
 template <class Cfg, int MODE, bool HEAD, bool QUEUE = false, bool ACTL = false>
 __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_nt_kernel(NtParams p) {
@@ -249,7 +1123,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_nt_kernel(NtParams p) {
   // ---- LDS-DMA staging addresses (non-ping-pong K-loops) ------------------------------
   // One instruction moves 1 KiB = RPI rows x ROWB bytes.  Lane L lands at row L/SPR, 16-B
   // slot L%SPR, and carries the logical chunk stage_swz(row, slot) (source-side swizzle).
-  constexpr int ROWB = Cfg::ROWB, RPI = Cfg::RPI, SPR = Cfg::SPR;
+  constexpr int RPI = Cfg::RPI, SPR = Cfg::SPR;
   size_t xrel[Cfg::XINSTR], wrel[Cfg::WINSTR];
 #pragma unroll
   for (int j = 0; j < Cfg::XINSTR; ++j) {
@@ -277,10 +1151,12 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_nt_kernel(NtParams p) {
   // ---- fragment read offsets --------------------------------------------------------
   // 16x16x32 operand: lane holds row (lane&15), k = 8*(lane>>4) .. +7 of a 32-deep half;
   // fragment rows start at multiples of 16, so the swizzle depends on the lane only.
+  constexpr int ROWB = Cfg::ROWB;
   int koff[BK / 32];
 #pragma unroll
   for (int kk = 0; kk < BK / 32; ++kk)
     koff[kk] = (lane & 15) * ROWB + (stage_swz<BK>(lane & 15, (lane >> 4) + 4 * kk) << 4);
+
   auto frags = [&](int slot, int kk, h16x8 (&A)[SN], h16x8 (&B)[SM]) {
     const char* xs = smem + slot * Cfg::STAGE;
     const char* ws = xs + Cfg::XBYTES;
@@ -296,864 +1172,44 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_nt_kernel(NtParams p) {
 #pragma unroll
     for (int j = 0; j < SM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // ---- epilogue (per tile) ------------------------------------------------------------
-  // acc[i][j][r] = out[m][n] with m = m0 + wm*TM + j*16 + (lane&15),
-  //                              n = n0 + wn*TN + i*16 + 4*(lane>>4) + r.
-  // Global traffic goes in 16-B row pieces: column subtiles (2p, 2p+1) are exchanged with
-  // swap16_pair, this lane's piece starting at column ncol + 32p + swap16_col(lane).
-  float* red = (float*)(smem + Cfg::RING);
-  auto st16 = [&](h16* dst, uint4 v) { *(uint4*)dst = v; };
-  // the whole-line stores (plain forward, dX): non-temporal (SIREN_NT_STNT)
-  auto stl = [&](h16* dst, uint4 v) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    if constexpr (SIREN_NT_STNT != 0) __builtin_nontemporal_store(__builtin_bit_cast(u32x4, v), (u32x4*)dst);
-    else *(uint4*)dst = v;
-  };
-  // Whole 128-B lines per store (Lay::LINES): the wave's 16-row x 64-column fp16 piece of one
-  // output (lane: row lane & 15, 16-B chunks 4 pp + swap16_col(lane) / 8) goes through its 2-KiB LDS
-  // scratch, 16-B chunks XOR-swizzled by row (conflict-free both ways), and each store writes rows
-  // 8q .. 8q+7 as 8 lanes x 16 B per row.  Same bytes and store count as 16 rows x 64 B, but no
-  // half-line writes.  Same-wave LDS accesses complete in order, so the reads see this
-  // wave's writes and the next output's writes follow the reads.  row = the piece's first row and
-  // col = the wave's first column, both wave-uniform: each store is then a wave-uniform 64-bit base in
-  // SGPRs plus a 32-bit lane offset that is the same for every piece (the saddr form), where per-lane
-  // 64-bit addresses cost 10 64-bit VALU per row piece (v_mad_i64_i32, v_lshl_add_u64; gfx950 listing)
-  // v[i]: this lane's 4 columns of column subtile i in the MFMA layout (row lane & 15, columns 16 i + 4 g ..
-  // + 3, g = lane >> 4), packed fp16: 8 B at byte 32 i + 8 g of the row's line.  Each goes into the scratch as
-  // one 8-B half of its swizzled 16-B chunk 2 i + (g >> 1) (SIREN_LINES_SWAP 1: first paired into 16-B row
-  // pieces across 16-lane groups by v_permlane16_swap, as round 5 did -- 4 VALU per row piece more)
-  // lines_out in two halves (the non-HALF path): lines_get exchanges one row piece through the wave's
-  // scratch into this lane's two 16-B line chunks, lines_put stores them.  The plain forward runs them
-  // a row apart, so a row's LDS round trip completes under the next row's sin / cos
-  auto lines_get = [&](const uint2 (&v)[Cfg::SN], uint4 (&line)[2]) {
-    static_assert(Cfg::SN == 4, "a wave's row piece is one 128-B line");
-    const int pr = lane & 15, pc = swap16_col(lane) >> 3;
-    const int g = lane >> 4;
-    const int qr = lane >> 3, qc = lane & 7;
-    char* sc = smem + Lay::ST + wave * 2048;
-    if constexpr (SIREN_LINES_SWAP != 0) {
-#pragma unroll
-      for (int pp = 0; pp < Cfg::SN / 2; ++pp) {
-        const int c = pp * 4 + pc;
-        *(uint4*)(sc + pr * 128 + ((c ^ (pr & 7)) << 4)) = swap16_pair(v[2 * pp], v[2 * pp + 1]);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < Cfg::SN; ++i) {
-        const int c = 2 * i + (g >> 1);
-        *(uint2*)(sc + pr * 128 + ((c ^ (pr & 7)) << 4) + ((g & 1) << 3)) = v[i];
-      }
-    }
-    __builtin_amdgcn_wave_barrier();  // cross-lane exchange: the reads stay after every lane's writes
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int r = qr + 8 * q;
-      line[q] = *(const uint4*)(sc + r * 128 + ((qc ^ (r & 7)) << 4));
-    }
-    __builtin_amdgcn_wave_barrier();  // ... and the next output's writes after these reads
-  };
-  auto lines_put = [&](h16* out, int row, int col, const uint4 (&line)[2]) {
-    const int qr = lane >> 3, qc = lane & 7;
-    const char* ub = (const char*)(out + (size_t)row * LD + col);
-    unsigned lo = (unsigned)((qr * LD + qc * 8) * 2);
-    asm("" : "+v"(lo));  // kept 32-bit at the stores (a hoisted 64-bit zext defeats the saddr form)
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      unsigned lq = lo;
-      asm("" : "+v"(lq));  // one opaque copy per store: no store's address is derived from another's
-      stl((h16*)(ub + (size_t)(16 * q) * LD + lq), line[q]);
-    }
-  };
-  auto lines_out = [&](h16* out, int row, int col, const uint2 (&v)[Cfg::SN]) {
-    static_assert(Cfg::SN == 4, "a wave's row piece is one 128-B line");
-    const int pr = lane & 15, pc = swap16_col(lane) >> 3;  // this lane's piece: row, 16-B chunk
-    const int g = lane >> 4;                                // MFMA layout: 16-lane group
-    const int qr = lane >> 3, qc = lane & 7;                // line layout: row (+ 8 q), chunk
-    uint4 vs[SIREN_LINES_SWAP ? Cfg::SN / 2 : 1];
-    if constexpr (SIREN_LINES_SWAP != 0) {
-#pragma unroll
-      for (int pp = 0; pp < Cfg::SN / 2; ++pp) vs[pp] = swap16_pair(v[2 * pp], v[2 * pp + 1]);
-    }
-    const char* ub = (const char*)(out + (size_t)row * LD + col);
-    unsigned lo = (unsigned)((qr * LD + qc * 8) * 2);
-    asm("" : "+v"(lo));  // kept 32-bit at the stores (a hoisted 64-bit zext defeats the saddr form)
-    if constexpr (Lay::HALF) {
-      // rows 8h .. 8h+7 per pass.  No lane may skip a pass's write: the compiler treats the scratch
-      // per lane, and a write under a divergent branch was moved past the other lanes' reads (wrong
-      // rows, gfx950 listing; a DPP exchange that avoids it spilled).  So every lane writes both its
-      // chunks in both passes, those of the other pass's rows to slots nobody reads (Lay::DM,
-      // shared by the block's waves: garbage by design).
-      char* sh = smem + Cfg::RING + wave * 1024;
-      char* dm = smem + Lay::DM + lane * 32;
-      const int r8 = pr & 7;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const bool mine = (pr >> 3) == h;
-        if constexpr (SIREN_LINES_SWAP != 0) {
-#pragma unroll
-          for (int pp = 0; pp < Cfg::SN / 2; ++pp) {
-            const int c = pp * 4 + pc;
-            *(uint4*)(mine ? sh + r8 * 128 + ((c ^ r8) << 4) : dm + pp * 16) = vs[pp];
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < Cfg::SN; ++i) {
-            const int c = 2 * i + (g >> 1);
-            *(uint2*)(mine ? sh + r8 * 128 + ((c ^ r8) << 4) + ((g & 1) << 3) : dm + i * 8) = v[i];
-          }
-        }
-        // the exchange is across lanes: no LDS access moves over these (LDS is in order within a
-        // wave, so they cost no wait; the ordering no longer rests on how the select is written)
-        __builtin_amdgcn_wave_barrier();
-        const uint4 line = *(const uint4*)(sh + qr * 128 + ((qc ^ qr) << 4));
-        __builtin_amdgcn_wave_barrier();
-        unsigned lh = lo;
-        asm("" : "+v"(lh));  // one opaque copy per store: no store's address is derived from another's
-        stl((h16*)(ub + (size_t)(16 * h) * LD + lh), line);
-      }
-      return;
-    }
-    uint4 line[2];
-    lines_get(v, line);
-    lines_put(out, row, col, line);
-  };
-  // NT_FWD: bias / head weights through LDS -- the epilogue then issues no global load
-  // whose compiler-counted vmcnt wait would also cover the asm-issued stage prefetch.
-  float* bias_lds = (float*)(smem + Lay::BIAS);
-  float* hw_lds = (float*)(smem + Lay::HW);
-  float* a_lds = (float*)(smem + Lay::A);    // Snake: a
-  float* ia_lds = (float*)(smem + Lay::IA);  // Snake: 1/a (the same IEEE quotient the epilogue used per element)
-  if constexpr (nt_is_fwd(MODE)) {
-    // the sine modes' bias in revolutions, b * omega / (2 pi), once per block (the same fp32 product the
-    // epilogues formed per tile); 1 for Snake / Tanh
-    const float xb = (MODE == NT_FWD || MODE == NT_FWD_HB) ? p.omega * kInv2Pi : 1.0f;
-    for (int c = tid * 4; c < N; c += Cfg::THREADS * 4) {
-      const float4 b4 = *(const float4*)(p.bias + c);
-      *(float4*)(bias_lds + c) = float4{b4.x * xb, b4.y * xb, b4.z * xb, b4.w * xb};
-      if constexpr (HEAD) *(float4*)(hw_lds + c) = *(const float4*)(p.head_w + c);
-      if constexpr (nt_is_snake_fwd(MODE)) {
-        const float4 a4 = *(const float4*)(p.act_a + c);
-        *(float4*)(a_lds + c) = a4;
-        *(float4*)(ia_lds + c) = float4{1.0f / a4.x, 1.0f / a4.y, 1.0f / a4.z, 1.0f / a4.w};
-      }
-    }
-    // visible to other waves after the pipeline's first barrier
-  }
-  // dZ carries the backward storage scale S; the fp32 column partials leave unscaled
-  const float inv_scale = (!nt_is_fwd(MODE) && p.gscale) ? p.gscale[1] : 1.0f;
-  // the fused last layer's S, 1/S and head bias, loaded once here: loaded in the epilogue, each
-  // tile's phase 2 waited at vmcnt(0) for them, i.e. for the next tile's stages issued before it
-  float hb_scale[2] = {1.0f, 1.0f}, hb_bias = 0.0f;
+  // ---- the epilogues' view of this wave, and their operands in flight (nt_pre) ----------------
+  NtWave<Cfg, MODE, HEAD, ACTL> w;
+  w.tid = tid;
+  w.lane = lane;
+  w.wave = wave;
+  w.wm = wm;
+  w.wn = wn;
+  w.LD = LD;
+  w.smem = smem;
+  w.bias_lds = (float*)(smem + Lay::BIAS);
+  w.hw_lds = (float*)(smem + Lay::HW);
+  w.a_lds = (float*)(smem + Lay::A);
+  w.ia_lds = (float*)(smem + Lay::IA);
+  w.red = (float*)(smem + Cfg::RING);
+  w.diag = diag;
+  nt_stage_vectors(w, p);
+  w.inv_scale = (!nt_is_fwd(MODE) && p.gscale) ? p.gscale[1] : 1.0f;
+  w.hb_S = 1.0f;
+  w.hb_invS = 1.0f;
+  w.hb_bias = 0.0f;
   if constexpr (nt_is_hb(MODE)) {
-    hb_scale[0] = p.gscale[0];
-    hb_scale[1] = p.gscale[1];
-    hb_bias = p.b_head[0];
+    w.hb_S = p.gscale[0];
+    w.hb_invS = p.gscale[1];
+    w.hb_bias = p.b_head[0];
     // in VGPRs (3 of the 20 free): as SGPRs they pushed 12 more SGPR spills into VGPR lanes
-    asm volatile("" : "+v"(hb_scale[0]), "+v"(hb_scale[1]), "+v"(hb_bias));
+    asm volatile("" : "+v"(w.hb_S), "+v"(w.hb_invS), "+v"(w.hb_bias));
   }
-  // NT_DX / NT_DX0 epilogue operands loaded by `pre` (before the next tile's early prefetch).  The
-  // rest are loaded by the epilogue in one batch once earlier pieces are consumed (their
-  // accumulators free the registers), so a batch waits once, not once per piece behind the
-  // in-order vmcnt (which also covers the next tile's stages and this tile's stores).  NT_DX and
-  // NT_DX0 preload every row (NT_DX0 has room for it since its products use v_fma_mix and its
-  // row sums v_add_f32_dpp: 229 VGPRs, against 235 with half the rows before).  The Snake modes
-  // (Cprev AND Eprev per piece) go in batches of EB rows with both column pairs of a row
-  // together: `pre` loads pair 0 of the first batch, and each batch loads the next one before
-  // its own dZ stores.
-  constexpr bool HAS_E = (MODE == NT_DX_SNAKE || MODE == NT_DX0_SNAKE);
-  constexpr int PRE_J = (nt_is_fwd(MODE) || HAS_E) ? 0 : SM;
-  // Snake modes: EB = 2 rows per batch, two batches in flight (gfx950 listing: 238 / 247 VGPRs
-  // for NT_DX_SNAKE / NT_DX0_SNAKE, no spills; 4 rows spill 164-196 B): dX Snake 2.559 -> 2.530 ms
-  // against 4-row batches loaded at use (profiles/r16c/ab_snake_dx_pipelined.json)
-  constexpr int EB0 = (MODE == NT_DX0_SNAKE) ? SIREN_SNAKE0_EB : SIREN_SNAKE_EB;
-  constexpr int EB = EB0 < SM ? EB0 : SM;
-  static_assert(SM % EB == 0, "Snake epilogue batches");
-  // Row-piece accesses of the epilogues: a wave-uniform row base (SGPRs) plus a 32-bit lane byte offset kept
-  // 32-bit at the access by an opaque copy, so that hipcc emits the saddr form (one SGPR pair, one VGPR)
-  // instead of per-lane 64-bit address arithmetic (v_mad_i64_i32, v_lshl_add_u64: lines_out)
-  auto at_lane = [](const void* ub, unsigned lo) -> char* {
-    asm("" : "+v"(lo));
-    return (char*)ub + lo;
-  };
-  // this lane's 16-B piece of a row piece (row lane & 15, columns swap16_col(lane) ..): byte offset in [*][LD] fp16
-  const unsigned lane_piece = (unsigned)(((lane & 15) * LD + swap16_col(lane)) * 2);
-  auto rowp = [&](const h16* base, int row_u, int col_u) { return (const char*)(base + (size_t)row_u * LD + col_u); };
-  uint4 cp_in[PRE_J > 0 ? PRE_J : 1][SN / 2];
-  uint4 ce_in[HAS_E ? EB : 1][2];
-  float t_in[SM][2];
+  w.lane_piece = (unsigned)(((lane & 15) * LD + swap16_col(lane)) * 2);
+  NtPre<Cfg, MODE> in;
   auto pre = [&](int g) {
     int m0, n0;
     tile_of(g, m0, n0);
-    const int mrowu = m0 + wm * TM, ncu = n0 + wn * TN;  // the wave's first row and column (wave-uniform)
-    if constexpr (!nt_is_fwd(MODE)) {
-#pragma unroll
-      for (int j = 0; j < PRE_J; ++j)
-#pragma unroll
-        for (int pp = 0; pp < SN / 2; ++pp)
-          cp_in[j][pp] = *(const uint4*)at_lane(rowp(p.Cprev, mrowu + j * 16, ncu), lane_piece + pp * 64);
-      if constexpr (HAS_E) {
-#pragma unroll
-        for (int j = 0; j < EB; ++j) {
-          ce_in[j][0] = *(const uint4*)at_lane(rowp(p.Cprev, mrowu + j * 16, ncu), lane_piece);
-          ce_in[j][1] = *(const uint4*)at_lane(rowp(p.Eprev, mrowu + j * 16, ncu), lane_piece);
-        }
-      }
-      if constexpr (nt_is_dx0(MODE)) {
-#pragma unroll
-        for (int j = 0; j < SM; ++j) {
-          const float* tb = p.t + (size_t)(mrowu + j * 16) * p.in_dim;
-          const unsigned lt = (unsigned)((lane & 15) * p.in_dim * 4);
-          t_in[j][0] = *(const float*)at_lane(tb, lt);
-          t_in[j][1] = (p.in_dim > 1) ? *(const float*)at_lane(tb, lt + 4) : 0.f;
-        }
-      }
-    }
+    nt_pre(m0, n0, w, p, in);
   };
   auto epilogue = [&](int g) {
     int m0, n0;
     tile_of(g, m0, n0);
-    const int tm = m0 / BM, tn = n0 / BN;
-    const int npc = n0 + wn * TN + swap16_col(lane);      // swapped layout: this lane's piece
-    const int mrowu = m0 + wm * TM;                       // the wave's first row (wave-uniform)
-    const int mrow0 = mrowu + (lane & 15);
-
-    if constexpr (nt_is_hb(MODE)) {
-      // The last hidden layer fused with the head, the loss gradient and the head backward, for
-      // the three last-layer kinds (models.py:114-115, 235-241, 366-372).
-      // ---- phase 1: the layer's outputs for the head partial of the band's rows over this column
-      // tile, summed exactly as NT_FWD(_SNAKE/_TANH) + HEAD sums them.  Sine / Tanh: Y and C (= cos,
-      // or 1 - Y^2) rounded to fp16 as the unfused forward stores them, packed IN PLACE of their
-      // accumulators (4 fp32 -> 4 + 4 fp16: the same 4 VGPRs, so nothing more is live across the
-      // hand-off than the accumulators).  Snake has three fp16 outputs (Y, D, E): Y and D go in
-      // place of the accumulators, E to the layer's E buffer, read back during phase 2.
-      constexpr bool SNK = MODE == NT_FWD_HB_SNAKE, TNH = MODE == NT_FWD_HB_TANH;
-      const int nq = n0 + wn * TN + 4 * (lane >> 4);
-      const float xs = (MODE == NT_FWD_HB) ? p.omega * kInv2Pi : 1.0f;
-      float4 bias[SN], hw[SN];  // (bias_lds holds b * xs)
-#pragma unroll
-      for (int i = 0; i < SN; ++i) {
-        bias[i] = *(const float4*)(bias_lds + nq + i * 16);
-        hw[i] = *(const float4*)(hw_lds + nq + i * 16);
-      }
-      float hp[SM];
-      uint2 epair[2];  // Snake: fp16 E of one row piece's two column subtiles
-#pragma unroll
-      for (int j = 0; j < SM; ++j) {
-        hp[j] = 0.f;
-#pragma unroll
-        for (int q = 0; q < SN / 2; ++q) {
-          const int pp = (Cfg::PP && j >= SM / 2) ? SN / 2 - 1 - q : q;
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int i = 2 * pp + h;
-            const float bb[4] = {bias[i].x, bias[i].y, bias[i].z, bias[i].w};
-            float sv[4];
-            if constexpr (SNK) {
-              const float4 a4 = *(const float4*)(a_lds + nq + i * 16);
-              const float4 ia4 = *(const float4*)(ia_lds + nq + i * 16);
-              const float av[4] = {a4.x, a4.y, a4.z, a4.w}, iav[4] = {ia4.x, ia4.y, ia4.z, ia4.w};
-              float cv[4], ev[4];
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                snake_epi(acc[i][j][r] + bb[r], av[r], iav[r], sv[r], cv[r], ev[r]);
-              }
-              // Y and D packed in place of the accumulators; E goes to HBM (p.E, the layer's E
-              // buffer) in 16-B row pieces once both subtiles of the pair have it, and phase 3 reads
-              // it back (held in registers, 64 more VGPRs across the hand-off spilled 400 B per lane)
-              const uint2 yv = as_u2(pack4(sv[0], sv[1], sv[2], sv[3])), cw = as_u2(pack4(cv[0], cv[1], cv[2], cv[3]));
-              acc[i][j] = __builtin_bit_cast(f32x4, uint4{yv.x, yv.y, cw.x, cw.y});
-              epair[h] = as_u2(pack4(ev[0], ev[1], ev[2], ev[3]));
-              asm volatile("" : "+v"(acc[i][j]));
-            } else {
-              float cv[4], xa[4];
-              if constexpr (!TNH) fma4_pk(acc[i][j], xs, bias[i], xa);  // as the plain forward
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                if constexpr (TNH) {
-                  const float y = tanh_epi(acc[i][j][r] + bb[r]);
-                  sv[r] = y;
-                  cv[r] = 1.0f - y * y;
-                } else {
-                  const float x = __builtin_amdgcn_fractf(xa[r]);
-                  sv[r] = __builtin_amdgcn_sinf(x);
-                  cv[r] = __builtin_amdgcn_cosf(x);
-                }
-              }
-              const uint2 yv = as_u2(pack4(sv[0], sv[1], sv[2], sv[3])), cw = as_u2(pack4(cv[0], cv[1], cv[2], cv[3]));
-              acc[i][j] = __builtin_bit_cast(f32x4, uint4{yv.x, yv.y, cw.x, cw.y});
-              // opaque: the packing happens here (left to itself the compiler sinks the cos past the
-              // hand-off into phase 2, keeping the fp32 arguments live across it: 372 B of spills)
-              asm volatile("" : "+v"(acc[i][j]));
-            }
-            hp[j] += dot4_pk(sv, hw[i]);
-          }
-          if constexpr (SNK)
-            st16((h16*)at_lane(rowp(p.E, mrowu + j * 16, n0 + wn * TN), lane_piece + pp * 64), swap16_pair(epair[0], epair[1]));
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < SM; ++j) {
-        hp[j] += __shfl_xor(hp[j], 16, 64);
-        hp[j] += __shfl_xor(hp[j], 32, 64);
-      }
-      if (lane < 16) {
-#pragma unroll
-        for (int j = 0; j < SM; ++j) red[wn * BM + wm * TM + j * 16 + lane] = hp[j];
-      }
-      lds_barrier();
-      // ---- the band hand-off: publish this column tile's partial of each row, take the other
-      // column tiles' partials as their blocks publish them (the band's tiles_n tiles run in
-      // lockstep on tiles_n consecutive blocks of one XCD; DESIGN §4 "fused head backward"), then
-      // head_loss for the band's rows.  The partial itself is the flag: head_part is filled with
-      // kHeadPending before the launch and a published value is never that pattern (NaN is
-      // stored canonical), so no fence orders it -- one agent-scope atomic word each way.
-      // g_lds sits past the column-partial scratch of phase 2 (3 partial rows with Snake)
-      float* g_lds = red + (SNK ? 3 * Cfg::WM * BN : WN * BM);
-      float e2 = 0.f, gv = 0.f;
-      if (tid < BM) {
-        float own = 0.f;
-#pragma unroll
-        for (int w = 0; w < WN; ++w) own += red[w * BM + tid];
-        const int m = m0 + tid;
-        unsigned* hpu = (unsigned*)p.head_part;
-        // SIREN_OPT_HB_FAULT bit 0 (SIREN_DIAG builds): column tile 1 never publishes (test hook)
-        if (!(SIREN_DIAG_ON && (p.hb_fault & 1) && tn == 1))
-          __hip_atomic_store(hpu + (size_t)tn * p.M + m, own == own ? __float_as_uint(own) : 0x7fc00000u,
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        // the row's target, loaded before the partners are polled: its latency runs under the polls (loaded
-        // after them, the block waited one more memory round trip per tile)
-        // (unconditional, the row clamped into [0, n_valid), and retired unconditionally below: a load or a use
-        // under `m < n_valid` left the register's reuse in phase 2 behind a vmcnt(0), i.e. behind the dZ_L stores)
-        // (the empty asm keeps hipcc from hoisting the now always-valid load above `tid < BM`, into the waves
-        // that never consume it)
-        asm volatile("" ::: "memory");
-        const float tgt = p.target[min(m, p.n_valid > 0 ? p.n_valid - 1 : 0)];
-        float o = 0.f;  // head_loss_kernel's order: partials j = 0, 1, ..., then the bias
-        for (int jt = 0; jt < tiles_n; ++jt) {
-          float v = own;
-          if (jt != tn) {
-            unsigned u;
-            int polls = 0;
-            while ((u = __hip_atomic_load(hpu + (size_t)jt * p.M + m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) ==
-                   kHeadPending) {
-              // bounded: a partner kept off the chip (CUs held by another process) voids the step
-              // instead of hanging the launch -- the band's partial becomes NaN and the wait is
-              // counted in the guard's stall word, which makes the update skip the step and the
-              // engine raise (a NaN alone would pass guard_skip and reach the weights)
-              if (++polls > p.spin_limit) {
-                u = 0x7fc00000u;
-                if (p.stall) __hip_atomic_fetch_add(p.stall, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-              }
-              // fail fast: once any wait of this step (this launch or an earlier micro-batch's) has given
-              // up, the step is void already -- every other wait stops within kStallCheck polls instead
-              // of spending its own whole limit (the stall word is sticky until the host clears it)
-              if ((polls & (kStallCheck - 1)) == 0 && p.stall &&
-                  __hip_atomic_load(p.stall, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-                u = 0x7fc00000u;
-                break;
-              }
-              __builtin_amdgcn_s_sleep(1);
-            }
-            v = __uint_as_float(u);
-          }
-          o += v;
-        }
-        o += hb_bias;
-        const float a = p.head_omega * o;
-        const float ov = p.head_omega > 0.f ? sinf(a) : o;
-        asm volatile("" ::"v"(tgt));  // consumed here on every path (the use below is under m < n_valid)
-        if (m < p.n_valid) {
-          const float err = ov - tgt;
-          if (p.loss_mode == 1) {
-            e2 = fabsf(err);
-            gv = (err > 0.f ? 1.0f : (err < 0.f ? -1.0f : 0.f)) * p.gfac;
-          } else {
-            e2 = err * err;
-            gv = err * p.gfac;
-          }
-          if (p.head_omega > 0.f) gv = (gv * cosf(a)) * p.head_omega;
-        }
-        g_lds[tid] = gv;
-        if (tn == 0) {
-          p.out[m] = ov;
-          p.g[m] = gv;
-        }
-      }
-      // the band's loss and bias-gradient partials (head_loss_kernel's 256-row blocks and sums;
-      // threads >= BM add zeros); the block sums' barriers also publish g_lds.  max|g| of the band
-      // (head_loss_kernel's gmax partial): the next launch's backward scale for a Snake last layer
-      float se = e2, gs = gv, gx = fabsf(gv);
-      block_sum2_max(se, gs, gx, g_lds + BM);
-      if (tn == 0 && tid == 0) {
-        p.sse_part[tm] = se;
-        p.gsum_part[tm] = gs;
-        if (p.gmax_part) p.gmax_part[tm] = gx;
-      }
-      // ---- phase 2: head_bwd_kernel on the registers: dz = ((g w) C) omega stored x S (omega 1 for
-      // Snake / Tanh: C is their derivative), column partials of dz (db_L) and of g Y (dw_head) over
-      // the tile's rows
-      constexpr int NQ = 2;  // db_L, dw_head here; a Snake's da_L in phase 3
-      // g x S per row: S is a power of two, so ((g S) w) C = ((g w) C) S exactly and the stored dz x S
-      // needs no multiply of its own; the column partials sum dz S, g S Y (and g S w E) and leave
-      // multiplied by 1/S -- power-of-two scalings commute with every rounding, so dZ_L and the
-      // partials are bit for bit those of the unscaled order (head_bwd_kernel's ((g w) C) omega)
-      const float om = (MODE == NT_FWD_HB) ? p.omega : 1.0f, S = hb_scale[0], invS = hb_scale[1];
-      float gm[SM];
-#pragma unroll
-      for (int j = 0; j < SM; ++j) gm[j] = g_lds[wm * TM + j * 16 + (lane & 15)] * S;
-      // rows outermost, both column pairs of a row piece back to back: each 128-B row segment of
-      // dZ_L is then written whole by two consecutive stores (column pairs outermost wrote each
-      // line's halves a pass apart: the HBM writes came to 2.63 GB for the 2.15 GB of dZ_L, PMC)
-      float cs[SN / 2][NQ][2][4];  // [column pair][db_L, dw_head][subtile h][column r]
-#pragma unroll
-      for (int pp = 0; pp < SN / 2; ++pp)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-#pragma unroll
-          for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) cs[pp][q][h][r] = 0.f;
-      // Snake: row j's E pieces are loaded as phase 2 reaches row j, ahead of its dZ_L stores (the
-      // registers of row j's accumulators free up as it goes); phase 3 reads them from registers
-      uint4 eall[SNK ? SM : 1][SNK ? SN / 2 : 1];
-      uint4 ldz[2];  // row j-1's dZ_L line chunks
-#pragma unroll
-      for (int j = 0; j < SM; ++j) {
-        if constexpr (SNK) {
-#pragma unroll
-          for (int pp = 0; pp < SN / 2; ++pp)
-            eall[j][pp] = *(const uint4*)at_lane(rowp(p.E, mrowu + j * 16, n0 + wn * TN), lane_piece + pp * 64);
-        }
-        uint2 dzq[SN];  // whole-line stores (Lay::LINES): this row piece's MFMA-layout halves
-#pragma unroll
-        for (int pp = 0; pp < SN / 2; ++pp) {
-          uint2 dzp[2];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int i = 2 * pp + h;
-            // the sine kind keeps phase 1's head weights in registers (same 239 VGPRs); the Snake / Tanh
-            // kinds re-read them from LDS per row (in registers they reach 255-256 VGPRs and spill)
-            const float4 w4 = (MODE == NT_FWD_HB) ? hw[i] : *(const float4*)(hw_lds + nq + i * 16);
-            const uint4 pk = __builtin_bit_cast(uint4, acc[i][j]);
-            const uint2 yh = uint2{pk.x, pk.y}, ch = uint2{pk.z, pk.w};
-            // head_bwd_kernel's dz, ((g w) C) omega (bit-identical), times S (gm carries it; omega
-            // is exactly 1 for a Snake / Tanh layer).  The fp32 x fp32 products and the db_L sums go
-            // in pairs (v_pk_mul_f32 / v_pk_add_f32: per element the same rounding as the scalar
-            // instruction); the products by an fp16 operand stay v_fma_mix_f32 (no packed form)
-            const f32x2 gw01 = f32x2{gm[j], gm[j]} * f32x2{w4.x, w4.y};
-            const f32x2 gw23 = f32x2{gm[j], gm[j]} * f32x2{w4.z, w4.w};
-            f32x2 d01 = f32x2{mul_mix<0>(gw01.x, ch), mul_mix<1>(gw01.y, ch)};
-            f32x2 d23 = f32x2{mul_mix<2>(gw23.x, ch), mul_mix<3>(gw23.y, ch)};
-            if constexpr (MODE == NT_FWD_HB) {
-              d01 *= f32x2{om, om};
-              d23 *= f32x2{om, om};
-              asm volatile("" : "+v"(d01), "+v"(d23));  // rounded to fp32 before the fp16 store (fp32_first)
-            }
-            const f32x2 c01 = f32x2{cs[pp][0][h][0], cs[pp][0][h][1]} + d01;
-            const f32x2 c23 = f32x2{cs[pp][0][h][2], cs[pp][0][h][3]} + d23;
-            cs[pp][0][h][0] = c01.x; cs[pp][0][h][1] = c01.y; cs[pp][0][h][2] = c23.x; cs[pp][0][h][3] = c23.y;
-            static_for<0, 4>([&](auto rc) {
-              constexpr int r = decltype(rc)::value;
-              cs[pp][1][h][r] = fma_mix<r>(gm[j], yh, cs[pp][1][h][r]);
-            });
-            dzp[h] = as_u2(pack4(d01.x, d01.y, d23.x, d23.y));
-          }
-          if constexpr (Lay::LINES) {
-            dzq[2 * pp] = dzp[0];
-            dzq[2 * pp + 1] = dzp[1];
-          }
-          else st16((h16*)at_lane(rowp(p.dZ, mrowu + j * 16, n0 + wn * TN), lane_piece + pp * 64), swap16_pair(dzp[0], dzp[1]));
-        }
-        if constexpr (Lay::LINES) {
-          // a row apart, as the forward: row j-1's dZ_L stores after row j's arithmetic
-          if (j > 0) lines_put(p.dZ, mrowu + (j - 1) * 16, n0 + wn * TN, ldz);
-          lines_get(dzq, ldz);
-          if (j == SM - 1) lines_put(p.dZ, mrowu + j * 16, n0 + wn * TN, ldz);
-        }
-      }
-#pragma unroll
-      for (int pp = 0; pp < SN / 2; ++pp)
-#pragma unroll
-        for (int q = 0; q < NQ; ++q)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = cs[pp][q][h][r];
-            row16_sum4(v);
-            if ((lane & 15) == 0)
-              *(float4*)(red + (q * Cfg::WM + wm) * BN + wn * TN + (2 * pp + h) * 16 + 4 * (lane >> 4)) =
-                  float4{v[0], v[1], v[2], v[3]};
-          }
-      if constexpr (SNK) {
-        // ---- phase 3 (Snake): da_L partials, sum over the tile's rows of (g w) E, with E read back
-        // from where phase 1 stored it (L2: written a hand-off earlier) during phase 2
-#pragma unroll
-        for (int pp = 0; pp < SN / 2; ++pp) {
-          uint4 eq[SM];
-#pragma unroll
-          for (int j = 0; j < SM; ++j) eq[j] = eall[j][pp];
-          float da[2][4];
-#pragma unroll
-          for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) da[h][r] = 0.f;
-#pragma unroll
-          for (int j = 0; j < SM; ++j) {
-            uint2 eu[2];
-            unswap16_pair(eq[j], eu[0], eu[1]);
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              const float4 w4 = *(const float4*)(hw_lds + nq + (2 * pp + h) * 16);
-              const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
-              static_for<0, 4>([&](auto rc) {
-                constexpr int r = decltype(rc)::value;
-                da[h][r] = fma_mix<r>(gm[j] * wv[r], eu[h], da[h][r]);
-              });
-            }
-          }
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = da[h][r];
-            row16_sum4(v);
-            if ((lane & 15) == 0)
-              *(float4*)(red + (2 * Cfg::WM + wm) * BN + wn * TN + (2 * pp + h) * 16 + 4 * (lane >> 4)) =
-                  float4{v[0], v[1], v[2], v[3]};
-          }
-        }
-      }
-      lds_barrier();
-      if (tid < BN) {
-        constexpr int NP = SNK ? 3 : 2;  // partial rows: db_L, dw_head (, da_L)
-#pragma unroll
-        for (int q = 0; q < NP; ++q) {
-          float sum = 0.f;
-#pragma unroll
-          for (int w = 0; w < Cfg::WM; ++w) sum += red[(q * Cfg::WM + w) * BN + tid];
-          p.colsum_part[((size_t)tm * NP + q) * LD + n0 + tid] = sum * invS;  // sums of x S: exact
-        }
-      }
-    } else if constexpr (nt_is_fwd(MODE)) {
-      const int nq = n0 + wn * TN + 4 * (lane >> 4);     // natural layout: this lane's columns
-      const float xs = (MODE == NT_FWD) ? p.omega * kInv2Pi : 1.0f;
-      float4 bias[SN], hw[SN];  // (bias_lds holds b * xs)
-#pragma unroll
-      for (int i = 0; i < SN; ++i) {
-        bias[i] = *(const float4*)(bias_lds + nq + i * 16);
-        if constexpr (HEAD) hw[i] = *(const float4*)(hw_lds + nq + i * 16);
-      }
-      float hp[SM];
-#pragma unroll
-      for (int j = 0; j < SM; ++j) hp[j] = 0.f;
-      uint4 ly[2], lc[2];  // NT_FWD: row j-1's Y / C line chunks, stored after row j's arithmetic
-#pragma unroll
-      for (int j = 0; j < SM; ++j) {
-        const size_t rowoff = (size_t)(mrow0 + j * 16) * LD;
-        uint4 yp[SN / 2], cpk[SN / 2], epk[SN / 2];  // 16-B row pieces (the per-lane stores)
-        uint2 yh[SN], chh[SN], eh[SN];                // MFMA-layout halves (lines_out)
-#pragma unroll
-        for (int q = 0; q < SN / 2; ++q) {
-          // ping-pong tiles: the lower row half takes its column pairs in reverse, the order of
-          // the K-loop's serpentine phases (a: pair 0 / rows 0-3, b: 1 / 0-3, c: 1 / 4-7, d: 0 /
-          // 4-7) -- the head partial sums keep that summation order
-          const int pp = (Cfg::PP && j >= SM / 2) ? SN / 2 - 1 - q : q;
-          uint2 ys[2], cs[2], es[2];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int i = 2 * pp + h;
-            const float bb[4] = {bias[i].x, bias[i].y, bias[i].z, bias[i].w};
-            float s[4], c[4], e[4];
-            if constexpr (MODE == NT_FWD) {
-              // revolutions: sin(2*pi*x) with x = omega*(z + b)/(2*pi) (packed fmas); fract keeps
-              // the hardware sin/cos inside their reduced domain for any magnitude.
-              float xa[4];
-              fma4_pk(acc[i][j], xs, bias[i], xa);
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const float x = __builtin_amdgcn_fractf(xa[r]);
-                s[r] = __builtin_amdgcn_sinf(x);
-                c[r] = __builtin_amdgcn_cosf(x);
-              }
-            } else if constexpr (MODE == NT_FWD_SNAKE) {
-              const float4 a4 = *(const float4*)(a_lds + nq + i * 16);
-              const float4 ia4 = *(const float4*)(ia_lds + nq + i * 16);
-              const float av[4] = {a4.x, a4.y, a4.z, a4.w}, iav[4] = {ia4.x, ia4.y, ia4.z, ia4.w};
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                snake_epi(acc[i][j][r] + bb[r], av[r], iav[r], s[r], c[r], e[r]);
-              }
-            } else {  // NT_FWD_TANH
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const float y = tanh_epi(acc[i][j][r] + bb[r]);
-                s[r] = y;
-                c[r] = 1.0f - y * y;
-              }
-            }
-            ys[h] = yh[i] = as_u2(pack4(s[0], s[1], s[2], s[3]));
-            cs[h] = chh[i] = as_u2(pack4(c[0], c[1], c[2], c[3]));
-            if constexpr (MODE == NT_FWD_SNAKE) es[h] = eh[i] = as_u2(pack4(e[0], e[1], e[2], e[3]));
-            if constexpr (HEAD) hp[j] += dot4_pk(s, hw[i]);
-          }
-          if constexpr (!(Lay::LINES || Lay::HALF)) {
-            yp[pp] = swap16_pair(ys[0], ys[1]);
-            cpk[pp] = swap16_pair(cs[0], cs[1]);
-            if constexpr (MODE == NT_FWD_SNAKE) epk[pp] = swap16_pair(es[0], es[1]);
-          }
-        }
-        if (SIREN_DIAG_ON && (diag & 2048)) {  // diag bit 11: the epilogue without its stores (timing only)
-          unsigned keep = 0;
-#pragma unroll
-          for (int i = 0; i < SN; ++i) keep ^= yh[i].x ^ yh[i].y ^ chh[i].x ^ chh[i].y;
-          asm volatile("" ::"v"(keep));
-          continue;
-        }
-        if constexpr (Lay::LINES && MODE == NT_FWD && !HEAD) {
-          // a row apart: row j-1's stores after row j's arithmetic, row j's exchange now
-          if (j > 0) {
-            lines_put(p.Y, mrowu + (j - 1) * 16, n0 + wn * TN, ly);
-            lines_put(p.C, mrowu + (j - 1) * 16, n0 + wn * TN, lc);
-          }
-          lines_get(yh, ly);
-          lines_get(chh, lc);
-          if (j == SM - 1) {
-            lines_put(p.Y, mrowu + j * 16, n0 + wn * TN, ly);
-            lines_put(p.C, mrowu + j * 16, n0 + wn * TN, lc);
-          }
-          continue;
-        }
-        if constexpr (Lay::LINES || Lay::HALF) {
-          // whole-line stores (lines_out): forward -4.6%, cfg4 -6.5% (static walk,
-          // profiles/r19/ab_full_lines.json)
-          lines_out(p.Y, mrowu + j * 16, n0 + wn * TN, yh);
-          lines_out(p.C, mrowu + j * 16, n0 + wn * TN, chh);
-          if constexpr (MODE == NT_FWD_SNAKE) lines_out(p.E, mrowu + j * 16, n0 + wn * TN, eh);
-          continue;
-        }
-#pragma unroll
-        for (int pp = 0; pp < SN / 2; ++pp) {
-          // (per-lane addresses here: the head forward has no registers for at_lane's copies -- Snake spilled)
-          st16(p.Y + rowoff + npc + pp * 32, yp[pp]);
-          st16(p.C + rowoff + npc + pp * 32, cpk[pp]);
-          if constexpr (MODE == NT_FWD_SNAKE) st16(p.E + rowoff + npc + pp * 32, epk[pp]);
-        }
-      }
-      if constexpr (HEAD) {
-        // lanes l, l^16, l^32, l^48 hold the same row: fold them, then the WN column waves.
-#pragma unroll
-        for (int j = 0; j < SM; ++j) {
-          hp[j] += __shfl_xor(hp[j], 16, 64);
-          hp[j] += __shfl_xor(hp[j], 32, 64);
-        }
-        if (lane < 16) {
-#pragma unroll
-          for (int j = 0; j < SM; ++j) red[wn * BM + wm * TM + j * 16 + lane] = hp[j];
-        }
-        lds_barrier();
-        if (tid < BM) {
-          float s = 0.f;
-#pragma unroll
-          for (int w = 0; w < WN; ++w) s += red[w * BM + tid];
-          p.head_part[(size_t)tn * p.M + m0 + tid] = s;
-        }
-      }
-    } else {
-      // column sums over this tile's BM rows (db / dW0 partials): per lane over its SM row
-      // tiles, over the 16 row-lanes by DPP, then over the WM row waves through LDS.
-      const int in_dim = nt_is_dx0(MODE) ? p.in_dim : 0;
-      const int nred = (MODE == NT_DX_SNAKE) ? 2 : (MODE == NT_DX0_SNAKE ? 2 + in_dim : 1 + in_dim);
-      // slots: 0 db; 1..in dW0 (NT_DX0*); 1 da (NT_DX_SNAKE); 3 da0 (NT_DX0_SNAKE, written as 1+in)
-      float cs[4][SN][4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int i = 0; i < SN; ++i)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) cs[q][i][r] = 0.f;
-
-      const float om = p.omega;
-      // partial layout: NT_DX [tm][N]; NT_DX0 [tm][1+in][N] with q=0 -> db0, q=1+j -> dW0[:, j];
-      // NT_DX_SNAKE [tm][2][N] with q=0 -> db, q=1 -> da.  flush(i): column subtile i's partials
-      // over this wave's rows (DPP across the 16 row lanes) into the LDS scratch
-      auto flush = [&](auto ic) {
-        constexpr int i = decltype(ic)::value;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (q >= nred) break;
-          // NT_DX0_SNAKE: da0 (slot 3) goes out as partial row 1 + in
-          const bool da0 = (MODE == NT_DX0_SNAKE) && q == nred - 1;
-          float v[4];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[r] = da0 ? cs[3][i][r] : cs[q][i][r];
-          row16_sum4(v);
-          if ((lane & 15) == 0)
-            *(float4*)(red + (q * Cfg::WM + wm) * BN + wn * TN + i * 16 + 4 * (lane >> 4)) =
-                float4{v[0], v[1], v[2], v[3]};
-        }
-      };
-      // the 16-B piece (row subtile j, column pair pp) from its Cprev (and Eprev) piece.  Each column
-      // partial sums its rows in order 0 .. SM-1 whatever order the pieces go in
-      // NT_DX_SNAKE with whole-line stores (Lay::LINES): a row piece's MFMA-layout halves (the Snake batches
-      // below take both column pairs of a row back to back, pair 1 last)
-      uint2 dzrow[SN];
-      auto piece = [&](auto jc, auto ppc, const uint4& cpv, const uint4& epv) {
-        constexpr int j = decltype(jc)::value, pp = decltype(ppc)::value;
-        const size_t rowoff = (size_t)(mrow0 + j * 16) * LD;
-        float t0 = 0.f, t1 = 0.f;
-        if constexpr (nt_is_dx0(MODE)) {
-          t0 = t_in[j][0];
-          t1 = t_in[j][1];
-        }
-        uint2 cpu[2];
-        unswap16_pair(cpv, cpu[0], cpu[1]);
-        uint2 epu[2];
-        if constexpr (HAS_E) unswap16_pair(epv, epu[0], epu[1]);
-        uint2 dzp[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int i = 2 * pp + h;
-          // (acc C) omega, paired as in the NT_DX / NT_DX0 loop below
-          f32x2 d01 = f32x2{mul_mix<0>(acc[i][j][0], cpu[h]), mul_mix<1>(acc[i][j][1], cpu[h])} * f32x2{om, om};
-          f32x2 d23 = f32x2{mul_mix<2>(acc[i][j][2], cpu[h]), mul_mix<3>(acc[i][j][3], cpu[h])} * f32x2{om, om};
-          asm volatile("" : "+v"(d01), "+v"(d23));  // rounded to fp32 before the fp16 store (fp32_first)
-          set4(cs[0][i], f32x2{cs[0][i][0], cs[0][i][1]} + d01, f32x2{cs[0][i][2], cs[0][i][3]} + d23);
-          if constexpr (nt_is_dx0(MODE)) {
-            set4(cs[1][i], __builtin_elementwise_fma(d01, f32x2{t0, t0}, f32x2{cs[1][i][0], cs[1][i][1]}),
-                 __builtin_elementwise_fma(d23, f32x2{t0, t0}, f32x2{cs[1][i][2], cs[1][i][3]}));
-            set4(cs[2][i], __builtin_elementwise_fma(d01, f32x2{t1, t1}, f32x2{cs[2][i][0], cs[2][i][1]}),
-                 __builtin_elementwise_fma(d23, f32x2{t1, t1}, f32x2{cs[2][i][2], cs[2][i][3]}));
-          }
-          static_for<0, 4>([&](auto rc) {
-            constexpr int r = decltype(rc)::value;
-            if constexpr (MODE == NT_DX_SNAKE) cs[1][i][r] = fma_mix<r>(acc[i][j][r], epu[h], cs[1][i][r]);
-            if constexpr (MODE == NT_DX0_SNAKE) cs[3][i][r] = fma_mix<r>(acc[i][j][r], epu[h], cs[3][i][r]);
-          });
-          dzp[h] = as_u2(pack4(d01.x, d01.y, d23.x, d23.y));
-        }
-        if constexpr (MODE == NT_DX_SNAKE && Lay::LINES) {
-          dzrow[2 * pp] = dzp[0];
-          dzrow[2 * pp + 1] = dzp[1];
-          if constexpr (pp == SN / 2 - 1) lines_out(p.dZ, mrowu + j * 16, n0 + wn * TN, dzrow);
-        } else if constexpr (MODE == NT_DX || MODE == NT_DX_SNAKE) {
-          st16((h16*)at_lane(rowp(p.dZ, mrowu + j * 16, n0 + wn * TN), lane_piece + pp * 64), swap16_pair(dzp[0], dzp[1]));
-        }
-      };
-      if constexpr (HAS_E) {
-        // batches of EB rows, both column pairs of a row back to back: the two 64-B halves of each
-        // row's 128-B Cprev / Eprev / dZ segments are read and written together (pair 0 of the
-        // first EB rows comes from `pre`)
-        static_assert(SN == 4, "two column pairs");
-        // software-pipelined: batch bq+1 is loaded before batch bq's dZ stores go out, so waiting
-        // for a batch never waits for earlier stores (vmcnt retires in issue order)
-        uint4 cq[2][EB][2], eq[2][EB][2];  // [buffer][row][column pair]
-        auto load_batch = [&](auto bqc) {
-          constexpr int bq = decltype(bqc)::value, bf = bq & 1;
-#pragma unroll
-          for (int jj = 0; jj < EB; ++jj)
-#pragma unroll
-            for (int pp = 0; pp < 2; ++pp) {
-              if (bq == 0 && pp == 0) {
-                cq[bf][jj][pp] = ce_in[jj][0];
-                eq[bf][jj][pp] = ce_in[jj][1];
-              } else {
-                const int ru = mrowu + (bq * EB + jj) * 16;
-                cq[bf][jj][pp] = *(const uint4*)at_lane(rowp(p.Cprev, ru, n0 + wn * TN), lane_piece + pp * 64);
-                eq[bf][jj][pp] = *(const uint4*)at_lane(rowp(p.Eprev, ru, n0 + wn * TN), lane_piece + pp * 64);
-              }
-            }
-        };
-        load_batch(std::integral_constant<int, 0>{});
-        static_for<0, SM / EB>([&](auto bqc) {
-          constexpr int bq = decltype(bqc)::value, bf = bq & 1;
-          if constexpr (bq + 1 < SM / EB) load_batch(std::integral_constant<int, bq + 1>{});
-          static_for<0, EB>([&](auto jc) {
-            constexpr int jj = decltype(jc)::value;
-            piece(std::integral_constant<int, bq * EB + jj>{}, std::integral_constant<int, 0>{}, cq[bf][jj][0], eq[bf][jj][0]);
-            piece(std::integral_constant<int, bq * EB + jj>{}, std::integral_constant<int, 1>{}, cq[bf][jj][1], eq[bf][jj][1]);
-          });
-        });
-        static_for<0, SN>([&](auto ic) { flush(ic); });
-      } else {
-        // NT_DX / NT_DX0: rows in order, both column pairs of a row together (rows >= PRE_J loaded
-        // at use), then the column partials.  The same arithmetic as `piece`, kept as a plain loop:
-        // written through the lambda, NT_DX0 takes 252-256 VGPRs instead of 239-244 (gfx950 listing)
-        uint4 ldz[2];  // NT_DX: row j-1's dZ line chunks
-#pragma unroll
-        for (int j = 0; j < SM; ++j) {
-          const size_t rowoff = (size_t)(mrow0 + j * 16) * LD;
-          float t0 = 0.f, t1 = 0.f;
-          if constexpr (nt_is_dx0(MODE)) {
-            t0 = t_in[j][0];
-            t1 = t_in[j][1];
-          }
-          uint2 dzq[SN];  // NT_DX with whole-line stores: this row piece's MFMA-layout halves
-#pragma unroll
-          for (int pp = 0; pp < SN / 2; ++pp) {
-            uint2 cpu[2];
-            const uint4 cpv =
-                (j < PRE_J) ? cp_in[j < PRE_J ? j : 0][pp]
-                            : *(const uint4*)at_lane(rowp(p.Cprev, mrowu + j * 16, n0 + wn * TN), lane_piece + pp * 64);
-            unswap16_pair(cpv, cpu[0], cpu[1]);
-            uint2 dzp[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              const int i = 2 * pp + h;
-              // (acc C) omega: the fp16 product in v_fma_mix_f32, the rest in pairs (v_pk_mul_f32,
-              // v_pk_add_f32, v_pk_fma_f32: per element the rounding of the scalar instruction)
-              f32x2 d01 = f32x2{mul_mix<0>(acc[i][j][0], cpu[h]), mul_mix<1>(acc[i][j][1], cpu[h])} * f32x2{om, om};
-              f32x2 d23 = f32x2{mul_mix<2>(acc[i][j][2], cpu[h]), mul_mix<3>(acc[i][j][3], cpu[h])} * f32x2{om, om};
-              asm volatile("" : "+v"(d01), "+v"(d23));  // rounded to fp32 before the fp16 store (fp32_first)
-              set4(cs[0][i], f32x2{cs[0][i][0], cs[0][i][1]} + d01, f32x2{cs[0][i][2], cs[0][i][3]} + d23);
-              if constexpr (nt_is_dx0(MODE)) {
-                set4(cs[1][i], __builtin_elementwise_fma(d01, f32x2{t0, t0}, f32x2{cs[1][i][0], cs[1][i][1]}),
-                     __builtin_elementwise_fma(d23, f32x2{t0, t0}, f32x2{cs[1][i][2], cs[1][i][3]}));
-                set4(cs[2][i], __builtin_elementwise_fma(d01, f32x2{t1, t1}, f32x2{cs[2][i][0], cs[2][i][1]}),
-                     __builtin_elementwise_fma(d23, f32x2{t1, t1}, f32x2{cs[2][i][2], cs[2][i][3]}));
-              }
-              dzp[h] = as_u2(pack4(d01.x, d01.y, d23.x, d23.y));
-            }
-            if constexpr (Lay::LINES && MODE == NT_DX) {
-              dzq[2 * pp] = dzp[0];
-              dzq[2 * pp + 1] = dzp[1];
-            }
-            else if constexpr (MODE == NT_DX)
-              st16((h16*)at_lane(rowp(p.dZ, mrowu + j * 16, n0 + wn * TN), lane_piece + pp * 64), swap16_pair(dzp[0], dzp[1]));
-          }
-          if constexpr (Lay::LINES && MODE == NT_DX) {
-            // a row apart, as the forward: row j-1's stores after row j's arithmetic
-            if (j > 0) lines_put(p.dZ, mrowu + (j - 1) * 16, n0 + wn * TN, ldz);
-            lines_get(dzq, ldz);
-            if (j == SM - 1) lines_put(p.dZ, mrowu + j * 16, n0 + wn * TN, ldz);
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          if (q >= nred) break;
-#pragma unroll
-          for (int i = 0; i < SN; ++i) {
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = cs[q][i][r];
-            row16_sum4(v);
-            if ((lane & 15) == 0)
-              *(float4*)(red + (q * Cfg::WM + wm) * BN + wn * TN + i * 16 + 4 * (lane >> 4)) =
-                  float4{v[0], v[1], v[2], v[3]};
-          }
-        }
-      }
-      lds_barrier();
-      if (tid < BN) {
-        for (int q = 0; q < nred; ++q) {
-          float s = 0.f;
-#pragma unroll
-          for (int w = 0; w < Cfg::WM; ++w) s += red[(q * Cfg::WM + w) * BN + tid];
-          p.colsum_part[((size_t)tm * nred + q) * LD + n0 + tid] = s * inv_scale;
-        }
-      }
-    }
+    nt_epilogue(acc, m0, n0, w, p, in);
   };
 
   if constexpr (Cfg::PP) {
@@ -1277,6 +1333,8 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_nt_kernel(NtParams p) {
             __builtin_amdgcn_mfma_f32_16x16x32_f16(a, xf[jl][kk], acc[2 * NH + il][4 * MH + jl], 0, 0, 0);
       }
     };
+    // A pull of the dynamic queue is one returning agent-scope atomic add on the block's shard head,
+    // issued at the start of a tile's epilogue and consumed after it (see the tile-queue comment above)
     auto tile_end = [&](int) {
       // both groups are aligned here
       pre(g_cur);
@@ -1294,14 +1352,10 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_nt_kernel(NtParams p) {
 #pragma unroll
         for (int j = 0; j < SM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
     };
-    if constexpr (SIREN_NT_SEG2 != 0)
-      // EARLY (the next tile's K-tile 1 piece 3 before the epilogue's stores): the fused last layer
-      // gains 2.3% (cfg2) / 0.8% (cfg4), the plain forward loses 2.3% at cfg2 (profiles/r20/ab_early.json)
-      pingpong2_tiles<epilogue_stores<Cfg, MODE>(), SIREN_NT_EARLY != 0 || nt_is_hb(MODE) || MODE == NT_DX0>(
-          in_range(g_cur), nk, wm, issue, read, mma, set_tiles, tile_end, more);
-    else
-      pingpong_tiles<epilogue_stores<Cfg, MODE>(), 0xB>(in_range(g_cur), nk, wm, issue, read, mma, set_tiles,
-                                                         tile_end, more);
+    // EARLY (the next tile's K-tile 1 piece 3 before the epilogue's stores): the fused last layer
+    // gains 2.3% (cfg2) / 0.8% (cfg4), the plain forward loses 2.3% at cfg2 (profiles/r20/ab_early.json)
+    pingpong2_tiles<epilogue_stores<Cfg, MODE>(), SIREN_NT_EARLY != 0 || nt_is_hb(MODE) || MODE == NT_DX0>(
+        in_range(g_cur), nk, wm, issue, read, mma, set_tiles, tile_end, more);
   } else {
     mfma_pipeline_tiles<Cfg::S, BK / 32, Cfg::XINSTR + Cfg::WINSTR, SN, SM, epilogue_stores<Cfg, MODE>()>(
         my_tiles, K / BK, acc, stage, frags, [&](int ti) { pre(bp + ti * G); },
@@ -1311,10 +1365,16 @@ __global__ __launch_bounds__(Cfg::THREADS, 2) void gemm_nt_kernel(NtParams p) {
 
 static int g_num_cus[64] = {};
 
-// CU count of the stream's device (queried once per device)
-static int stream_cus(hipStream_t s) {
+// the stream's device (the current one, then 0, when the stream does not tell)
+static int stream_device(hipStream_t s) {
   int dev = 0;
   if (hipStreamGetDevice(s, &dev) != hipSuccess && hipGetDevice(&dev) != hipSuccess) dev = 0;
+  return dev;
+}
+
+// CU count of the stream's device (queried once per device)
+static int stream_cus(hipStream_t s) {
+  const int dev = stream_device(s);
   if (dev < 0 || dev >= 64) return 256;
   if (g_num_cus[dev] <= 0) {
     int n = 0;
@@ -1384,15 +1444,20 @@ static hipError_t launch_nt(const NtParams& p_in, hipStream_t s, bool persistent
   return hipGetLastError();
 }
 
+// the fused kernel of one last-layer kind, as the occupancy query takes it
+template <int MODE>
+static const void* hb_kernel() {
+  return reinterpret_cast<const void*>(&gemm_nt_kernel<NtLargePP, MODE, true>);
+}
+
 static bool hb_coresident(int mode, int grid, hipStream_t s) {
-  int dev = 0;
-  if (hipStreamGetDevice(s, &dev) != hipSuccess && hipGetDevice(&dev) != hipSuccess) dev = 0;
+  const int dev = stream_device(s);
   if (dev < 0 || dev >= 64 || !nt_is_hb(mode)) return false;
   int& per_cu = g_hb_per_cu[mode - NT_FWD_HB][dev];
   if (per_cu == 0) {
-    const void* fn = mode == NT_FWD_HB         ? reinterpret_cast<const void*>(&gemm_nt_kernel<NtLargePP, NT_FWD_HB, true>)
-                     : mode == NT_FWD_HB_SNAKE ? reinterpret_cast<const void*>(&gemm_nt_kernel<NtLargePP, NT_FWD_HB_SNAKE, true>)
-                                               : reinterpret_cast<const void*>(&gemm_nt_kernel<NtLargePP, NT_FWD_HB_TANH, true>);
+    const void* fn = mode == NT_FWD_HB         ? hb_kernel<NT_FWD_HB>()
+                     : mode == NT_FWD_HB_SNAKE ? hb_kernel<NT_FWD_HB_SNAKE>()
+                                               : hb_kernel<NT_FWD_HB_TANH>();
     int n = 0;
     const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, NtLargePP::THREADS, 0);
     per_cu = (e == hipSuccess && n > 0) ? n : -1;
@@ -1412,27 +1477,23 @@ static hipError_t dispatch_mode(int mode, bool head, const NtParams& p, hipStrea
   return hipErrorInvalidValue;
 }
 
-// first_linear=True: dX into the Linear + Snake first layer (default persistent K-loop / 128 tile)
-template <class Cfg>
-static hipError_t dispatch_dx0_snake(const NtParams& p, hipStream_t s, bool persistent) {
-  return launch_nt<Cfg, NT_DX0_SNAKE, false>(p, s, persistent);
-}
-
-// Snake / Tanh layers: the default persistent K-loop (or the 128x128 tile)
+// Snake / Tanh layers: the default persistent K-loop (or the 128x128 tile); the whole-line
+// epilogues (ACTL, see NtLds) on the ping-pong kernels at K <= 512 (the forwards with head partials have none)
 template <class Cfg>
 static hipError_t dispatch_act(int mode, bool head, const NtParams& p, hipStream_t s, bool persistent) {
+  const bool actl = (Cfg::PP && p.K <= 512);
   switch (mode) {
     case NT_FWD_SNAKE:
       if (head) return launch_nt<Cfg, NT_FWD_SNAKE, true>(p, s, persistent);
-      return (Cfg::PP && p.K <= 512) ? launch_nt<Cfg, NT_FWD_SNAKE, false, true>(p, s, persistent)
-                                     : launch_nt<Cfg, NT_FWD_SNAKE, false>(p, s, persistent);
+      return actl ? launch_nt<Cfg, NT_FWD_SNAKE, false, true>(p, s, persistent)
+                  : launch_nt<Cfg, NT_FWD_SNAKE, false>(p, s, persistent);
     case NT_FWD_TANH:
       if (head) return launch_nt<Cfg, NT_FWD_TANH, true>(p, s, persistent);
-      return (Cfg::PP && p.K <= 512) ? launch_nt<Cfg, NT_FWD_TANH, false, true>(p, s, persistent)
-                                     : launch_nt<Cfg, NT_FWD_TANH, false>(p, s, persistent);
+      return actl ? launch_nt<Cfg, NT_FWD_TANH, false, true>(p, s, persistent)
+                  : launch_nt<Cfg, NT_FWD_TANH, false>(p, s, persistent);
     case NT_DX_SNAKE:
-      return (Cfg::PP && p.K <= 512) ? launch_nt<Cfg, NT_DX_SNAKE, false, true>(p, s, persistent)
-                                     : launch_nt<Cfg, NT_DX_SNAKE, false>(p, s, persistent);
+      return actl ? launch_nt<Cfg, NT_DX_SNAKE, false, true>(p, s, persistent)
+                  : launch_nt<Cfg, NT_DX_SNAKE, false>(p, s, persistent);
   }
   return hipErrorInvalidValue;
 }
@@ -1470,14 +1531,15 @@ static hipError_t gemm_nt_window(int mode, bool head, const NtParams& p, hipStre
     return launch_nt<NtLargePP, NT_FWD_HB, true>(p, s, true);
   }
   if (nt_is_dx0(mode) && (p.in_dim < 1 || p.in_dim > 2)) return hipErrorInvalidValue;
-  if (mode == NT_DX0_SNAKE) {
+  if (mode == NT_DX0_SNAKE) {  // first_linear=True: dX into the Linear + Snake first layer
     if (!p.Eprev) return hipErrorInvalidValue;
     if (p.tile == 256) {
       if (p.M % 256 || p.N % 256) return hipErrorInvalidValue;
-      return nt_pp() ? dispatch_dx0_snake<NtLargePP>(p, s, true) : dispatch_dx0_snake<NtLarge>(p, s, true);
+      return nt_pp() ? launch_nt<NtLargePP, NT_DX0_SNAKE, false>(p, s, true)
+                     : launch_nt<NtLarge, NT_DX0_SNAKE, false>(p, s, true);
     }
     if (p.tile != 128) return hipErrorInvalidValue;
-    return dispatch_dx0_snake<NtSmall>(p, s, false);
+    return launch_nt<NtSmall, NT_DX0_SNAKE, false>(p, s, false);
   }
   if (mode >= NT_FWD_SNAKE && mode <= NT_DX_SNAKE) {
     if ((mode == NT_FWD_SNAKE && (!p.act_a || !p.E)) || (mode == NT_DX_SNAKE && !p.Eprev))

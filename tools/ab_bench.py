@@ -104,6 +104,9 @@ def main():
             act = 1 if kind == "fwd_snake" else 2
             return lambda: lib.siren_inner_fwd_act(P(X), P(W), P(b), act, ctypes.c_float(1.0), P(a_snake), R, H,
                                                    P(o["Y"]), P(o["C"]), P(o["E"]), None, None, P(tq), s())
+        if kind == "fwd_snake_head":  # the Snake forward with the head partials (an unfused Snake last layer)
+            return lambda: lib.siren_inner_fwd_act(P(X), P(W), P(b), 1, ctypes.c_float(1.0), P(a_snake), R, H,
+                                                   P(o["Y"]), P(o["C"]), P(o["E"]), P(hw), P(o["hp"]), P(tq), s())
         if kind == "dw":
             return lambda: lib.siren_inner_bwd_dw(P(X), P(dZ), R, H, splits, 0, P(o["slab"]), s())
         raise ValueError(kind)
@@ -127,6 +130,7 @@ def main():
                 got[nm] = {"fwd": (o["Y"], o["C"]), "fwd_head": (o["Y"], o["C"], o["hp"]), "dx": (o["dZp"], o["part"]),
                            "dx_snake": (o["dZp"], o["part"]), "dx_tanh": (o["dZp"], o["part"]),
                            "fwd_snake": (o["Y"], o["C"], o["E"]), "fwd_tanh": (o["Y"], o["C"]),
+                           "fwd_snake_head": (o["Y"], o["C"], o["E"], o["hp"]),
                            "dx0": (o["part"],), "fwd_hb": (o["out"], o["g"], o["sse"], o["dZp"], o["part"]),
                            "dw": (o["slab"],)}[k]
                 got[nm] = tuple(x.clone() for x in got[nm])
@@ -159,7 +163,7 @@ def main():
     for (nm, k), ts in times.items():
         ts = sorted(ts)
         med = ts[len(ts) // 2]
-        res.setdefault(k, {})[nm] = {"median_ms": round(med, 4), "min_ms": round(ts[0], 4),
+        res.setdefault(k, {})[nm] = {"median_ms": round(med, 4), "min_ms": round(ts[0], 4), "max_ms": round(ts[-1], 4),
                                      "frac": round(flops / (med * 1e-3) / 2.5e15, 4)}
     print(json.dumps({"rows": R, "hidden": H, "rounds": args.rounds, "bit_identical": mism, "results": res},
                      indent=1))

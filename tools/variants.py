@@ -23,64 +23,65 @@ CSRC = os.path.join(ROOT, "inr-for-audio_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "inr-for-audio_amd"))
 from buildinfo import SOURCES  # noqa: E402  (the product library's source list)
 
-_ST16 = "  auto st16 = [&](h16* dst, uint4 v) { *(uint4*)dst = v; };"
+_ST16 = "__device__ __forceinline__ void st16(h16* dst, uint4 v) { *(uint4*)dst = v; }"
 
 
 def _st16_asm(pol: str) -> str:
     # the asm store carries its own s_nop: a VALU write of the data VGPRs must wait a cycle after a
     # 128-bit store, which hipcc's hazard recognizer does not see inside inline asm
-    return ("  auto st16 = [&](h16* dst, uint4 v) {\n"
-            "    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));\n"
-            "    const u32x4 w = u32x4{v.x, v.y, v.z, v.w};\n"
-            f"    asm volatile(\"global_store_dwordx4 %0, %1, off {pol}\\n\\ts_nop 1\" ::\"v\"(dst), \"v\"(w) : \"memory\");\n"
-            "  };")
+    return ("__device__ __forceinline__ void st16(h16* dst, uint4 v) {\n"
+            "  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));\n"
+            "  const u32x4 w = u32x4{v.x, v.y, v.z, v.w};\n"
+            f"  asm volatile(\"global_store_dwordx4 %0, %1, off {pol}\\n\\ts_nop 1\" ::\"v\"(dst), \"v\"(w) : \"memory\");\n"
+            "}")
 
 
 # forward epilogue stores through buffer descriptors of the wave's 128-row band (base in SGPRs,
 # one 32-bit lane offset, the row subtile in soffset) instead of 64-bit per-lane addresses
-_BST_OLD1 = """      float hp[SM];
+_BST_OLD1 = """  float hp[SM];
 #pragma unroll
-      for (int j = 0; j < SM; ++j) hp[j] = 0.f;"""
-_BST_NEW1 = """      float hp[SM];
+  for (int j = 0; j < SM; ++j) hp[j] = 0.f;"""
+_BST_NEW1 = """  float hp[SM];
 #pragma unroll
-      for (int j = 0; j < SM; ++j) hp[j] = 0.f;
-      const size_t obase = (size_t)(m0 + wm * TM) * N + n0;
-      const auto rsy = __builtin_amdgcn_make_buffer_rsrc(p.Y + obase, (short)0, TM * N * 2, 0x00020000);
-      const auto rsc = __builtin_amdgcn_make_buffer_rsrc(p.C + obase, (short)0, TM * N * 2, 0x00020000);
-      const int qv = ((lane & 15) * N + wn * TN + swap16_col(lane)) * 2;
-      typedef unsigned u32x4 __attribute__((ext_vector_type(4)));"""
-_BST_OLD2 = """          st16(p.Y + rowoff + npc + pp * 32, yp[pp]);
-          st16(p.C + rowoff + npc + pp * 32, cpk[pp]);"""
-_BST_NEW2 = """          if constexpr (MODE == NT_FWD) {
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{yp[pp].x, yp[pp].y, yp[pp].z, yp[pp].w}, rsy, qv + pp * 64,
-                                                   j * 16 * N * 2, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{cpk[pp].x, cpk[pp].y, cpk[pp].z, cpk[pp].w}, rsc,
-                                                   qv + pp * 64, j * 16 * N * 2, 0);
-          } else {
-            st16(p.Y + rowoff + npc + pp * 32, yp[pp]);
-            st16(p.C + rowoff + npc + pp * 32, cpk[pp]);
-          }"""
+  for (int j = 0; j < SM; ++j) hp[j] = 0.f;
+  const int N = p.N;
+  const size_t obase = (size_t)(m0 + w.wm * TM) * N + n0;
+  const auto rsy = __builtin_amdgcn_make_buffer_rsrc(p.Y + obase, (short)0, TM * N * 2, 0x00020000);
+  const auto rsc = __builtin_amdgcn_make_buffer_rsrc(p.C + obase, (short)0, TM * N * 2, 0x00020000);
+  const int qv = ((lane & 15) * N + w.wn * TN + swap16_col(lane)) * 2;
+  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));"""
+_BST_OLD2 = """      st16(p.Y + rowoff + npc + pp * 32, yp[pp]);
+      st16(p.C + rowoff + npc + pp * 32, cpk[pp]);"""
+_BST_NEW2 = """      if constexpr (MODE == NT_FWD) {
+        __builtin_amdgcn_raw_buffer_store_b128(u32x4{yp[pp].x, yp[pp].y, yp[pp].z, yp[pp].w}, rsy, qv + pp * 64,
+                                               j * 16 * N * 2, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(u32x4{cpk[pp].x, cpk[pp].y, cpk[pp].z, cpk[pp].w}, rsc,
+                                               qv + pp * 64, j * 16 * N * 2, 0);
+      } else {
+        st16(p.Y + rowoff + npc + pp * 32, yp[pp]);
+        st16(p.C + rowoff + npc + pp * 32, cpk[pp]);
+      }"""
 
 # fused head (NT_FWD_HB) cost split: no hand-off (each block uses its own partial for all column
 # tiles: WRONG g, timing only)
-_HB_WAIT_OLD = """            while ((u = __hip_atomic_load(hpu + (size_t)jt * p.M + m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) ==
-                   kHeadPending) {"""
-_HB_WAIT_NEW = """            u = __float_as_uint(own) + jt;
-            while (polls == 12345) {"""
+_HB_WAIT_OLD = """        while ((u = __hip_atomic_load(hpu + (size_t)jt * p.M + m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) ==
+               kHeadPending) {"""
+_HB_WAIT_NEW = """        u = __float_as_uint(own) + jt;
+        while (polls == 12345) {"""
 
 # forward stores folded onto the first 512 rows of Y / C (1 MB each: L2-resident, no HBM write-back):
 # WRONG outputs, timing only -- prices the forward's 4.3 GB of output writes against HBM
-_L2ST_OLD = """          st16(p.Y + rowoff + npc + pp * 32, yp[pp]);
-          st16(p.C + rowoff + npc + pp * 32, cpk[pp]);"""
-_L2ST_NEW = """          st16(p.Y + (rowoff & (size_t)(512 * N - 1)) + npc + pp * 32, yp[pp]);
-          st16(p.C + (rowoff & (size_t)(512 * N - 1)) + npc + pp * 32, cpk[pp]);"""
+_L2ST_OLD = """      st16(p.Y + rowoff + npc + pp * 32, yp[pp]);
+      st16(p.C + rowoff + npc + pp * 32, cpk[pp]);"""
+_L2ST_NEW = """      st16(p.Y + (rowoff & (size_t)(512 * p.N - 1)) + npc + pp * 32, yp[pp]);
+      st16(p.C + (rowoff & (size_t)(512 * p.N - 1)) + npc + pp * 32, cpk[pp]);"""
 
 # forward epilogue computes everything but issues no stores (a never-true guard keeps the values):
 # WRONG outputs, timing only -- the epilogue's VALU alone against its stores
-_NOST_NEW = """          if (yp[pp].x == 0x12345u && cpk[pp].y == 0x6789u) {
-            st16(p.Y + rowoff + npc + pp * 32, yp[pp]);
-            st16(p.C + rowoff + npc + pp * 32, cpk[pp]);
-          }"""
+_NOST_NEW = """      if (yp[pp].x == 0x12345u && cpk[pp].y == 0x6789u) {
+        st16(p.Y + rowoff + npc + pp * 32, yp[pp]);
+        st16(p.C + rowoff + npc + pp * 32, cpk[pp]);
+      }"""
 
 # dW GEMM operands from 8 K-steps of the slice only (L2-resident Y and dZ): WRONG dW, timing only --
 # prices the dW K-loop's operand latency
@@ -132,10 +133,10 @@ VARIANTS["stnt0"] = {}
 # the XCD's L2 instead of keeping it (MI355X_MICROARCH.md store table) -- do 8 MB of Y / C per tile round
 # stop evicting W and X?  (asm stores are invisible to hipcc's vmcnt counting: its waits only get stricter;
 # the s_nop covers the store-data VGPR write hazard hipcc cannot see inside asm, as _st16_asm's)
-_STSC1 = ('      stl((h16*)(ub + (size_t)(16 * q) * LD + lq), line[q]);',
-          '      { typedef unsigned u32x4 __attribute__((ext_vector_type(4)));\n'
-          '        asm volatile("global_store_dwordx4 %0, %1, %2 sc1\\n\\ts_nop 1" :: "v"(lq), "v"(__builtin_bit_cast(u32x4, line[q])),\n'
-          '                     "s"(ub + (size_t)(16 * q) * LD) : "memory"); }')
+_STSC1 = ('    stl((h16*)(ub + (size_t)(16 * q) * w.LD + lq), line[q]);',
+          '    { typedef unsigned u32x4 __attribute__((ext_vector_type(4)));\n'
+          '      asm volatile("global_store_dwordx4 %0, %1, %2 sc1\\n\\ts_nop 1" :: "v"(lq), "v"(__builtin_bit_cast(u32x4, line[q])),\n'
+          '                   "s"(ub + (size_t)(16 * q) * w.LD) : "memory"); }')
 VARIANTS["stsc1"] = {"gemm_nt.hip": [_STSC1]}
 # PROBE (wrong outputs, timing only): group 0 (waves 0-3) issues every LDS-DMA and stores nothing, group 1
 # (waves 4-7) stores its own lines twice (its rows and group 0's: the same bytes) and never waits on vmcnt
@@ -164,15 +165,15 @@ VARIANTS["dmag0"] = {"gemm_nt.hip": [
           glds16x2o_asm_s(lane_src, lane_src8, (const char*)src + urowp[PC][0], lds_addr(dst + pdstp[PC][0]));
         }
       } else {"""),
-    ("""      stl((h16*)(ub + (size_t)(16 * q) * LD + lq), line[q]);
+    ("""    stl((h16*)(ub + (size_t)(16 * q) * w.LD + lq), line[q]);
+  }
+}""",
+     """    if (w.wm == 1) {
+      stl((h16*)(ub + (size_t)(16 * q) * w.LD + lq), line[q]);
+      stl((h16*)(ub - (size_t)256 * w.LD + (size_t)(16 * q) * w.LD + lq), line[q]);
     }
-  };""",
-     """      if (wm == 1) {
-        stl((h16*)(ub + (size_t)(16 * q) * LD + lq), line[q]);
-        stl((h16*)(ub - (size_t)256 * LD + (size_t)(16 * q) * LD + lq), line[q]);
-      }
-    }
-  };"""),
+  }
+}"""),
   ],
   "gemm_pipeline.h": [
     ("""    if constexpr (EARLY) {
@@ -194,12 +195,10 @@ VARIANTS["dmag0"] = {"gemm_nt.hip": [
 # its store half alone (both groups issue their DMAs and wait as in the product): group 1 stores its lines
 # twice, group 0 none (wrong outputs, timing only) -- dmag0 minus this = the DMA / store decoupling
 VARIANTS["st1x2"] = {"gemm_nt.hip": [VARIANTS["dmag0"]["gemm_nt.hip"][3]]}
-VARIANTS["lswap"] = {}
 # every ping-pong NT kernel with the EARLY tile boundary (the product takes it for the fused last layer and
 # dX0 only): round 5 measured the plain forward +2.3% at cfg2 and -2.3% at cfg4 -- a K-dependent choice?
 VARIANTS["early"] = {}
-DEFINES = {"glds0": ("SIREN_GLDS_PAIR=0",), "stnt0": ("SIREN_NT_STNT=0",), "lswap": ("SIREN_LINES_SWAP=1",),
-           "early": ("SIREN_NT_EARLY=1",)}
+DEFINES = {"glds0": ("SIREN_GLDS_PAIR=0",), "stnt0": ("SIREN_NT_STNT=0",), "early": ("SIREN_NT_EARLY=1",)}
 
 
 def apply(name: str) -> dict:
