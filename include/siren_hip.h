@@ -619,6 +619,33 @@ int siren_kan_train_step(const siren_kan_net* net, const siren_kan_grads* grads,
 int siren_kan_backward(const siren_kan_net* net, const siren_kan_grads* grads, siren_kan_batch* batch,
                        float* grad_coords, void* stream);
 
+/* ---- KAN grid update: KANLinear.update_grid of kan.py:168-215 for one layer ----------------
+ * The reference refits the layer's curves on new knots by a least-squares fit over the batch.  Per
+ * input i that fit is c_new[i] = G_nn[i]^-1 G_no[i] (spline_w[:, i, :] * scaler[:, i])^T with the
+ * 8 x 8 Gram matrices G_nn = sum_r b_new(x_ri) b_new(x_ri)^T and G_no = sum_r b_new(x_ri) b_old(x_ri)^T
+ * of the fp32 bases on the new and the old knots, summed in fp64 in a fixed order (two calls on the
+ * same data agree bit for bit).  The three steps are separate calls; none allocates or synchronises,
+ * and none writes a live parameter: the caller copies grid_new and spline_w_new over the layer's
+ * buffers once status reads {0, *}.  All pointers are device pointers. */
+/* rows that one pass of the Gram kernel's grid covers (more rows loop); -1: in < 1 */
+int64_t siren_kan_grid_pass_rows(int32_t in);
+/* bytes of the scratch `ws` of siren_kan_grid_gram over `rows` rows and of siren_kan_grid_refit
+ * (the larger of the two); -1 on a bad shape */
+int64_t siren_kan_grid_workspace_bytes(int64_t rows, int32_t in);
+/* kan.py:190-212 op for op in fp32: q [6][in] holds, per input, x_sorted at
+ * torch.linspace(0, rows - 1, 6, dtype=int64) (any exact selection); grid_new [in][12] */
+int siren_kan_grid_knots(const float* q, int32_t in, double margin, double grid_eps, float* grid_new, void* stream);
+/* gram [in][2][8][8] fp64 (G_nn, then G_no; [new basis][new / old basis]) over x [rows][in];
+ * accumulate != 0 adds to gram's contents (micro-batches of one update); x is read once */
+int siren_kan_grid_gram(const float* x, int64_t rows, int32_t in, const float* grid_old, const float* grid_new,
+                        int32_t accumulate, double* gram, void* ws, void* stream);
+/* kan.py:173-177, :215: spline_w_new [out][in][8] = fp32(G_nn^-1 G_no (spline_w * scaler)), by an
+ * fp64 Cholesky factorisation per input.  status [2]: the number of rank-deficient inputs (a pivot at
+ * or below 2^-40 x the largest diagonal entry of G_nn) and the lowest such index; their rows of
+ * spline_w_new are left unwritten */
+int siren_kan_grid_refit(const double* gram, int32_t in, int32_t out, const float* spline_w, const float* scaler,
+                         float* spline_w_new, int32_t* status, void* ws, void* stream);
+
 /* ---- per-launch HIP-event profiling of the fused path (bench.py) --------------------
  * siren_profile_enable(n) creates 2n hipEvents; while enabled every launch made by
  * siren_train_step / siren_backward / siren_forward / siren_apply_update (and the KAN

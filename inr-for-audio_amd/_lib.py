@@ -228,6 +228,12 @@ _SIGS = {
                                             ctypes.POINTER(SirenKanBatch), _p]),
     "siren_kan_backward": (ctypes.c_int, [ctypes.POINTER(SirenKanNet), ctypes.POINTER(SirenKanGrads),
                                           ctypes.POINTER(SirenKanBatch), _p, _p]),
+    # KANLinear.update_grid (kan.py:168-215): knots, Gram sums, refit
+    "siren_kan_grid_pass_rows": (_i64, [_i32]),
+    "siren_kan_grid_workspace_bytes": (_i64, [_i64, _i32]),
+    "siren_kan_grid_knots": (ctypes.c_int, [_p, _i32, ctypes.c_double, ctypes.c_double, _p, _p]),
+    "siren_kan_grid_gram": (ctypes.c_int, [_p, _i64, _i32, _p, _p, _i32, _p, _p, _p]),
+    "siren_kan_grid_refit": (ctypes.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _p, _p]),
     "siren_profile_enable": (ctypes.c_int, [_i32]),
     "siren_profile_reset": (ctypes.c_int, []),
     "siren_profile_mask": (ctypes.c_int, [ctypes.c_uint32]),

@@ -999,6 +999,19 @@ class KanEngine(FitEngine):
                                           self.hist_cap, s), "siren_plateau_step")
 
     @torch.no_grad()
+    def update_grid(self) -> torch.Tensor:
+        """model(coords, update_grid=True) (kan.py:274-279) on the engine's own weights, between
+        steps: every layer's knots move to its inputs' distribution and its curves are refitted, in
+        place in the flat parameter vector and the grid buffers, so the net struct and a captured
+        graph keep their pointers.  The Adam state, the scheduler and the history are untouched, as
+        in the reference, whose optimizer knows nothing of it.  Returns the updated model's output.
+        Single process only: a rank sees only its shard, and the knots need global order statistics."""
+        if _dist() is not None:
+            raise NotImplementedError("KanEngine.update_grid: one process only (global order statistics across "
+                                      "ranks are not implemented)")
+        return self.model(self.coords, update_grid=True)
+
+    @torch.no_grad()
     def infer(self, coords: torch.Tensor, chunk: int | None = None) -> torch.Tensor:
         from .kan import kan_forward
         return kan_forward(self.model, coords.reshape(-1, self.model.widths[0]), self.device,

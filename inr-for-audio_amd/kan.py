@@ -13,8 +13,10 @@ standalone spline scaler.  ``KAN.forward`` and ``KANLinear.forward`` are differe
 (``_KanFunction``: siren_kan_forward, then siren_kan_backward for any upstream gradient, into the
 parameters and, when asked for, the input), so a user loop with ``loss.backward()`` and
 ``torch.optim`` trains them as it trains the reference's modules (kan.py:153-166, 268-273); the
-fused fit goes through ``KanEngine`` / ``run.train(arch='kan')``.  Grid updates and the
-regularisation loss (not used by run.py) are not on the path.
+fused fit goes through ``KanEngine`` / ``run.train(arch='kan')``.  ``KANLinear.update_grid`` /
+``KAN.forward(x, update_grid=True)`` (kan.py:168-215, :274-279) run on the HIP path too
+(siren_kan_grid_*: knots, per-input Gram sums in fp64, Cholesky refit); ``regularization_loss``
+(kan.py:217-237, :281-285) is the reference's torch expression on the parameters.
 """
 from __future__ import annotations
 
@@ -93,6 +95,58 @@ class KANLinear(torch.nn.Module):
         _hip_check_layer(self)
         return _kan_apply([self.in_features, self.out_features], [self], x,
                           [self.base_weight, self.spline_weight, self.spline_scaler])
+
+    @torch.no_grad()
+    def update_grid(self, x: torch.Tensor, margin=0.01, chunk: int = 1 << 20):
+        """kan.py:168-215 on the HIP path: new knots from the order statistics of x (batch, in), then
+        the curves refitted on them over the batch -- through the 8 x 8 Gram matrices of the bases
+        per input (siren_kan_grid_*), not the reference's (batch, in, out) intermediate and lstsq.
+        Like the reference the refit targets the scaled curves and stores the result in
+        spline_weight undivided.  `grid` and `spline_weight` are written in place, and only once the
+        refit succeeded: an input whose Gram matrix is rank deficient (a constant input, fewer than
+        8 distinct useful samples) raises SirenError and leaves the layer as it was."""
+        _hip_check_layer(self)
+        if not x.is_cuda:
+            raise RuntimeError("KANLinear.update_grid runs on the HIP path only (CUDA tensors)")
+        if x.dim() != 2 or x.size(1) != self.in_features:
+            raise ValueError(f"update_grid: x must be (batch, {self.in_features})")
+        lib, dev = _lib.load(), x.device
+        s = torch.cuda.current_stream(dev).cuda_stream
+        n_in, n_out, rows = self.in_features, self.out_features, x.size(0)
+        xs = x.detach().float().contiguous()
+        # order statistics: any exact selection will do; the indices are the reference's own call
+        idx = torch.linspace(0, rows - 1, self.grid_size + 1, dtype=torch.int64)
+        q = torch.sort(xs, dim=0)[0][idx.to(dev)].contiguous()
+        grid_new = torch.empty_like(self.grid)
+        check(lib.siren_kan_grid_knots(ptr(q), n_in, float(margin), float(self.grid_eps), ptr(grid_new), s),
+              "siren_kan_grid_knots")
+        rows_c = max(1, min(int(chunk), rows))
+        ws = torch.empty(int(lib.siren_kan_grid_workspace_bytes(rows_c, n_in)), dtype=torch.uint8, device=dev)
+        gram = torch.empty(n_in, 2, 8, 8, dtype=torch.float64, device=dev)
+        for lo in range(0, rows, rows_c):
+            hi = min(rows, lo + rows_c)
+            check(lib.siren_kan_grid_gram(ptr(xs[lo:hi]), hi - lo, n_in, ptr(self.grid), ptr(grid_new), int(lo > 0),
+                                          ptr(gram), ptr(ws), s), "siren_kan_grid_gram")
+        sw = self.spline_weight.detach()
+        sw_new = torch.empty_like(sw)
+        status = torch.empty(2, dtype=torch.int32, device=dev)
+        check(lib.siren_kan_grid_refit(ptr(gram), n_in, n_out, ptr(sw), ptr(self.spline_scaler.detach()),
+                                       ptr(sw_new), ptr(status), ptr(ws), s), "siren_kan_grid_refit")
+        bad, first = status.tolist()  # the one host synchronisation: this is not a per-step call
+        if bad:
+            raise _lib.SirenError(
+                f"update_grid: the refit of input {first} is rank deficient ({bad} input(s) in all: a constant "
+                "input, or fewer than 8 distinct useful samples); the layer is unchanged")
+        self.grid.copy_(grid_new)
+        self.spline_weight.data.copy_(sw_new)
+
+    def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0):
+        """kan.py:217-237: the L1 / entropy surrogate on the spline weights (differentiable torch ops)."""
+        mean_abs = self.spline_weight.abs().mean(-1)
+        activation = mean_abs.sum()
+        p = mean_abs / activation
+        entropy = -torch.sum(p * p.log())
+        return regularize_activation * activation + regularize_entropy * entropy
 
 
 def _hip_check_layer(lay: "KANLinear"):
@@ -225,11 +279,20 @@ class KAN(torch.nn.Module):
     def forward(self, x: torch.Tensor, update_grid=False):
         """kan.py:268-273: (..., in) CUDA coords -> (..., out).  Differentiable when autograd needs
         it (siren_kan_forward + siren_kan_backward); chunked HIP inference otherwise."""
-        if update_grid:
-            raise NotImplementedError("update_grid is not on the HIP path (run.py never uses it)")
         if not x.is_cuda:
             raise RuntimeError("KAN.forward runs on the HIP path only (CUDA tensors)")
         self.hip_check()
+        if update_grid:
+            # kan.py:274-279: per layer, update_grid(x) then x = layer(x); the layer forwards run the
+            # lone-layer route in row chunks, so the output is the updated model's (not differentiable:
+            # the reference's update_grid is @torch.no_grad too, and the refit moves the parameters)
+            lead = x.shape[:-1]
+            with torch.no_grad():
+                h = x.detach().reshape(-1, self.widths[0]).float().contiguous()
+                for lay in self.layers:
+                    lay.update_grid(h)
+                    h = layer_forward(lay, h)
+            return h.reshape(*lead, self.widths[-1])
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             params = [t for lay in self.layers for t in (lay.base_weight, lay.spline_weight, lay.spline_scaler)]
             return _kan_apply(self.widths, self.layers, x, params)
@@ -237,6 +300,10 @@ class KAN(torch.nn.Module):
         with torch.no_grad():
             out = kan_forward(self, x.reshape(-1, self.widths[0]), x.device)
         return out.reshape(*lead, 1)
+
+    def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0):
+        """kan.py:281-285: the layers' regularisation losses summed."""
+        return sum(lay.regularization_loss(regularize_activation, regularize_entropy) for lay in self.layers)
 
 
 def kan_forward(model: KAN, coords: torch.Tensor, device, chunk: int = 1 << 20, net=None) -> torch.Tensor:
@@ -257,6 +324,27 @@ def kan_forward(model: KAN, coords: torch.Tensor, device, chunk: int = 1 << 20, 
         b.coords, b.target, b.out, b.g, b.ws = ptr(c), 0, ptr(o), ptr(g), ptr(ws)
         check(lib.siren_kan_forward(ctypes.byref(net), ctypes.byref(b), s), "siren_kan_forward")
         out[lo:hi] = o[:hi - lo]
+    return out
+
+
+def layer_forward(lay: KANLinear, x: torch.Tensor, chunk: int = 1 << 18) -> torch.Tensor:
+    """(rows, in) -> (rows, out) of one layer by siren_kan_forward on a one-layer net, in row chunks
+    (inference; the same kernels, row by row the same bits, as the layer inside a stack)."""
+    lib, dev = _lib.load(), x.device
+    widths = [lay.in_features, lay.out_features]
+    net = _net(widths, [lay], [lay.base_weight.detach(), lay.spline_weight.detach(), lay.spline_scaler.detach()])
+    n = x.shape[0]
+    rows = max(1, min(chunk, n))
+    ws = torch.empty(int(lib.siren_kan_workspace_floats(ctypes.byref(net), rows, 1)), device=dev)
+    out = torch.empty(n, widths[1], dtype=torch.float32, device=dev)
+    g = torch.empty(rows, widths[1], dtype=torch.float32, device=dev)
+    s = torch.cuda.current_stream(dev).cuda_stream
+    for lo in range(0, n, rows):
+        hi = min(n, lo + rows)
+        b = SirenKanBatch()
+        b.rows, b.n_valid, b.n_total, b.splits, b.zero_grads = hi - lo, 0, 1.0, 1, 0
+        b.coords, b.target, b.out, b.g, b.ws = ptr(x[lo:hi]), 0, ptr(out[lo:hi]), ptr(g), ptr(ws)
+        check(lib.siren_kan_forward(ctypes.byref(net), ctypes.byref(b), s), "siren_kan_forward")
     return out
 
 
