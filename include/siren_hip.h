@@ -618,6 +618,21 @@ int siren_kan_train_step(const siren_kan_net* net, const siren_kan_grads* grads,
  * grad_coords != NULL also receives dLoss/dcoords [rows][width[0]] (grads->sse is not used). */
 int siren_kan_backward(const siren_kan_net* net, const siren_kan_grads* grads, siren_kan_batch* batch,
                        float* grad_coords, void* stream);
+/* run.py:124-125, :158-185 for arch='kan' under a point loss: loss_mode 0 is nn.MSELoss
+ * (siren_kan_train_step, bit for bit), 1 is nn.L1Loss (loss_mode='mae', run.py:161-163): g =
+ * sign(out - y) / n_total with torch's sign (0 at out == y) and grads->sse[0] accumulates the sum of
+ * |out - y| over the valid rows.  Any other loss_mode: SIREN_ERR_CONFIG, nothing launched. */
+int siren_kan_train_step_loss(const siren_kan_net* net, const siren_kan_grads* grads, siren_kan_batch* batch,
+                              int32_t loss_mode, void* stream);
+/* loss.backward() of run.py:185 for arch='kan' when the loss was computed outside the step (the
+ * STFT / SNR losses of run.py:126-128, :160-169 on the whole signal): batch->g holds dLoss/dout
+ * [rows] (zero past n_valid) and batch->ws the workspace of a siren_kan_forward of the same coords,
+ * rows and splits; last width 1.  A last layer of width <= 64 after a hidden layer runs its rank-1
+ * backward in siren_kan_train_step's block partition and summation order (fed that step's g, the
+ * gradients are that step's bit for bit); any other shape is siren_kan_backward(grad_coords = NULL).
+ * Gradients ACCUMULATE (zero_grads + flat: memset first); grads->sse is not used. */
+int siren_kan_step_backward(const siren_kan_net* net, const siren_kan_grads* grads, siren_kan_batch* batch,
+                            void* stream);
 
 /* ---- KAN grid update: KANLinear.update_grid of kan.py:168-215 for one layer ----------------
  * The reference refits the layer's curves on new knots by a least-squares fit over the batch.  Per

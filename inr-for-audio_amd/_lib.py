@@ -228,6 +228,11 @@ _SIGS = {
                                             ctypes.POINTER(SirenKanBatch), _p]),
     "siren_kan_backward": (ctypes.c_int, [ctypes.POINTER(SirenKanNet), ctypes.POINTER(SirenKanGrads),
                                           ctypes.POINTER(SirenKanBatch), _p, _p]),
+    # the KAN fit under the other losses: the L1 step, and the backward half of a phased spectral step
+    "siren_kan_train_step_loss": (ctypes.c_int, [ctypes.POINTER(SirenKanNet), ctypes.POINTER(SirenKanGrads),
+                                                 ctypes.POINTER(SirenKanBatch), _i32, _p]),
+    "siren_kan_step_backward": (ctypes.c_int, [ctypes.POINTER(SirenKanNet), ctypes.POINTER(SirenKanGrads),
+                                               ctypes.POINTER(SirenKanBatch), _p]),
     # KANLinear.update_grid (kan.py:168-215): knots, Gram sums, refit
     "siren_kan_grid_pass_rows": (_i64, [_i32]),
     "siren_kan_grid_workspace_bytes": (_i64, [_i64, _i32]),

@@ -1426,26 +1426,28 @@ int siren_kan_forward(const siren_kan_net* net, siren_kan_batch* b, void* stream
   return SIREN_OK;
 }
 
-int siren_kan_train_step(const siren_kan_net* net, const siren_kan_grads* gr, siren_kan_batch* b, void* stream) {
+int siren_kan_train_step_loss(const siren_kan_net* net, const siren_kan_grads* gr, siren_kan_batch* b,
+                              int32_t loss_mode, void* stream) {
   int st = check_kan(net);
   if (st) return st;
   if (!b || !gr || !gr->sse) return SIREN_ERR_NULL;
   if (!b->coords || !b->target || !b->out || !b->g || !b->ws) return SIREN_ERR_NULL;
+  if (loss_mode != 0 && loss_mode != 1) return SIREN_ERR_CONFIG;  // nn.MSELoss / nn.L1Loss (run.py:124-125)
   if (b->rows < 1 || b->splits < 1 || b->n_valid < 0 || b->n_valid > b->rows || b->n_total <= 0)
     return SIREN_ERR_SHAPE;
   for (int l = 0; l < net->n_layers; ++l)
     if (!gr->base_w[l] || !gr->spline_w[l] || !gr->scaler[l]) return SIREN_ERR_NULL;
-  if (net->width[net->n_layers] != 1) return SIREN_ERR_SHAPE;  // MSELoss on a scalar output
+  if (net->width[net->n_layers] != 1) return SIREN_ERR_SHAPE;  // a point loss on a scalar output
   hipStream_t s = S(stream);
   const int64_t R = b->rows;
   const KanWs w = kan_layout(net, R, b->splits, b->ws);
   SIREN_TRY(zero_grads(gr, b, s));
   SIREN_TRY(hipMemsetAsync(w.zero, 0, sizeof(float), s));
   const int L = net->n_layers;
-  // a last layer of width in <= 64 after a hidden layer runs its forward, the MSE gradient and its
+  // a last layer of width in <= 64 after a hidden layer runs its forward, the loss gradient and its
   // backward in one pass (kan_head_train); otherwise forward, head_loss, backward
   const bool head_train = L > 1 && net->width[L - 1] <= 64;
-  const float gfac = loss_gfac(0, b->n_total);
+  const float gfac = loss_gfac(loss_mode, b->n_total);
   const float* G = b->g;
   int cur = 0, l_top = L - 1;
   if (head_train) {
@@ -1456,7 +1458,8 @@ int siren_kan_train_step(const siren_kan_net* net, const siren_kan_grads* gr, si
     int nparts = 0;
     SIREN_PROF(SIREN_PROF_KAN_DW, s, kan_head_train(w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->target, R, in,
                                                     b->n_valid, gfac, w.slab_floats / (KAN_K1 * in), (R + 255) / 256,
-                                                    b->out, b->g, w.sse_part, w.slab, w.dW, w.G[cur], &nparts, s));
+                                                    b->out, b->g, w.sse_part, w.slab, w.dW, w.G[cur], &nparts, s,
+                                                    loss_mode));
     SIREN_PROF(SIREN_PROF_KAN_MISC, s, sum_to(w.sse_part, nparts, gr->sse, 1, s));
     SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_param_grads(w.dW, net->spline_w[L - 1], net->scaler[L - 1], 1, in, 1,
                                                        gr->base_w[L - 1], gr->spline_w[L - 1], gr->scaler[L - 1], s));
@@ -1465,13 +1468,45 @@ int siren_kan_train_step(const siren_kan_net* net, const siren_kan_grads* gr, si
     l_top = L - 2;
   } else {
     SIREN_TRY(kan_run_forward(net, b, w, s, L));
-    // MSELoss (run.py:168): out, g = 2(out - y)/N_total, squared-error partials
+    // MSELoss (run.py:168): out, g = 2(out - y)/N_total, squared-error partials; L1Loss
+    // (run.py:161-163): g = sign(out - y)/N_total, absolute-error partials
     SIREN_PROF(SIREN_PROF_KAN_MISC, s, head_loss(w.X[L], 1, b->rows, w.zero, b->target, b->n_valid, gfac, b->out, b->g,
-                                                 w.sse_part, w.gsum_part, w.gmax_part, s));
+                                                 w.sse_part, w.gsum_part, w.gmax_part, s, 0.f, loss_mode));
     SIREN_PROF(SIREN_PROF_KAN_MISC, s, sum_to(w.sse_part, (int)((R + 255) / 256), gr->sse, 1, s));
   }
   // backward (autograd of run.py:185): G = dLoss/dX[l+1], [R][out]
   SIREN_TRY(kan_run_backward(net, gr, b, w, s, G, l_top, cur, nullptr));
+  return SIREN_OK;
+}
+
+int siren_kan_train_step(const siren_kan_net* net, const siren_kan_grads* gr, siren_kan_batch* b, void* stream) {
+  return siren_kan_train_step_loss(net, gr, b, 0, stream);
+}
+
+int siren_kan_step_backward(const siren_kan_net* net, const siren_kan_grads* gr, siren_kan_batch* b, void* stream) {
+  int st = check_kan(net);
+  if (st) return st;
+  if (!b || !gr) return SIREN_ERR_NULL;
+  if (!b->coords || !b->g || !b->ws) return SIREN_ERR_NULL;
+  if (b->rows < 1 || b->splits < 1) return SIREN_ERR_SHAPE;
+  for (int l = 0; l < net->n_layers; ++l)
+    if (!gr->base_w[l] || !gr->spline_w[l] || !gr->scaler[l]) return SIREN_ERR_NULL;
+  const int L = net->n_layers;
+  if (net->width[L] != 1) return SIREN_ERR_SHAPE;  // the fit's scalar output
+  if (!(L > 1 && net->width[L - 1] <= 64)) return siren_kan_backward(net, gr, b, nullptr, stream);
+  hipStream_t s = S(stream);
+  const int64_t R = b->rows;
+  const int in = net->width[L - 1];
+  const KanWs w = kan_layout(net, R, b->splits, b->ws);
+  SIREN_TRY(zero_grads(gr, b, s));
+  // the last layer's rank-1 backward on the VALU (kan_head_bwd) in siren_kan_train_step's block
+  // partition, then the hidden layers as in that step
+  SIREN_PROF(SIREN_PROF_KAN_DW, s, kan_head_bwd(w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->g, R, in,
+                                                w.slab_floats / (KAN_K1 * in), (R + 255) / 256, w.slab, w.dW, w.G[0],
+                                                s));
+  SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_param_grads(w.dW, net->spline_w[L - 1], net->scaler[L - 1], 1, in, 1,
+                                                     gr->base_w[L - 1], gr->spline_w[L - 1], gr->scaler[L - 1], s));
+  SIREN_TRY(kan_run_backward(net, gr, b, w, s, w.G[0], L - 2, 1, nullptr));
   return SIREN_OK;
 }
 

@@ -10,8 +10,9 @@
 //   kan_dw_fused   dW chunk [out][144] += G[rows]^T A_chunk[rows]   (split-K over rows, slabs)
 //   kan_dx_fused   dA_chunk = G W_chunk (in LDS), contracted at once with the bases' derivatives
 //   kan_bwd_fused  both backward products of a chunk in one pass (out <= 64)
-//   kan_head_fwd / kan_head_train  the last layer (out = 1): inference; forward, MSE gradient and
-//                  backward in one pass (one row evaluation for both: kan_head_row)
+//   kan_head_fwd / kan_head_train / kan_head_bwd  the last layer (out = 1): inference; forward,
+//                  MSE or L1 gradient and backward in one pass; the backward alone for a given
+//                  g (one row evaluation for all: kan_head_row)
 //   kan_grid_knots / kan_grid_gram / kan_grid_refit  update_grid (kan.py:168-215), at the end of the file
 // The three backward kernels are put together from one set of tile helpers: kf_fill_a (A tile;
 // kan_bwd_fused keeps its own, with the derivatives in registers),
@@ -662,20 +663,31 @@ __global__ __launch_bounds__(256) void kan_head_fwd_kernel(const float* __restri
   }
 }
 
-// Training step of the last layer (out = 1, in <= 64) in one pass over its rows.  Per row: the
+// Training pass of the last layer (out = 1, in <= 64) over its rows.  Per row: the
 // forward out = SiLU(x) W[i] + sum_c B_c(x) W[in + 8 i + c] through kan_head_row like
-// kan_head_fwd (so out is bit-identical to inference), the MSE gradient g = 2 (out - y) / N and the
-// squared error (run.py:160-168; rows >= n_valid contribute nothing), then the backward: Gin[n][i]
+// kan_head_fwd (so out is bit-identical to inference), the loss gradient g and the loss partial
+// (rows >= n_valid contribute nothing), then the backward: Gin[n][i]
 // = g_n (SiLU'(x) W[i] + sum_c B'_c(x) W[in + 8 i + c]) (dA = g W is a rank-1 product, never
 // formed) and the weight-gradient partials -- one basis evaluation per (row, input) for the
 // forward and the backward, and no pass over X or out between them.  Blocks take >= 256 contiguous rows (one
-// slab row and one squared-error partial each); their 4 waves take every 4th row.
+// slab row and one loss partial each); their 4 waves take every 4th row.
+// SRC says where g comes from:
+//   KAN_HEAD_MSE    g = 2 (out - y) / N, partial err^2              (run.py:160, :168 nn.MSELoss)
+//   KAN_HEAD_L1     g = sign(out - y) / N, partial |err| (torch's sign: 0 at err == 0), as
+//                   head_loss_kernel's loss_mode 1                  (run.py:124, :161-163 nn.L1Loss)
+//   KAN_HEAD_GIVEN  g is read from yg (dLoss/dout of a loss computed elsewhere, zero on pad rows):
+//                   the backward half alone -- no out, g or loss partial is written.  Same block
+//                   partition and accumulation order, so fed an MSE pass's g it reproduces that
+//                   pass's Gin and slab bit for bit.
+enum { KAN_HEAD_MSE = 0, KAN_HEAD_L1 = 1, KAN_HEAD_GIVEN = 2 };
+template <int SRC>
 __global__ __launch_bounds__(256) void kan_head_train_kernel(const float* __restrict__ X, const float* __restrict__ grid,
-                                                             const float* __restrict__ W, const float* __restrict__ y,
+                                                             const float* __restrict__ W, const float* __restrict__ yg,
                                                              int64_t N, int in, int64_t n_valid, float gfac,
                                                              int64_t rows_per_block, float* __restrict__ out,
                                                              float* __restrict__ g, float* __restrict__ sse_part,
                                                              float* __restrict__ slab, float* __restrict__ Gin) {
+  constexpr bool GIVEN = SRC == KAN_HEAD_GIVEN;
   __shared__ float gk[64][KF_GST];
   __shared__ float inv[64][KF_VST];
   __shared__ float part[4][KAN_K1][64];
@@ -684,34 +696,44 @@ __global__ __launch_bounds__(256) void kan_head_train_kernel(const float* __rest
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t nb = (int64_t)blockIdx.x * rows_per_block;
   const int64_t ne = nb + rows_per_block < N ? nb + rows_per_block : N;
+  const int64_t nyg = GIVEN ? ne : n_valid;  // rows whose yg is read: a given g covers the pad rows
   const bool on = lane < in;
   float ab = 0.f, as[KAN_NB] = {}, sse = 0.f;
-  // the next row's x and y are loaded before this row's stores: vmcnt retires loads and stores in
-  // issue order, so a load issued after the stores would wait for them too
+  // the next row's x and y (or g) are loaded before this row's stores: vmcnt retires loads and
+  // stores in issue order, so a load issued after the stores would wait for them too
   int64_t n = nb + wv;
   float xn = 0.f, yn = 0.f;
   if (n < ne) {
     if (on) xn = X[n * in + lane];
-    if (n < n_valid) yn = y[n];
+    if (n < nyg) yn = yg[n];
   }
   for (; n < ne; n += 4) {
     const float xc = xn, yc = yn;
     if (n + 4 < ne) {
       if (on) xn = X[(n + 4) * in + lane];
-      if (n + 4 < n_valid) yn = y[n + 4];
+      if (n + 4 < nyg) yn = yg[n + 4];
     }
     float sl, dsl, b[KAN_NB], db[KAN_NB];
     const float v = kan_head_row<true>(on, xc, gk[lane], inv[lane], w, sl, dsl, b, db);
-    const float o = (0.f + v) + 0.f;  // head_loss's accumulation of the one partial and the zero bias
     float gn = 0.f;
-    if (n < n_valid) {
-      const float err = o - yc;
-      sse += err * err;
-      gn = err * gfac;
-    }
-    if (lane == 0) {
-      out[n] = o;
-      g[n] = gn;
+    if constexpr (GIVEN) {
+      gn = yc;
+    } else {
+      const float o = (0.f + v) + 0.f;  // head_loss's accumulation of the one partial and the zero bias
+      if (n < n_valid) {
+        const float err = o - yc;
+        if constexpr (SRC == KAN_HEAD_L1) {
+          sse += fabsf(err);
+          gn = (err > 0.f ? 1.0f : (err < 0.f ? -1.0f : 0.f)) * gfac;
+        } else {
+          sse += err * err;
+          gn = err * gfac;
+        }
+      }
+      if (lane == 0) {
+        out[n] = o;
+        g[n] = gn;
+      }
     }
     if (on) {
       ab += gn * sl;
@@ -727,7 +749,7 @@ __global__ __launch_bounds__(256) void kan_head_train_kernel(const float* __rest
   part[wv][0][lane] = ab;
 #pragma unroll
   for (int c = 0; c < KAN_NB; ++c) part[wv][1 + c][lane] = as[c];
-  if (lane == 0) sse_w[wv] = sse;
+  if (!GIVEN && lane == 0) sse_w[wv] = sse;
   __syncthreads();
   if (wv == 0) {
     if (on) {
@@ -738,7 +760,7 @@ __global__ __launch_bounds__(256) void kan_head_train_kernel(const float* __rest
         row[t == 0 ? lane : in + KAN_NB * lane + (t - 1)] = v;
       }
     }
-    if (lane == 0) sse_part[blockIdx.x] = ((sse_w[0] + sse_w[1]) + sse_w[2]) + sse_w[3];
+    if (!GIVEN && lane == 0) sse_part[blockIdx.x] = ((sse_w[0] + sse_w[1]) + sse_w[2]) + sse_w[3];
   }
 }
 
@@ -1120,21 +1142,44 @@ hipError_t kan_head_fwd(const float* X, const float* grid, const float* W, int64
   return hipGetLastError();
 }
 
-// the last layer's training pass (out = 1, in <= 64): returns the number of squared-error
-// partials written (<= max_parts, one per block) in *nparts
-hipError_t kan_head_train(const float* X, const float* grid, const float* W, const float* y, int64_t N, int in,
-                          int64_t n_valid, float gfac, int64_t slots, int64_t max_parts, float* out, float* g,
-                          float* sse_part, float* slab, float* dW, float* Gin, int* nparts, hipStream_t s) {
-  if (N <= 0 || in <= 0 || in > 64 || slots < 1 || max_parts < 1 || !nparts) return hipErrorInvalidValue;
+// The head pass's launch: blocks of >= 256 contiguous rows, at most `slots` (slab rows) and
+// max_parts (loss partials) of them, then the fixed-order slab sum into dW.  One partition for the
+// three sources of g, so a given g reproduces the pass that wrote it.
+template <int SRC>
+static hipError_t kan_head_pass(const float* X, const float* grid, const float* W, const float* yg, int64_t N, int in,
+                                int64_t n_valid, float gfac, int64_t slots, int64_t max_parts, float* out, float* g,
+                                float* sse_part, float* slab, float* dW, float* Gin, int* nparts, hipStream_t s) {
+  if (N <= 0 || in <= 0 || in > 64 || slots < 1 || max_parts < 1) return hipErrorInvalidValue;
   int64_t blocks = (N + 255) / 256;
   if (blocks > slots) blocks = slots;
   if (blocks > max_parts) blocks = max_parts;
   const int64_t rpb = (N + blocks - 1) / blocks;
   blocks = (N + rpb - 1) / rpb;
-  hipLaunchKernelGGL(kan_head_train_kernel, dim3((unsigned)blocks), dim3(256), 0, s, X, grid, W, y, N, in, n_valid, gfac,
-                     rpb, out, g, sse_part, slab, Gin);
-  *nparts = (int)blocks;
+  hipLaunchKernelGGL(kan_head_train_kernel<SRC>, dim3((unsigned)blocks), dim3(256), 0, s, X, grid, W, yg, N, in, n_valid,
+                     gfac, rpb, out, g, sse_part, slab, Gin);
+  if (nparts) *nparts = (int)blocks;
   return slab_reduce(slab, (int)blocks, (int64_t)KAN_K1 * in, dW, s);
+}
+
+// the last layer's training pass (out = 1, in <= 64), loss_mode 0 MSE / 1 L1: returns the number
+// of loss partials written (<= max_parts, one per block) in *nparts
+hipError_t kan_head_train(const float* X, const float* grid, const float* W, const float* y, int64_t N, int in,
+                          int64_t n_valid, float gfac, int64_t slots, int64_t max_parts, float* out, float* g,
+                          float* sse_part, float* slab, float* dW, float* Gin, int* nparts, hipStream_t s,
+                          int loss_mode) {
+  if (!nparts || (loss_mode != 0 && loss_mode != 1)) return hipErrorInvalidValue;
+  return loss_mode == 1 ? kan_head_pass<KAN_HEAD_L1>(X, grid, W, y, N, in, n_valid, gfac, slots, max_parts, out, g,
+                                                     sse_part, slab, dW, Gin, nparts, s)
+                        : kan_head_pass<KAN_HEAD_MSE>(X, grid, W, y, N, in, n_valid, gfac, slots, max_parts, out, g,
+                                                      sse_part, slab, dW, Gin, nparts, s);
+}
+
+// the backward half of that pass for a given g [N] (zero on pad rows): Gin and dW, with
+// kan_head_train's block partition for the same slots and max_parts
+hipError_t kan_head_bwd(const float* X, const float* grid, const float* W, const float* g, int64_t N, int in,
+                        int64_t slots, int64_t max_parts, float* slab, float* dW, float* Gin, hipStream_t s) {
+  return kan_head_pass<KAN_HEAD_GIVEN>(X, grid, W, g, N, in, N, 0.f, slots, max_parts, nullptr, nullptr, nullptr, slab,
+                                       dW, Gin, nullptr, s);
 }
 
 // Row splits of a split-K backward kernel with `per` chunk tiles: one round of `resident` blocks

@@ -298,11 +298,16 @@ hipError_t kan_bwd_fused(const float* X, const float* grid, const float* G, cons
                          int64_t max_splits, float* slab, float* dW, float* Gin, hipStream_t s);
 // the last layer (out = 1, in <= 64): wave-per-row forward (inference)
 hipError_t kan_head_fwd(const float* X, const float* grid, const float* W, int64_t N, int in, float* Y, hipStream_t s);
-// the last layer's forward + MSE gradient + backward in one pass (out = 1, in <= 64); *nparts
-// squared-error partials
+// the last layer's forward + loss gradient + backward in one pass (out = 1, in <= 64); *nparts
+// loss partials (loss_mode 0: MSE, squared errors; 1: L1, absolute errors)
 hipError_t kan_head_train(const float* X, const float* grid, const float* W, const float* y, int64_t N, int in,
                           int64_t n_valid, float gfac, int64_t slots, int64_t max_parts, float* out, float* g,
-                          float* sse_part, float* slab, float* dW, float* Gin, int* nparts, hipStream_t s);
+                          float* sse_part, float* slab, float* dW, float* Gin, int* nparts, hipStream_t s,
+                          int loss_mode = 0);
+// its backward half for a given g [N] (zero on pad rows): Gin and dW in kan_head_train's block
+// partition and accumulation order for the same slots and max_parts
+hipError_t kan_head_bwd(const float* X, const float* grid, const float* W, const float* g, int64_t N, int in,
+                        int64_t slots, int64_t max_parts, float* slab, float* dW, float* Gin, hipStream_t s);
 // W = [base_w | spline_w * scaler] as [out][9 in], and (WT != null) its transpose [9 in][out]
 hipError_t kan_combine(const float* base_w, const float* spline_w, const float* scaler, int out, int in, float* W,
                        float* WT, hipStream_t s);

@@ -371,6 +371,132 @@ class FitEngine:
     def _check_capture(self):
         """capture_graph's hook for a launch configuration that the first step changes."""
 
+    def _spectral_args(self, target, n_total, micro_batch, micro_rows, loss_mode, alpha, stft_loss, split_spectral):
+        """The loss arguments of run.py:124-128, :160-169, checked before anything is built: loss_mode,
+        stft_loss, alpha in [0, 1], and for a spectral loss (alpha != 0 or 'snr') the whole signal in one
+        micro-batch of `micro_rows` rows on one rank unless split_spectral, and enough samples for the
+        reflect padding."""
+        if loss_mode not in LOSS_MODES:
+            raise NotImplementedError(f"loss_mode={loss_mode!r}: the HIP path has {sorted(LOSS_MODES)}")
+        if stft_loss not in STFT_LOSSES:
+            raise ValueError(f"stft_loss={stft_loss!r}: one of {STFT_LOSSES} (run.py:127-128)")
+        self.loss_mode_id = LOSS_MODES[loss_mode]
+        self.stft_loss = stft_loss
+        self.alpha = float(alpha)
+        if not 0.0 <= self.alpha <= 1.0:
+            raise ValueError(f"alpha={alpha!r} must be in [0, 1] (run.py:161-169 mixes (1 - alpha) and alpha)")
+        self.spectral = self.alpha != 0.0 or loss_mode == "snr"
+        self.split_spectral = split = self.spectral and bool(split_spectral)
+        if self.spectral:
+            n_sig = int(target.numel())
+            if _dist() is not None and not split:
+                raise NotImplementedError("the STFT / SNR losses need the whole signal on one rank (frames and the "
+                                          "sums cross shard boundaries): no process group of more than one rank "
+                                          "(split_spectral=True gathers the signal)")
+            if n_total is not None and (int(n_total) != n_sig or _dist() is not None):
+                raise NotImplementedError("the STFT / SNR losses need the whole signal (n_total == len(target))")
+            if n_sig > micro_rows and not split:
+                raise NotImplementedError(f"the STFT / SNR losses need the whole signal in one micro-batch: "
+                                          f"{n_sig} samples > micro_batch={micro_batch} (split_spectral=True "
+                                          f"runs the loss between the micro-batches' forwards and backwards)")
+            if self.alpha != 0.0 and n_sig <= 512:
+                raise ValueError(f"the STFT loss needs more than 512 samples (reflect padding of a 1024-point "
+                                 f"frame is undefined for {n_sig}; torch.stft refuses it too)")
+            if self.alpha != 0.0 and stft_loss == "mrstft" and n_sig <= 1024:
+                raise ValueError(f"the multi-resolution STFT loss needs more than 1024 samples (reflect padding of "
+                                 f"its 2048-point frame is undefined for {n_sig}; torch.stft refuses it too)")
+
+    def _setup_signal(self, target):
+        """The split step's target: the whole signal on every rank; [_sig_lo, _sig_hi) are this rank's samples."""
+        self.target_sig = target.reshape(-1).to(self.device, torch.float32).contiguous()
+        n_sig = self.target_sig.numel()
+        self._sig_lo, self._sig_hi = 0, n_sig
+        d = _dist()
+        if d is not None:
+            self._sig_lo, self._sig_hi = shard_range(n_sig, d.get_rank(), d.get_world_size())
+
+    def _setup_split(self, prefix):
+        """The split step's buffers (DESIGN 6d): out_sig / g_sig [N], the whole-signal loss workspace with
+        the target's side set once, this rank's windows of frame blocks and, in a process group, where
+        the transforms' partials live and which of them this rank owns."""
+        lib, dev, N, d = self.lib, self.device, self.n_total, _dist()
+        lo, hi = self._sig_lo, self._sig_hi
+        fn = lambda name: getattr(lib, f"{prefix}_{name}")  # noqa: E731
+        mr = self.stft_loss == "mrstft"
+        rr = lambda r: (r,) if mr else ()   # mrstft's calls name the resolution  # noqa: E731
+        self.out_sig = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.g_sig = torch.zeros(N, dtype=torch.float32, device=dev)
+        self.stft_ws = torch.zeros(int(fn("workspace_floats")(N, N)), dtype=torch.float32, device=dev)
+        self._sig_win = (ctypes.c_int32 * 6)()
+        self._parts = []   # per transform (ws offset, npart, frame blocks, grid.y, owned lo, owned hi, pack offset)
+        # the finished loss: the gradients' tail slot on rank 0 alone, so that the SUM all-reduce leaves it once
+        self._loss_scratch = torch.zeros(4, dtype=torch.float32, device=dev)
+        own = d is None or d.get_rank() == 0
+        self._loss_ptr = self.grads.data_ptr() + 4 * self.layout.sse_offset if own else ptr(self._loss_scratch)
+        if self.alpha == 0.0:
+            return
+        self.stft_basis = _basis(self.stft_loss, dev)
+        check(fn("forward")(ptr(self.target_sig), N, N, ptr(self.stft_basis), ptr(self.stft_ws), 1, self._stream()),
+              prefix + "_forward")
+        pack = 0
+        for r in range(3 if mr else 1):
+            blocks = (ctypes.c_int32 * 4)()
+            check(fn("window")(N, *rr(r), lo, hi, blocks), prefix + "_window")
+            self._sig_win[2 * r], self._sig_win[2 * r + 1] = blocks[0], blocks[1]
+            off, npart, nblk, gy = (int(fn("signal_parts")(N, N, *rr(r), k)) for k in range(4))
+            self._parts.append((off, npart, nblk, gy, blocks[2], blocks[3], pack))
+            pack += 2 * npart
+        self._part_pack = torch.zeros(pack, dtype=torch.float32, device=dev) if d is not None else None
+
+    def _reduce_partials(self, d):
+        """Every rank's complete partial arrays: the ones of the blocks this rank owns, zeros elsewhere,
+        summed over the ranks (x + 0 = x: the arrays are the one-rank launch's, bit for bit)."""
+        pk, ws = self._part_pack, self.stft_ws
+        pk.zero_()
+        for off, npart, nblk, gy, olo, ohi, po in self._parts:
+            for row in range(2):
+                for y in range(gy):
+                    a = row * npart + y * nblk
+                    pk[po + a + olo:po + a + ohi] = ws[off + a + olo:off + a + ohi]
+        d.all_reduce(pk)
+        for off, npart, _, _, _, _, po in self._parts:
+            ws[off:off + 2 * npart] = pk[po:po + 2 * npart]
+
+    def _launch_grads_split(self):
+        """run.py:160-169 across micro-batches and ranks (DESIGN 6d): forwards into out_sig, the loss on the
+        gathered signal, backwards from the slices of g_sig.  No host synchronisation on one rank.  The
+        engine's two hooks: _split_forward(batch, stream) runs a micro-batch's forward and returns its
+        output rows; _split_backward(batch, g, stream) accumulates its gradients from g = dLoss/dout of
+        its valid rows."""
+        lib, s, N, mb = self.lib, self._stream(), self.n_total, self.rows
+        prefix = _SPECTRAL[self.stft_loss][2]
+        mode, alpha = self.loss_mode_id, self.alpha
+        d = _dist()
+        x, y, basis, ws = ptr(self.out_sig), ptr(self.target_sig), ptr(self.stft_basis), ptr(self.stft_ws)
+        self.grads.zero_()
+        if d is not None:
+            self.out_sig.zero_()   # zero outside the own shard: the SUM all-reduce is the gather
+        for k, b in enumerate(self.batches):
+            out = self._split_forward(b, s)
+            lo = self._sig_lo + k * mb
+            self.out_sig[lo:lo + b.n_valid] = out[:b.n_valid]
+        if d is not None:
+            d.all_reduce(self.out_sig)
+        check(getattr(lib, prefix + "_signal_forward")(x, y, N, N, mode, alpha, basis, ws, self._sig_win, s),
+              prefix + "_signal_forward")
+        if d is not None and alpha != 0.0:
+            self._reduce_partials(d)
+        check(getattr(lib, prefix + "_signal_finish")(N, N, mode, alpha, ws, self._loss_ptr, s),
+              prefix + "_signal_finish")
+        check(getattr(lib, prefix + "_signal_backward")(x, y, N, N, mode, alpha, basis, ws, self._sig_win,
+                                                        self._sig_lo, self._sig_hi, ptr(self.g_sig), s),
+              prefix + "_signal_backward")
+        for k, b in enumerate(self.batches):
+            if self.n_micro > 1:   # the workspace holds the last micro-batch's activations
+                self._split_forward(b, s)
+            lo = self._sig_lo + k * mb
+            self._split_backward(b, self.g_sig[lo:lo + b.n_valid], s)
+
     # ------------------------------------------------------------------ public API
     def step(self):
         """One optimizer step over the full batch (all micro-batches, all ranks)."""
@@ -531,34 +657,9 @@ class SirenEngine(FitEngine):
         g = dLoss/dout.  Only then does such an engine take more than one micro-batch or rank; each rank
         holds the whole target and a whole-signal loss workspace, so the caller passes the whole signal
         (no n_total)."""
-        if loss_mode not in LOSS_MODES:
-            raise NotImplementedError(f"loss_mode={loss_mode!r}: the HIP path has {sorted(LOSS_MODES)}")
-        if stft_loss not in STFT_LOSSES:
-            raise ValueError(f"stft_loss={stft_loss!r}: one of {STFT_LOSSES} (run.py:127-128)")
-        self.stft_loss = stft_loss
-        self.alpha = float(alpha)
-        if not 0.0 <= self.alpha <= 1.0:
-            raise ValueError(f"alpha={alpha!r} must be in [0, 1] (run.py:161-169 mixes (1 - alpha) and alpha)")
-        self.spectral = self.alpha != 0.0 or loss_mode == "snr"
-        self.split_spectral = split = self.spectral and bool(split_spectral)
-        if self.spectral:
-            n_sig = int(target.numel())
-            if _dist() is not None and not split:
-                raise NotImplementedError("the STFT / SNR losses need the whole signal on one rank (frames and the "
-                                          "sums cross shard boundaries): no process group of more than one rank "
-                                          "(split_spectral=True gathers the signal)")
-            if n_total is not None and (int(n_total) != n_sig or _dist() is not None):
-                raise NotImplementedError("the STFT / SNR losses need the whole signal (n_total == len(target))")
-            if n_sig > round_up(int(micro_batch), 2 * ROW_TILE) and not split:
-                raise NotImplementedError(f"the STFT / SNR losses need the whole signal in one micro-batch: "
-                                          f"{n_sig} samples > micro_batch={micro_batch} (split_spectral=True "
-                                          f"runs the loss between the micro-batches' forwards and backwards)")
-            if self.alpha != 0.0 and n_sig <= 512:
-                raise ValueError(f"the STFT loss needs more than 512 samples (reflect padding of a 1024-point "
-                                 f"frame is undefined for {n_sig}; torch.stft refuses it too)")
-            if self.alpha != 0.0 and stft_loss == "mrstft" and n_sig <= 1024:
-                raise ValueError(f"the multi-resolution STFT loss needs more than 1024 samples (reflect padding of "
-                                 f"its 2048-point frame is undefined for {n_sig}; torch.stft refuses it too)")
+        self._spectral_args(target, n_total, micro_batch, round_up(int(micro_batch), 2 * ROW_TILE), loss_mode, alpha,
+                            stft_loss, split_spectral)
+        split = self.split_spectral
         super().__init__(device)
         self.model = model
         self.encoding = encoding
@@ -592,12 +693,8 @@ class SirenEngine(FitEngine):
         self._setup_opt(lr, min_lr, factor, patience, hist_cap)
 
         # data: this rank's contiguous shard, padded per micro-batch
-        if split:   # the loss sees the whole target on every rank; [_sig_lo, _sig_hi) are this rank's samples
-            self.target_sig = target.reshape(-1).to(dev, torch.float32).contiguous()
-            n_sig = self.target_sig.numel()
-            self._sig_lo, self._sig_hi = 0, n_sig
-            if d is not None:
-                self._sig_lo, self._sig_hi = shard_range(n_sig, d.get_rank(), d.get_world_size())
+        if split:
+            self._setup_signal(target)
         coords, target = self._shard(coords, target, spec.in_dim, n_total)
         n, n_global = self.n_local, self.n_total
         # rows padded to 256 (pad rows carry g = 0): the 256x256 GEMM tiles need M % 256 == 0,
@@ -654,87 +751,15 @@ class SirenEngine(FitEngine):
             check(getattr(lib, prefix + "_forward")(ptr(self.target), n, self.rows, ptr(self.stft_basis),
                                                     ptr(self.stft_ws), 1, self._stream()), prefix + "_forward")
 
-    def _setup_split(self, prefix):
-        """The split step's buffers (DESIGN 6d): out_sig / g_sig [N], the whole-signal loss workspace with
-        the target's side set once, this rank's windows of frame blocks and, in a process group, where
-        the transforms' partials live and which of them this rank owns."""
-        lib, dev, N, d = self.lib, self.device, self.n_total, _dist()
-        lo, hi = self._sig_lo, self._sig_hi
-        fn = lambda name: getattr(lib, f"{prefix}_{name}")  # noqa: E731
-        mr = self.stft_loss == "mrstft"
-        rr = lambda r: (r,) if mr else ()   # mrstft's calls name the resolution  # noqa: E731
-        self.out_sig = torch.zeros(N, dtype=torch.float32, device=dev)
-        self.g_sig = torch.zeros(N, dtype=torch.float32, device=dev)
-        self.stft_ws = torch.zeros(int(fn("workspace_floats")(N, N)), dtype=torch.float32, device=dev)
-        self._sig_win = (ctypes.c_int32 * 6)()
-        self._parts = []   # per transform (ws offset, npart, frame blocks, grid.y, owned lo, owned hi, pack offset)
-        # the finished loss: the gradients' tail slot on rank 0 alone, so that the SUM all-reduce leaves it once
-        self._loss_scratch = torch.zeros(4, dtype=torch.float32, device=dev)
-        own = d is None or d.get_rank() == 0
-        self._loss_ptr = self.grads.data_ptr() + 4 * self.layout.sse_offset if own else ptr(self._loss_scratch)
-        if self.alpha == 0.0:
-            return
-        self.stft_basis = _basis(self.stft_loss, dev)
-        check(fn("forward")(ptr(self.target_sig), N, N, ptr(self.stft_basis), ptr(self.stft_ws), 1, self._stream()),
-              prefix + "_forward")
-        pack = 0
-        for r in range(3 if mr else 1):
-            blocks = (ctypes.c_int32 * 4)()
-            check(fn("window")(N, *rr(r), lo, hi, blocks), prefix + "_window")
-            self._sig_win[2 * r], self._sig_win[2 * r + 1] = blocks[0], blocks[1]
-            off, npart, nblk, gy = (int(fn("signal_parts")(N, N, *rr(r), k)) for k in range(4))
-            self._parts.append((off, npart, nblk, gy, blocks[2], blocks[3], pack))
-            pack += 2 * npart
-        self._part_pack = torch.zeros(pack, dtype=torch.float32, device=dev) if d is not None else None
+    def _split_forward(self, b, s):
+        check(self.lib.siren_forward(ctypes.byref(self.net), ctypes.byref(b), s), "siren_forward")
+        return self.ws.out
 
-    def _reduce_partials(self, d):
-        """Every rank's complete partial arrays: the ones of the blocks this rank owns, zeros elsewhere,
-        summed over the ranks (x + 0 = x: the arrays are the one-rank launch's, bit for bit)."""
-        pk, ws = self._part_pack, self.stft_ws
-        pk.zero_()
-        for off, npart, nblk, gy, olo, ohi, po in self._parts:
-            for row in range(2):
-                for y in range(gy):
-                    a = row * npart + y * nblk
-                    pk[po + a + olo:po + a + ohi] = ws[off + a + olo:off + a + ohi]
-        d.all_reduce(pk)
-        for off, npart, _, _, _, _, po in self._parts:
-            ws[off:off + 2 * npart] = pk[po:po + 2 * npart]
-
-    def _launch_grads_split(self):
-        """run.py:160-169 across micro-batches and ranks (DESIGN 6d): forwards into out_sig, the loss on the
-        gathered signal, backwards from the slices of g_sig.  No host synchronisation on one rank."""
-        lib, s, N, mb = self.lib, self._stream(), self.n_total, self.rows
-        net, gr = ctypes.byref(self.net), ctypes.byref(self.grad_struct)
-        prefix = _SPECTRAL[self.stft_loss][2]
-        mode, alpha = self.batches[0].loss_mode, self.alpha
-        d = _dist()
-        x, y, basis, ws = ptr(self.out_sig), ptr(self.target_sig), ptr(self.stft_basis), ptr(self.stft_ws)
-        self.grads.zero_()
-        if d is not None:
-            self.out_sig.zero_()   # zero outside the own shard: the SUM all-reduce is the gather
-        for k, b in enumerate(self.batches):
-            check(lib.siren_forward(net, ctypes.byref(b), s), "siren_forward")
-            lo = self._sig_lo + k * mb
-            self.out_sig[lo:lo + b.n_valid] = self.ws.out[:b.n_valid]
-        if d is not None:
-            d.all_reduce(self.out_sig)
-        check(getattr(lib, prefix + "_signal_forward")(x, y, N, N, mode, alpha, basis, ws, self._sig_win, s),
-              prefix + "_signal_forward")
-        if d is not None and alpha != 0.0:
-            self._reduce_partials(d)
-        check(getattr(lib, prefix + "_signal_finish")(N, N, mode, alpha, ws, self._loss_ptr, s),
-              prefix + "_signal_finish")
-        check(getattr(lib, prefix + "_signal_backward")(x, y, N, N, mode, alpha, basis, ws, self._sig_win,
-                                                        self._sig_lo, self._sig_hi, ptr(self.g_sig), s),
-              prefix + "_signal_backward")
-        for k, b in enumerate(self.batches):
-            if self.n_micro > 1:   # the workspace holds the last micro-batch's activations
-                check(lib.siren_forward(net, ctypes.byref(b), s), "siren_forward")
-            lo = self._sig_lo + k * mb
-            self.ws.g[:b.n_valid] = self.g_sig[lo:lo + b.n_valid]
-            self.ws.g[b.n_valid:].zero_()
-            check(lib.siren_backward(net, gr, ctypes.byref(b), s), "siren_backward")
+    def _split_backward(self, b, g, s):
+        self.ws.g[:b.n_valid] = g
+        self.ws.g[b.n_valid:].zero_()
+        check(self.lib.siren_backward(ctypes.byref(self.net), ctypes.byref(self.grad_struct), ctypes.byref(b), s),
+              "siren_backward")
 
     def _setup_buckets(self):
         """One bucket per layer (contiguous in the flat layout): the head (+ the SSE tail slot),
@@ -935,18 +960,29 @@ def forward_net(spec: NetSpec, net: SirenNet, coords: torch.Tensor, device, chun
 
 class KanEngine(FitEngine):
     """Full-batch fit of the KAN variant (run.py:92-93 arch='kan') on the HIP
-    path: siren_kan_train_step per micro-batch, gradient all-reduce across DP ranks, then the
-    same flat Adam + ReduceLROnPlateau kernels as the SIREN path.  The optimizer, history,
-    checkpoint and graph-capture methods are FitEngine's; fp32 throughout, so no range guard."""
+    path: siren_kan_train_step_loss per micro-batch (nn.MSELoss or nn.L1Loss), gradient all-reduce
+    across DP ranks, then the same flat Adam + ReduceLROnPlateau kernels as the SIREN path.  The
+    optimizer, history, checkpoint and graph-capture methods are FitEngine's; fp32 throughout, so no
+    range guard.
+
+    loss_mode='snr' and alpha != 0 (run.py:126-128, :160-169) run as FitEngine's phased step alone
+    (`split_spectral=True`, the keyword of SirenEngine): siren_kan_forward per micro-batch
+    into the signal-length out_sig, the loss once on the whole signal, siren_kan_step_backward from
+    each slice of g_sig."""
 
     def __init__(self, model, coords: torch.Tensor, target: torch.Tensor, *, lr: float = 1e-3,
                  min_lr: float = 1e-6, factor: float = 0.8, patience: int = 200,
                  n_total: int | None = None, micro_batch: int = 1 << 20, hist_cap: int = 20000,
-                 splits: int | None = None, device=None, loss_mode: str = "mse", alpha: float = 0.0):
+                 splits: int | None = None, device=None, loss_mode: str = "mse", alpha: float = 0.0,
+                 stft_loss: str = "stft", split_spectral: bool = False):
         from .kan import make_kan_grads
-        if loss_mode != "mse" or alpha != 0.0:
-            raise NotImplementedError("KanEngine is fitted with MSELoss only (no loss_mode 'mae' / 'snr', no STFT "
-                                      "term: alpha must be 0)")
+        if (loss_mode == "snr" or alpha != 0.0) and not split_spectral:
+            raise NotImplementedError("KanEngine's one-pass step is fitted with a point loss (MSELoss only, or L1Loss "
+                                      "for loss_mode='mae'); loss_mode='snr' and the STFT term (alpha != 0) run as the "
+                                      "phased step: pass split_spectral=True")
+        self._spectral_args(target, n_total, micro_batch, int(micro_batch), loss_mode, alpha, stft_loss,
+                            split_spectral)
+        split = self.split_spectral
         super().__init__(device)
         lib, dev = self.lib, self.device
         model.hip_check()
@@ -960,6 +996,8 @@ class KanEngine(FitEngine):
                                           self.grads, lay.flat_len)
         self._setup_opt(lr, min_lr, factor, patience, hist_cap)
 
+        if split:
+            self._setup_signal(target)
         coords, target = self._shard(coords, target, model.widths[0], n_total)
         n, n_global = self.n_local, self.n_total
         self.rows = mb = max(1, min(int(micro_batch), n))
@@ -979,23 +1017,41 @@ class KanEngine(FitEngine):
             hi = min(n, lo + mb)
             b = SirenKanBatch()
             b.rows, b.n_valid, b.n_total = hi - lo, hi - lo, float(n_global)
-            b.splits, b.zero_grads = self.splits, int(k == 0)
+            # the split step clears the gradients itself, before the loss lands in their tail slot
+            b.splits, b.zero_grads = self.splits, int(k == 0 and not split)
             b.coords, b.target = self.coords[lo:hi].data_ptr(), self.target[lo:hi].data_ptr()
             b.out, b.g, b.ws = ptr(self.out), ptr(self.g), ptr(self.ws)
             self.batches.append(b)
+        self.stft_basis = self.stft_ws = None
+        if split:
+            self._setup_split(_SPECTRAL[self.stft_loss][2])
+
+    def _split_forward(self, b, s):
+        check(self.lib.siren_kan_forward(ctypes.byref(self.net), ctypes.byref(b), s), "siren_kan_forward")
+        return self.out
+
+    def _split_backward(self, b, g, s):
+        self.g[:b.n_valid] = g   # rows == n_valid: a KAN micro-batch carries no pad rows
+        check(self.lib.siren_kan_step_backward(ctypes.byref(self.net), ctypes.byref(self.grad_struct),
+                                               ctypes.byref(b), s), "siren_kan_step_backward")
 
     def _launch_grads(self):
+        if self.split_spectral:
+            return self._launch_grads_split()
         s = self._stream()
-        for b in self.batches:
-            check(self.lib.siren_kan_train_step(ctypes.byref(self.net), ctypes.byref(self.grad_struct),
-                                                ctypes.byref(b), s), "siren_kan_train_step")
+        for b in self.batches:   # run.py:124-125: nn.MSELoss / nn.L1Loss, the sum of the valid rows in the sse slot
+            check(self.lib.siren_kan_train_step_loss(ctypes.byref(self.net), ctypes.byref(self.grad_struct),
+                                                     ctypes.byref(b), self.loss_mode_id, s),
+                  "siren_kan_train_step_loss")
 
     def _launch_update(self):
         s = self._stream()
         check(self.lib.siren_adam_step(ptr(self.params), ptr(self.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq),
                                        self.layout.n_params, ptr(self.state), s), "siren_adam_step")
         check(self.lib.siren_plateau_step(ptr(self.state), self.grads.data_ptr() + 4 * self.layout.sse_offset,
-                                          float(self.n_total), ptr(self.loss_hist), ptr(self.lr_hist),
+                                          # a phased step leaves the finished mixed loss in the sse slot, not a sum over N
+                                          1.0 if self.spectral else float(self.n_total),
+                                          ptr(self.loss_hist), ptr(self.lr_hist),
                                           self.hist_cap, s), "siren_plateau_step")
 
     @torch.no_grad()

@@ -96,13 +96,15 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     ``restated_losses`` (opt-in: fit with ``alpha > 0`` and / or ``loss_mode='snr'`` using this
     project's restatement of auraloss's STFTLoss / SNRLoss defaults -- run.py:126-128, :160-169 --
     instead of raising; parity is to the published formula, not to an installed auraloss.  For
-    method 'wave' and 'mdct' of the MLP, the whole signal in one micro-batch on one GPU; with 'snr'
+    method 'wave' and 'mdct' of the MLP, the whole signal in one micro-batch on one GPU, and for
+    arch='kan' together with ``split_spectral``; with 'snr'
     the loss is negative, so the dB history is NaN as in the reference, run.py:180),
     ``stft_loss`` (with ``restated_losses``: 'stft', the single STFTLoss() of run.py:128, or 'mrstft',
     the MultiResolutionSTFTLoss() of run.py:127 -- more than 1024 samples; recorded in parameters.json
-    only when it is not 'stft'), ``split_spectral`` (with ``restated_losses``: SirenEngine's split step,
+    only when it is not 'stft'), ``split_spectral`` (with ``restated_losses``: the engines' split step,
     which fits with these losses across micro-batches and data-parallel ranks -- a clip longer than
-    ``micro_batch``, or more than one GPU; recorded in parameters.json only when true)."""
+    ``micro_batch``, or more than one GPU, and the only way arch='kan' fits with them; recorded in
+    parameters.json only when true)."""
     if method not in ("wave", "mdct"):
         raise ValueError("specify the correct fitting method as wave or mdct (run.py:77-78)")
     if method == "mdct" and bwe:
@@ -117,10 +119,11 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
                                   "restated_losses=True fits 'snr' and alpha > 0 with the restated auraloss terms")
     if stft_loss not in ("stft", "mrstft"):
         raise ValueError(f"stft_loss={stft_loss!r}: 'stft' (run.py:128) or 'mrstft' (run.py:127)")
-    if spectral and (multichannel or arch != "mlp"):
-        raise NotImplementedError("restated_losses fits the waveform / MDCT MLP (no multichannel, no arch='kan')")
-    if arch == "kan" and loss_mode != "mse":
-        raise NotImplementedError("arch='kan' is fitted with loss_mode='mse'")
+    if spectral and multichannel:
+        raise NotImplementedError("restated_losses fits the waveform / MDCT MLP and the KAN (no multichannel)")
+    if spectral and arch == "kan" and not split_spectral:
+        raise NotImplementedError("arch='kan' is fitted with 'snr' and alpha > 0 by the phased step alone: add "
+                                  "split_spectral=True to restated_losses=True")
     if multichannel and (method != "wave" or arch != "mlp" or bwe):
         raise NotImplementedError("multichannel fits the waveform MLP (run.py:59-63) without bwe")
     if num_freq is not None and (method != "wave" or arch != "mlp" or multichannel):
@@ -188,14 +191,14 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
 
     dev = torch.device(device or "cuda")
     Engine = KanEngine if arch == "kan" else SirenEngine
-    kw = {} if arch == "kan" else {"loss_mode": loss_mode, "encoding": encoding, "alpha": alpha}
+    kw = {"loss_mode": loss_mode, "alpha": alpha}
+    if arch != "kan":
+        kw["encoding"] = encoding
     if stft_loss != "stft":
-        if arch == "kan":
-            raise NotImplementedError("stft_loss='mrstft' fits the MLP (arch='kan' is fitted with MSELoss only)")
         kw["stft_loss"] = stft_loss
     if split_spectral:
-        if not restated_losses or arch == "kan":
-            raise NotImplementedError("split_spectral is the MLP's restated_losses step across micro-batches and ranks")
+        if not restated_losses:
+            raise NotImplementedError("split_spectral is the restated_losses step across micro-batches and ranks")
         kw["split_spectral"] = True
     engine = Engine(model, model_input, ground_truth, lr=learning_rate, min_lr=min_learning_rate,
                     patience=patience, micro_batch=micro_batch, hist_cap=total_steps, device=dev, **kw)
