@@ -571,19 +571,25 @@ int siren_fp32_linear_bwd(const float* x, int64_t rows, int32_t in, int32_t out,
 
 /* ---- KAN variant: run.py:92-93 KAN([in, H, H, 1]) of kan.py:169-285 ----------
  * Layer l maps width[l] -> width[l+1] as efficient-KAN's KANLinear (kan.py:6-166) with
- * grid_size 5, spline_order 3, SiLU base: out = SiLU(x) base_w^T + B(x) (spline_w*scaler)^T,
- * B = the 8 order-3 B-spline bases on the layer's `grid` buffer [in][12].  fp32 throughout.
+ * spline_order 3, SiLU base: out = SiLU(x) base_w^T + B(x) (spline_w*scaler)^T,
+ * B = the G + 3 order-3 B-spline bases on the layer's `grid` buffer [in][G + 7], for one grid size
+ * G = siren_kan_net.grid_size of 1 .. SIREN_KAN_MAX_GRID in every layer (0 means the default 5, so a
+ * zero-initialised struct is a grid-5 net: 8 bases on 12 knots).  A value outside 0 .. 64 is
+ * SIREN_ERR_CONFIG before any launch.  Grid 5 runs kernels with its sizes fixed at compile time,
+ * every other size the any-grid-size set (kan.hip); the siren_kan_grid_* refit below is grid 5 only.
+ * fp32 throughout.
  * siren_kan_forward / _backward take any last width (out is then [rows][last width]); the fused
  * fit step (siren_kan_train_step) needs last width 1.  Workspace: one caller-owned fp32 buffer of
  * siren_kan_workspace_floats(net, rows, splits) floats (activations, combined weights,
  * gradients of the layer outputs, split-K slabs -- the expansions are never stored). */
 #define SIREN_KAN_MAX_LAYERS 8
+#define SIREN_KAN_MAX_GRID 64
 typedef struct siren_kan_net {
-  int32_t n_layers, pad0;
+  int32_t n_layers, grid_size;                  /* grid_size: 0 (= 5) or 1 .. SIREN_KAN_MAX_GRID      */
   int32_t width[SIREN_KAN_MAX_LAYERS + 1];
-  const float* grid[SIREN_KAN_MAX_LAYERS];      /* [in][12]     buffer layers.l.grid        */
+  const float* grid[SIREN_KAN_MAX_LAYERS];      /* [in][G+7]    buffer layers.l.grid        */
   const float* base_w[SIREN_KAN_MAX_LAYERS];    /* [out][in]    layers.l.base_weight        */
-  const float* spline_w[SIREN_KAN_MAX_LAYERS];  /* [out][in][8] layers.l.spline_weight      */
+  const float* spline_w[SIREN_KAN_MAX_LAYERS];  /* [out][in][G+3] layers.l.spline_weight    */
   const float* scaler[SIREN_KAN_MAX_LAYERS];    /* [out][in]    layers.l.spline_scaler      */
 } siren_kan_net;
 typedef struct siren_kan_grads {
@@ -713,11 +719,14 @@ enum siren_prof_kind {
  * SIREN_OPT_HEAD_FUSE = 1 (default): siren_train_step runs a sine last layer on 256x256
  * ping-pong tiles as one launch with the head, the loss gradient and the head backward
  * (dZ_L is written instead of Y_L / C_L; the backward scale S then comes from a bound of
- * max|g| known before the forward); 0: separate forward, head_loss and head_bwd launches. */
+ * max|g| known before the forward); 0: separate forward, head_loss and head_bwd launches.
+ * SIREN_OPT_KAN_GENERAL = 0 (default): a KAN of grid_size 5 runs its own kernels; 1: it runs the
+ * any-grid-size kernels that every other grid size runs (tests and measurement: the two sets
+ * side by side on one net). */
 enum siren_option {
   SIREN_OPT_NT_TILE = 0, SIREN_OPT_TN_TILE = 1, SIREN_OPT_NT_PIPE = 2, SIREN_OPT_TN_PIPE = 3,
   SIREN_OPT_NT_GRID = 4, SIREN_OPT_NT_DIAG = 6, SIREN_OPT_NT_QUEUE = 8, SIREN_OPT_HEAD_FUSE = 9,
-  SIREN_OPT_HB_FAULT = 10
+  SIREN_OPT_HB_FAULT = 10, SIREN_OPT_KAN_GENERAL = 11
 };
 int siren_set_option(int32_t option, int32_t value);
 int siren_profile_enable(int32_t max_records);

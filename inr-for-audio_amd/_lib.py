@@ -99,11 +99,12 @@ class SirenSpectralMR(ctypes.Structure):
 
 
 KAN_MAX_LAYERS = 8
+KAN_MAX_GRID = 64  # SIREN_KAN_MAX_GRID: grid_size 1 .. 64 at spline_order 3
 
 
 class SirenKanNet(ctypes.Structure):
     _fields_ = [
-        ("n_layers", _i32), ("pad0", _i32), ("width", _i32 * (KAN_MAX_LAYERS + 1)),
+        ("n_layers", _i32), ("grid_size", _i32), ("width", _i32 * (KAN_MAX_LAYERS + 1)),
         ("grid", _p * KAN_MAX_LAYERS), ("base_w", _p * KAN_MAX_LAYERS),
         ("spline_w", _p * KAN_MAX_LAYERS), ("scaler", _p * KAN_MAX_LAYERS),
     ]
@@ -336,11 +337,12 @@ class Opt(enum.IntEnum):
     NT_QUEUE = 8
     HEAD_FUSE = 9
     HB_FAULT = 10
+    KAN_GENERAL = 11
 
 
 # what a freshly loaded library holds (capi.hip's option table)
 OPT_DEFAULTS = {Opt.NT_TILE: 0, Opt.TN_TILE: 0, Opt.NT_PIPE: -1, Opt.TN_PIPE: -1, Opt.NT_GRID: 0,
-                Opt.NT_DIAG: 0, Opt.NT_QUEUE: 1, Opt.HEAD_FUSE: 1, Opt.HB_FAULT: 0}
+                Opt.NT_DIAG: 0, Opt.NT_QUEUE: 1, Opt.HEAD_FUSE: 1, Opt.HB_FAULT: 0, Opt.KAN_GENERAL: 0}
 
 
 def _opt_shadow(lib) -> dict:

@@ -1209,6 +1209,7 @@ const OptionRow kOptions[] = {
     {SIREN_OPT_NT_QUEUE, &Tuning::nt_queue, 1, [](int v) { return v >= 0 && v <= 2; }, false},
     {SIREN_OPT_HEAD_FUSE, &Tuning::head_fuse, 1, [](int v) { return v == 0 || v == 1; }, false},
     {SIREN_OPT_HB_FAULT, &Tuning::hb_fault, 0, not_negative, true},
+    {SIREN_OPT_KAN_GENERAL, &Tuning::kan_general, 0, [](int v) { return v == 0 || v == 1; }, false},
 };
 
 Tuning default_tuning() {
@@ -1285,9 +1286,34 @@ int siren_profile_read(int32_t kind, double* total_ms, int64_t* count) {
 // ---- KAN variant (kan.py, run.py:92-93) -----------------------------------
 namespace {
 
+static_assert(SIREN_KAN_MAX_GRID == KG_MAX_GRID, "the header's grid-size limit is the kernels'");
+
+// The net's grid size (0 = the default 5) and which kernel set runs it: grid_size 5 keeps its own
+// kernels (KAN_NB = 8 at compile time) unless SIREN_OPT_KAN_GENERAL sends it through the
+// any-grid-size set, which runs every other size.
+struct KanSel {
+  int G, k1;
+  bool general;
+};
+KanSel kan_sel(const siren_kan_net* n) {
+  const int G = n->grid_size == 0 ? 5 : n->grid_size;
+  return KanSel{G, G + 4, G != 5 || tuning().kan_general != 0};
+}
+hipError_t sel_combine(const KanSel& k, const float* base_w, const float* spline_w, const float* scaler, int out, int in,
+                       float* W, float* WT, hipStream_t s) {
+  return k.general ? kang_combine(base_w, spline_w, scaler, out, in, k.G, W, WT, s)
+                   : kan_combine(base_w, spline_w, scaler, out, in, W, WT, s);
+}
+hipError_t sel_param_grads(const KanSel& k, const float* dW, const float* spline_w, const float* scaler, int out, int in,
+                           float* g_base, float* g_spline, float* g_scaler, hipStream_t s) {
+  return k.general ? kang_param_grads(dW, spline_w, scaler, out, in, k.G, 1, g_base, g_spline, g_scaler, s)
+                   : kan_param_grads(dW, spline_w, scaler, out, in, 1, g_base, g_spline, g_scaler, s);
+}
+
 int check_kan(const siren_kan_net* n) {
   if (!n) return SIREN_ERR_NULL;
   if (n->n_layers < 1 || n->n_layers > SIREN_KAN_MAX_LAYERS) return SIREN_ERR_CONFIG;
+  if (n->grid_size < 0 || n->grid_size > SIREN_KAN_MAX_GRID) return SIREN_ERR_CONFIG;
   for (int l = 0; l <= n->n_layers; ++l)
     if (n->width[l] < 1 || n->width[l] > 4096) return SIREN_ERR_SHAPE;
   for (int l = 0; l < n->n_layers; ++l)
@@ -1296,9 +1322,9 @@ int check_kan(const siren_kan_net* n) {
 }
 
 // Workspace carve-up (floats, each piece 64-float aligned):
-//   X[l] rows x w[l] for l = 1..L (X[L] = the output row vector);  W[l] w[l+1] x 9 w[l] and its
-//   transpose WT[l];
-//   dW w_max_out x 9 w_max_in;  slab splits x that;  G[2] rows x w_max;
+//   X[l] rows x w[l] for l = 1..L (X[L] = the output row vector);  W[l] w[l+1] x K1 w[l] and its
+//   transpose WT[l]  (K1 = grid_size + 4: 9 at the default grid);
+//   dW w_max_out x K1 w_max_in;  slab splits x that;  G[2] rows x w_max;
 //   sse/gsum/gmax partials 3 x ceil(rows/256);  one zero float.
 // (No expansion A or dA: the fused kernels recompute the bases -- kan.hip.)
 struct KanWs {
@@ -1313,6 +1339,7 @@ inline int64_t al64(int64_t x) { return (x + 63) / 64 * 64; }
 
 KanWs kan_layout(const siren_kan_net* n, int64_t rows, int splits, float* base) {
   KanWs w = {};
+  const int64_t K1 = kan_sel(n).k1;
   int64_t off = 0;
   auto take = [&](int64_t floats) {
     float* p = base ? base + off : nullptr;
@@ -1321,19 +1348,19 @@ KanWs kan_layout(const siren_kan_net* n, int64_t rows, int splits, float* base) 
   };
   int64_t wmax = 1, wk = 1;
   for (int l = 0; l < n->n_layers; ++l) {
-    w.W[l] = take((int64_t)n->width[l + 1] * KAN_K1 * n->width[l]);
-    w.WT[l] = take((int64_t)n->width[l + 1] * KAN_K1 * n->width[l]);
-    const int64_t kw = (int64_t)n->width[l + 1] * KAN_K1 * n->width[l];
+    w.W[l] = take((int64_t)n->width[l + 1] * K1 * n->width[l]);
+    w.WT[l] = take((int64_t)n->width[l + 1] * K1 * n->width[l]);
+    const int64_t kw = (int64_t)n->width[l + 1] * K1 * n->width[l];
     if (kw > wk) wk = kw;
     if (n->width[l] > wmax) wmax = n->width[l];
   }
   for (int l = 1; l <= n->n_layers; ++l) w.X[l] = take(rows * n->width[l]);
   w.dW = take(wk);
-  // split-K slabs: splits x (out x 9 in) for the fused weight gradient, 4 splits x 9 in for the
+  // split-K slabs: splits x (out x K1 in) for the fused weight gradient, 4 splits x K1 in for the
   // last layer's wave partials
   int64_t slab = wk * splits;
   for (int l = 0; l < n->n_layers; ++l)
-    if (n->width[l + 1] == 1 && 4LL * splits * KAN_K1 * n->width[l] > slab) slab = 4LL * splits * KAN_K1 * n->width[l];
+    if (n->width[l + 1] == 1 && 4LL * splits * K1 * n->width[l] > slab) slab = 4LL * splits * K1 * n->width[l];
   w.slab = take(slab);
   w.slab_floats = slab;
   w.G[0] = take(rows * wmax);
@@ -1351,14 +1378,17 @@ KanWs kan_layout(const siren_kan_net* n, int64_t rows, int splits, float* base) 
 hipError_t kan_run_forward(const siren_kan_net* n, const siren_kan_batch* b, const KanWs& w, hipStream_t s, int nl) {
   const int64_t R = b->rows;
   const float* x = b->coords;
+  const KanSel k = kan_sel(n);
   for (int l = 0; l < nl; ++l) {
     const int in = n->width[l], out = n->width[l + 1];
-    SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_combine(n->base_w[l], n->spline_w[l], n->scaler[l], out, in, w.W[l], w.WT[l], s));
+    SIREN_PROF(SIREN_PROF_KAN_MISC, s, sel_combine(k, n->base_w[l], n->spline_w[l], n->scaler[l], out, in, w.W[l], w.WT[l], s));
     // X[l+1][r][o] = sum_k A[r][k] W[o][k], A = [SiLU(x) | bases(x)] recomputed in LDS
     if (out == 1 && in <= 64)
-      SIREN_PROF(SIREN_PROF_KAN_FWD, s, kan_head_fwd(x, n->grid[l], w.W[l], R, in, w.X[l + 1], s));
+      SIREN_PROF(SIREN_PROF_KAN_FWD, s, k.general ? kang_head_fwd(x, n->grid[l], w.W[l], R, in, k.G, w.X[l + 1], s)
+                                                  : kan_head_fwd(x, n->grid[l], w.W[l], R, in, w.X[l + 1], s));
     else
-      SIREN_PROF(SIREN_PROF_KAN_FWD, s, kan_fwd_fused(x, n->grid[l], w.W[l], R, in, out, w.X[l + 1], s));
+      SIREN_PROF(SIREN_PROF_KAN_FWD, s, k.general ? kang_fwd_fused(x, n->grid[l], w.W[l], R, in, out, k.G, w.X[l + 1], s)
+                                                  : kan_fwd_fused(x, n->grid[l], w.W[l], R, in, out, w.X[l + 1], s));
     x = w.X[l + 1];
   }
   return hipSuccess;
@@ -1370,12 +1400,13 @@ hipError_t kan_run_forward(const siren_kan_net* n, const siren_kan_batch* b, con
 hipError_t kan_run_backward(const siren_kan_net* net, const siren_kan_grads* gr, const siren_kan_batch* b,
                             const KanWs& w, hipStream_t s, const float* G, int l_top, int cur, float* grad_coords) {
   const int64_t R = b->rows;
+  const KanSel k = kan_sel(net);
   for (int l = l_top; l >= 0; --l) {
     const int in = net->width[l], out = net->width[l + 1];
     const float* xl = l == 0 ? b->coords : w.X[l];
-    const int64_t max_splits = w.slab_floats / ((int64_t)out * KAN_K1 * in);
+    const int64_t max_splits = w.slab_floats / ((int64_t)out * k.k1 * in);
     float* gin = l > 0 ? w.G[cur] : grad_coords;
-    if (out <= 64 && gin) {
+    if (out <= 64 && gin && !k.general) {  // the any-grid-size set has no one-pass backward
       // dW and dX = SiLU' dA_base + sum_c B'_c dA_c in one pass (bases and G read once)
       SIREN_PROF(SIREN_PROF_KAN_DX, s, kan_bwd_fused(xl, net->grid[l], G, w.WT[l], R, in, out, max_splits, w.slab,
                                                      w.dW, gin, s));
@@ -1386,12 +1417,14 @@ hipError_t kan_run_backward(const siren_kan_net* net, const siren_kan_grads* gr,
       continue;
     }
     // dW[o][k] = sum_r G[r][o] A[r][k]  (split-K over the coordinates, bases recomputed)
-    SIREN_PROF(SIREN_PROF_KAN_DW, s, kan_dw_fused(xl, net->grid[l], G, R, in, out, max_splits, w.slab, w.dW, s));
-    SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_param_grads(w.dW, net->spline_w[l], net->scaler[l], out, in, 1,
+    SIREN_PROF(SIREN_PROF_KAN_DW, s, k.general ? kang_dw_fused(xl, net->grid[l], G, R, in, out, k.G, max_splits, w.slab, w.dW, s)
+                                               : kan_dw_fused(xl, net->grid[l], G, R, in, out, max_splits, w.slab, w.dW, s));
+    SIREN_PROF(SIREN_PROF_KAN_MISC, s, sel_param_grads(k, w.dW, net->spline_w[l], net->scaler[l], out, in,
                                                        gr->base_w[l], gr->spline_w[l], gr->scaler[l], s));
     if (!gin) break;  // layer 0 without a coordinate gradient
     // dX = SiLU' dA_base + sum_c B'_c dA_spline_c with dA = G W formed per chunk in LDS
-    SIREN_PROF(SIREN_PROF_KAN_DX, s, kan_dx_fused(xl, net->grid[l], G, w.WT[l], R, in, out, gin, s));
+    SIREN_PROF(SIREN_PROF_KAN_DX, s, k.general ? kang_dx_fused(xl, net->grid[l], G, w.WT[l], R, in, out, k.G, gin, s)
+                                               : kan_dx_fused(xl, net->grid[l], G, w.WT[l], R, in, out, gin, s));
     G = gin;
     cur ^= 1;
   }
@@ -1452,16 +1485,21 @@ int siren_kan_train_step_loss(const siren_kan_net* net, const siren_kan_grads* g
   int cur = 0, l_top = L - 1;
   if (head_train) {
     const int in = net->width[L - 1];
+    const KanSel k = kan_sel(net);
     SIREN_TRY(kan_run_forward(net, b, w, s, L - 1));
-    SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_combine(net->base_w[L - 1], net->spline_w[L - 1], net->scaler[L - 1], 1, in,
+    SIREN_PROF(SIREN_PROF_KAN_MISC, s, sel_combine(k, net->base_w[L - 1], net->spline_w[L - 1], net->scaler[L - 1], 1, in,
                                                    w.W[L - 1], w.WT[L - 1], s));
     int nparts = 0;
-    SIREN_PROF(SIREN_PROF_KAN_DW, s, kan_head_train(w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->target, R, in,
-                                                    b->n_valid, gfac, w.slab_floats / (KAN_K1 * in), (R + 255) / 256,
-                                                    b->out, b->g, w.sse_part, w.slab, w.dW, w.G[cur], &nparts, s,
-                                                    loss_mode));
+    const int64_t slots = w.slab_floats / (k.k1 * in), max_parts = (R + 255) / 256;
+    SIREN_PROF(SIREN_PROF_KAN_DW, s,
+               k.general ? kang_head_train(w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->target, R, in, k.G, b->n_valid,
+                                           gfac, slots, max_parts, b->out, b->g, w.sse_part, w.slab, w.dW, w.G[cur],
+                                           &nparts, s, loss_mode)
+                         : kan_head_train(w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->target, R, in, b->n_valid, gfac,
+                                          slots, max_parts, b->out, b->g, w.sse_part, w.slab, w.dW, w.G[cur], &nparts,
+                                          s, loss_mode));
     SIREN_PROF(SIREN_PROF_KAN_MISC, s, sum_to(w.sse_part, nparts, gr->sse, 1, s));
-    SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_param_grads(w.dW, net->spline_w[L - 1], net->scaler[L - 1], 1, in, 1,
+    SIREN_PROF(SIREN_PROF_KAN_MISC, s, sel_param_grads(k, w.dW, net->spline_w[L - 1], net->scaler[L - 1], 1, in,
                                                        gr->base_w[L - 1], gr->spline_w[L - 1], gr->scaler[L - 1], s));
     G = w.G[cur];
     cur ^= 1;
@@ -1501,10 +1539,13 @@ int siren_kan_step_backward(const siren_kan_net* net, const siren_kan_grads* gr,
   SIREN_TRY(zero_grads(gr, b, s));
   // the last layer's rank-1 backward on the VALU (kan_head_bwd) in siren_kan_train_step's block
   // partition, then the hidden layers as in that step
-  SIREN_PROF(SIREN_PROF_KAN_DW, s, kan_head_bwd(w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->g, R, in,
-                                                w.slab_floats / (KAN_K1 * in), (R + 255) / 256, w.slab, w.dW, w.G[0],
-                                                s));
-  SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_param_grads(w.dW, net->spline_w[L - 1], net->scaler[L - 1], 1, in, 1,
+  const KanSel k = kan_sel(net);
+  const int64_t slots = w.slab_floats / (k.k1 * in), max_parts = (R + 255) / 256;
+  SIREN_PROF(SIREN_PROF_KAN_DW, s, k.general ? kang_head_bwd(w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->g, R, in, k.G,
+                                                             slots, max_parts, w.slab, w.dW, w.G[0], s)
+                                             : kan_head_bwd(w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->g, R, in, slots,
+                                                            max_parts, w.slab, w.dW, w.G[0], s));
+  SIREN_PROF(SIREN_PROF_KAN_MISC, s, sel_param_grads(k, w.dW, net->spline_w[L - 1], net->scaler[L - 1], 1, in,
                                                      gr->base_w[L - 1], gr->spline_w[L - 1], gr->scaler[L - 1], s));
   SIREN_TRY(kan_run_backward(net, gr, b, w, s, w.G[0], L - 2, 1, nullptr));
   return SIREN_OK;

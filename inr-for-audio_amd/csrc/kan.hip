@@ -14,6 +14,8 @@
 //                  MSE or L1 gradient and backward in one pass; the backward alone for a given
 //                  g (one row evaluation for all: kan_head_row)
 //   kan_grid_knots / kan_grid_gram / kan_grid_refit  update_grid (kan.py:168-215), at the end of the file
+// These kernels are grid_size 5's (KAN_NB = 8 at compile time).  Every other grid size runs their twins in
+// kan_general.hip, which takes its tool kit from this file ("shared with kan_general.hip" below).
 // The three backward kernels are put together from one set of tile helpers: kf_fill_a (A tile;
 // kan_bwd_fused keeps its own, with the derivatives in registers),
 // kf_g_load / kf_g_store / kf_g_scalar (G tile), kf_load_wt (W^T chunk), kf_da_to_gin (dA -> Gin),
@@ -501,6 +503,80 @@ __device__ __forceinline__ void kf_mfma_groups_n(int nj, const float* ap, const 
   }
 }
 
+// ---- shared with kan_general.hip ----------------------------------------------------------
+// Everything above and down to KAN_TILES_ONLY is also the tool kit of the any-grid-size kernels, which
+// live in a translation unit of their own (kan_general.hip includes this file with KAN_TILES_ONLY
+// defined and so takes the helpers without the kernels below): with both sets in one unit the
+// compiler scheduled kan_dw_fused_kernel differently (152 instead of 156 VGPRs), and the grid-5
+// kernels are to stay instruction for instruction what they were.
+// where the head pass takes g from (kan_head_train_kernel)
+enum { KAN_HEAD_MSE = 0, KAN_HEAD_L1 = 1, KAN_HEAD_GIVEN = 2 };
+
+// out[e] = sum_z slab[z][e] in a fixed order: a block takes C columns; its 256 / C thread groups
+// sum every (256/C)-th slab row (4 loads in flight per thread), then the group partials add up
+// in group order.  C = 64 for wide slabs; C = 16 (64-byte row segments, 16 groups) when there are
+// few columns and many slab rows.
+template <int C>
+__global__ __launch_bounds__(256) void kan_slab_reduce_kernel(const float* __restrict__ slab, int splits, int64_t mn,
+                                                              float* __restrict__ out) {
+  constexpr int NG = 256 / C;
+  __shared__ float part[NG][C];
+  const int col = threadIdx.x % C, grp = threadIdx.x / C;
+  const int64_t e = (int64_t)blockIdx.x * C + col;
+  float acc = 0.f;
+  if (e < mn) {
+    int z = grp;
+    for (; z + 3 * NG < splits; z += 4 * NG) {
+      const float a0 = slab[(int64_t)z * mn + e], a1 = slab[(int64_t)(z + NG) * mn + e];
+      const float a2 = slab[(int64_t)(z + 2 * NG) * mn + e], a3 = slab[(int64_t)(z + 3 * NG) * mn + e];
+      acc = (((acc + a0) + a1) + a2) + a3;
+    }
+    for (; z < splits; z += NG) acc += slab[(int64_t)z * mn + e];
+  }
+  part[grp][col] = acc;
+  __syncthreads();
+  if (grp == 0 && e < mn) {
+    float v = part[0][col];
+#pragma unroll
+    for (int g = 1; g < NG; ++g) v += part[g][col];
+    out[e] = v;
+  }
+}
+
+static hipError_t slab_reduce(const float* slab, int splits, int64_t mn, float* out, hipStream_t s) {
+  if (mn < 64 * 256 && splits > 64)
+    hipLaunchKernelGGL(kan_slab_reduce_kernel<16>, dim3((unsigned)((mn + 15) / 16)), dim3(256), 0, s, slab, splits, mn, out);
+  else
+    hipLaunchKernelGGL(kan_slab_reduce_kernel<64>, dim3((unsigned)((mn + 63) / 64)), dim3(256), 0, s, slab, splits, mn, out);
+  return hipGetLastError();
+}
+
+static inline int ew_grid(int64_t n) {
+  int64_t g = (n + 255) / 256;
+  return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
+}
+
+// Row splits of a split-K backward kernel with `per` chunk tiles: one round of `resident` blocks
+// (every CU busy, no tail), at most max_splits, each a multiple of 64 rows; the grid pads the
+// splits to a multiple of 8 (kf_split_block).  blocks = 0: too many for a 1-D grid.
+struct KfSplitPlan {
+  int64_t rows_per_split;
+  int z;            // splits that hold rows = slabs written
+  unsigned blocks;
+};
+static KfSplitPlan kf_plan_splits(int64_t N, int64_t resident, int64_t per, int64_t max_splits) {
+  int64_t splits = resident / per;
+  if (splits < 1) splits = 1;
+  if (splits > max_splits) splits = max_splits;
+  int64_t rps = (N + splits - 1) / splits;
+  rps = (rps + KF_R - 1) / KF_R * KF_R;
+  const int z = (int)((N + rps - 1) / rps);
+  const int64_t blocks = per * ((z + 7) / 8 * 8);
+  return KfSplitPlan{rps, z, blocks > 0x7fffffff ? 0u : (unsigned)blocks};
+}
+
+#ifndef KAN_TILES_ONLY
+
 // As[r][ii] = SiLU(x), As[r][ic + 8 ii + c] = B_c(x) for the pair (r, ii) (zeros for rows past N)
 __device__ __forceinline__ void kf_put_pair(float (*As)[KF_AST], int r, int ii, int ic, float x, bool valid,
                                             const float (*gk)[KF_GST], const float (*inv)[KF_VST]) {
@@ -679,7 +755,6 @@ __global__ __launch_bounds__(256) void kan_head_fwd_kernel(const float* __restri
 //                   the backward half alone -- no out, g or loss partial is written.  Same block
 //                   partition and accumulation order, so fed an MSE pass's g it reproduces that
 //                   pass's Gin and slab bit for bit.
-enum { KAN_HEAD_MSE = 0, KAN_HEAD_L1 = 1, KAN_HEAD_GIVEN = 2 };
 template <int SRC>
 __global__ __launch_bounds__(256) void kan_head_train_kernel(const float* __restrict__ X, const float* __restrict__ grid,
                                                              const float* __restrict__ W, const float* __restrict__ yg,
@@ -1082,50 +1157,6 @@ __global__ __launch_bounds__(256) void kan_gemm_kernel(const float* __restrict__
     }
 }
 
-// out[e] = sum_z slab[z][e] in a fixed order: a block takes C columns; its 256 / C thread groups
-// sum every (256/C)-th slab row (4 loads in flight per thread), then the group partials add up
-// in group order.  C = 64 for wide slabs; C = 16 (64-byte row segments, 16 groups) when there are
-// few columns and many slab rows.
-template <int C>
-__global__ __launch_bounds__(256) void kan_slab_reduce_kernel(const float* __restrict__ slab, int splits, int64_t mn,
-                                                              float* __restrict__ out) {
-  constexpr int NG = 256 / C;
-  __shared__ float part[NG][C];
-  const int col = threadIdx.x % C, grp = threadIdx.x / C;
-  const int64_t e = (int64_t)blockIdx.x * C + col;
-  float acc = 0.f;
-  if (e < mn) {
-    int z = grp;
-    for (; z + 3 * NG < splits; z += 4 * NG) {
-      const float a0 = slab[(int64_t)z * mn + e], a1 = slab[(int64_t)(z + NG) * mn + e];
-      const float a2 = slab[(int64_t)(z + 2 * NG) * mn + e], a3 = slab[(int64_t)(z + 3 * NG) * mn + e];
-      acc = (((acc + a0) + a1) + a2) + a3;
-    }
-    for (; z < splits; z += NG) acc += slab[(int64_t)z * mn + e];
-  }
-  part[grp][col] = acc;
-  __syncthreads();
-  if (grp == 0 && e < mn) {
-    float v = part[0][col];
-#pragma unroll
-    for (int g = 1; g < NG; ++g) v += part[g][col];
-    out[e] = v;
-  }
-}
-
-static hipError_t slab_reduce(const float* slab, int splits, int64_t mn, float* out, hipStream_t s) {
-  if (mn < 64 * 256 && splits > 64)
-    hipLaunchKernelGGL(kan_slab_reduce_kernel<16>, dim3((unsigned)((mn + 15) / 16)), dim3(256), 0, s, slab, splits, mn, out);
-  else
-    hipLaunchKernelGGL(kan_slab_reduce_kernel<64>, dim3((unsigned)((mn + 63) / 64)), dim3(256), 0, s, slab, splits, mn, out);
-  return hipGetLastError();
-}
-
-static inline int ew_grid(int64_t n) {
-  int64_t g = (n + 255) / 256;
-  return (int)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
-}
-
 hipError_t kan_fwd_fused(const float* X, const float* grid, const float* W, int64_t N, int in, int out, float* Y,
                          hipStream_t s) {
   if (N <= 0 || in <= 0 || out <= 0) return hipErrorInvalidValue;
@@ -1180,25 +1211,6 @@ hipError_t kan_head_bwd(const float* X, const float* grid, const float* W, const
                         int64_t slots, int64_t max_parts, float* slab, float* dW, float* Gin, hipStream_t s) {
   return kan_head_pass<KAN_HEAD_GIVEN>(X, grid, W, g, N, in, N, 0.f, slots, max_parts, nullptr, nullptr, nullptr, slab,
                                        dW, Gin, nullptr, s);
-}
-
-// Row splits of a split-K backward kernel with `per` chunk tiles: one round of `resident` blocks
-// (every CU busy, no tail), at most max_splits, each a multiple of 64 rows; the grid pads the
-// splits to a multiple of 8 (kf_split_block).  blocks = 0: too many for a 1-D grid.
-struct KfSplitPlan {
-  int64_t rows_per_split;
-  int z;            // splits that hold rows = slabs written
-  unsigned blocks;
-};
-static KfSplitPlan kf_plan_splits(int64_t N, int64_t resident, int64_t per, int64_t max_splits) {
-  int64_t splits = resident / per;
-  if (splits < 1) splits = 1;
-  if (splits > max_splits) splits = max_splits;
-  int64_t rps = (N + splits - 1) / splits;
-  rps = (rps + KF_R - 1) / KF_R * KF_R;
-  const int z = (int)((N + rps - 1) / rps);
-  const int64_t blocks = per * ((z + 7) / 8 * 8);
-  return KfSplitPlan{rps, z, blocks > 0x7fffffff ? 0u : (unsigned)blocks};
 }
 
 // dW[o][k] = sum_n G[n][o] A[n][k]: `splits` row slices into slabs, then the fixed-order slab sum
@@ -1499,5 +1511,7 @@ hipError_t kan_grid_refit(const double* gram, int in, int out, const float* spli
                      out, in, spline_w_new);
   return hipGetLastError();
 }
+
+#endif  // KAN_TILES_ONLY
 
 }  // namespace siren

@@ -34,6 +34,7 @@ struct Tuning {
   int nt_queue;          // dynamic tile queue: 0 off, 1 forward modes, 2 every ping-pong mode
   int head_fuse;         // siren_train_step runs the last layer as NT_FWD_HB* when it can
   int hb_fault;          // hand-off fault hook (SIREN_DIAG builds)
+  int kan_general;       // grid_size 5 runs the any-grid-size KAN kernels (tests and measurement)
 };
 Tuning& tuning();
 
@@ -313,6 +314,28 @@ hipError_t kan_combine(const float* base_w, const float* spline_w, const float* 
                        float* WT, hipStream_t s);
 hipError_t kan_param_grads(const float* dW, const float* spline_w, const float* scaler, int out, int in,
                            int accumulate, float* g_base, float* g_spline, float* g_scaler, hipStream_t s);
+// The same launches for any grid size G = 1 .. KG_MAX_GRID (spline_order 3): NB = G + 3 bases,
+// NG = G + 7 knots, K1 = G + 4 A-columns per input as run-time values (kan.hip, "any grid size").
+// grid [in][G + 7], spline_w [out][in][G + 3], W [out][(G + 4) in]; slabs of out x (G + 4) in floats.
+constexpr int KG_MAX_GRID = 64;
+hipError_t kang_fwd_fused(const float* X, const float* grid, const float* W, int64_t N, int in, int out, int G, float* Y,
+                          hipStream_t s);
+hipError_t kang_dw_fused(const float* X, const float* grid, const float* Gr, int64_t N, int in, int out, int G,
+                         int64_t max_splits, float* slab, float* dW, hipStream_t s);
+hipError_t kang_dx_fused(const float* X, const float* grid, const float* Gout, const float* WT, int64_t N, int in,
+                         int out, int G, float* Gin, hipStream_t s);
+hipError_t kang_head_fwd(const float* X, const float* grid, const float* W, int64_t N, int in, int G, float* Y,
+                         hipStream_t s);
+hipError_t kang_head_train(const float* X, const float* grid, const float* W, const float* y, int64_t N, int in, int G,
+                           int64_t n_valid, float gfac, int64_t slots, int64_t max_parts, float* out, float* g,
+                           float* sse_part, float* slab, float* dW, float* Gin, int* nparts, hipStream_t s,
+                           int loss_mode = 0);
+hipError_t kang_head_bwd(const float* X, const float* grid, const float* W, const float* g, int64_t N, int in, int G,
+                         int64_t slots, int64_t max_parts, float* slab, float* dW, float* Gin, hipStream_t s);
+hipError_t kang_combine(const float* base_w, const float* spline_w, const float* scaler, int out, int in, int G,
+                        float* W, float* WT, hipStream_t s);
+hipError_t kang_param_grads(const float* dW, const float* spline_w, const float* scaler, int out, int in, int G,
+                            int accumulate, float* g_base, float* g_spline, float* g_scaler, hipStream_t s);
 hipError_t kan_gemm(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, int M,
                     int N, int64_t K, int splits, float* C, float* out, hipStream_t s);
 // grid update (kan.py:168-215).  New knots [in][12] from the six order statistics q[6][in]

@@ -8,14 +8,15 @@ weight, a uniform-noise curve fitted by least squares onto the B-spline basis, k
 scaler), so ``torch.manual_seed(s)`` gives bit-identical parameters.  The B-spline basis used
 for that fit is the Cox-de Boor recursion of kan.py:94-104, vectorised over knots.
 
-Supported like run.py uses it: grid_size 5, spline_order 3, SiLU base activation,
-standalone spline scaler.  ``KAN.forward`` and ``KANLinear.forward`` are differentiable
+Supported: spline_order 3 with any grid_size from 1 to 64 (run.py uses 5; the other sizes run the
+any-grid-size kernels of kan.hip), SiLU base activation, standalone spline scaler.  ``KAN.forward`` and ``KANLinear.forward`` are differentiable
 (``_KanFunction``: siren_kan_forward, then siren_kan_backward for any upstream gradient, into the
 parameters and, when asked for, the input), so a user loop with ``loss.backward()`` and
 ``torch.optim`` trains them as it trains the reference's modules (kan.py:153-166, 268-273); the
 fused fit goes through ``KanEngine`` / ``run.train(arch='kan')``.  ``KANLinear.update_grid`` /
 ``KAN.forward(x, update_grid=True)`` (kan.py:168-215, :274-279) run on the HIP path too
-(siren_kan_grid_*: knots, per-input Gram sums in fp64, Cholesky refit); ``regularization_loss``
+(siren_kan_grid_*: knots, per-input Gram sums in fp64, Cholesky refit) at grid_size 5, whose 8 x 8
+Gram matrices those kernels are written for; ``regularization_loss``
 (kan.py:217-237, :281-285) is the reference's torch expression on the parameters.
 """
 from __future__ import annotations
@@ -106,6 +107,7 @@ class KANLinear(torch.nn.Module):
         refit succeeded: an input whose Gram matrix is rank deficient (a constant input, fewer than
         8 distinct useful samples) raises SirenError and leaves the layer as it was."""
         _hip_check_layer(self)
+        _update_grid_check(self.grid_size)
         if not x.is_cuda:
             raise RuntimeError("KANLinear.update_grid runs on the HIP path only (CUDA tensors)")
         if x.dim() != 2 or x.size(1) != self.in_features:
@@ -149,9 +151,22 @@ class KANLinear(torch.nn.Module):
         return regularize_activation * activation + regularize_entropy * entropy
 
 
+def _hip_check_grid(grid_size, spline_order):
+    if spline_order != 3:
+        raise NotImplementedError(f"HIP KAN path: spline_order=3 only (got {spline_order})")
+    if not 1 <= int(grid_size) <= _lib.KAN_MAX_GRID or int(grid_size) != grid_size:
+        raise NotImplementedError(f"HIP KAN path: grid_size from 1 to {_lib.KAN_MAX_GRID} (got {grid_size})")
+
+
+def _update_grid_check(grid_size):
+    if grid_size != 5:
+        raise NotImplementedError(
+            f"update_grid: the refit's Gram and Cholesky kernels are 8 x 8 (grid_size=5); grid_size={grid_size} "
+            "trains and infers on the HIP path but cannot refit its grid")
+
+
 def _hip_check_layer(lay: "KANLinear"):
-    if lay.grid_size != 5 or lay.spline_order != 3:
-        raise NotImplementedError("HIP KAN path: grid_size=5, spline_order=3 (kan.py defaults)")
+    _hip_check_grid(lay.grid_size, lay.spline_order)
     if not lay.enable_standalone_scale_spline or not isinstance(lay.base_activation, torch.nn.SiLU):
         raise NotImplementedError("HIP KAN path: SiLU base and a standalone spline scaler")
     # kan.hip finds a basis span by counting knots <= x, which equals kan.py:94-96's span predicate
@@ -170,7 +185,9 @@ def _kan_splits(rows: int) -> int:
 
 def _net(widths, layers, params) -> SirenKanNet:
     n = SirenKanNet()
-    n.n_layers = len(layers)
+    n.n_layers, n.grid_size = len(layers), layers[0].grid_size
+    if any(lay.grid_size != n.grid_size for lay in layers):
+        raise NotImplementedError("HIP KAN path: one grid_size for every layer of a stack")
     for l, w in enumerate(widths):
         n.width[l] = w
     for l, lay in enumerate(layers):
@@ -250,12 +267,13 @@ class KAN(torch.nn.Module):
             for i, o in zip(layers_hidden, layers_hidden[1:]))
 
     def hip_check(self):
-        if self.grid_size != 5 or self.spline_order != 3:
-            raise NotImplementedError("HIP KAN path: grid_size=5, spline_order=3 (kan.py defaults)")
+        _hip_check_grid(self.grid_size, self.spline_order)
         if len(self.layers) > _lib.KAN_MAX_LAYERS or self.widths[-1] != 1:
             raise NotImplementedError(f"HIP KAN path: <= {_lib.KAN_MAX_LAYERS} layers, last width 1")
         for lay in self.layers:
             _hip_check_layer(lay)
+            if lay.grid_size != self.grid_size:
+                raise NotImplementedError("HIP KAN path: one grid_size for every layer of a stack")
 
     def param_index(self):
         pos = {n: k for k, (n, _) in enumerate(self.named_parameters())}
@@ -267,7 +285,7 @@ class KAN(torch.nn.Module):
         named_parameters order, e.g. views of a flat vector)."""
         self.hip_check()
         n = SirenKanNet()
-        n.n_layers = len(self.layers)
+        n.n_layers, n.grid_size = len(self.layers), self.grid_size
         for l, w in enumerate(self.widths):
             n.width[l] = w
         params = tensors if tensors is not None else [p for _, p in self.named_parameters()]
@@ -283,6 +301,7 @@ class KAN(torch.nn.Module):
             raise RuntimeError("KAN.forward runs on the HIP path only (CUDA tensors)")
         self.hip_check()
         if update_grid:
+            _update_grid_check(self.grid_size)
             # kan.py:274-279: per layer, update_grid(x) then x = layer(x); the layer forwards run the
             # lone-layer route in row chunks, so the output is the updated model's (not differentiable:
             # the reference's update_grid is @torch.no_grad too, and the refit moves the parameters)

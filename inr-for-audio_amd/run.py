@@ -87,7 +87,7 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
           min_learning_rate=1e-6, alpha=0.0, prev_ckpt_path=None, visualization=False, *,
           filename=None, data_dir="data", seed=None, micro_batch=1 << 20, use_graph=True,
           device=None, verbose=False, multichannel=False, patience=200, restated_losses=False,
-          stft_loss="stft", split_spectral=False):
+          stft_loss="stft", split_spectral=False, kan_grid_size=5):
     """Fit one clip; returns the checkpoint path (run.py:400).  Extra keyword-only knobs:
     ``filename`` (default ``{data_dir}/{inst}.wav`` as run.py:33), ``seed`` (torch.manual_seed
     before model construction), ``micro_batch`` (rows per fused micro-batch), ``use_graph``
@@ -104,13 +104,17 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     only when it is not 'stft'), ``split_spectral`` (with ``restated_losses``: the engines' split step,
     which fits with these losses across micro-batches and data-parallel ranks -- a clip longer than
     ``micro_batch``, or more than one GPU, and the only way arch='kan' fits with them; recorded in
-    parameters.json only when true)."""
+    parameters.json only when true), ``kan_grid_size`` (arch='kan': the ``grid_size`` of KAN(...), 1 to 64;
+    run.py:93 leaves it at kan.py's default 5; recorded in parameters.json only when it is not 5;
+    ``prev_ckpt_path`` resumes a checkpoint of the same grid size)."""
     if method not in ("wave", "mdct"):
         raise ValueError("specify the correct fitting method as wave or mdct (run.py:77-78)")
     if method == "mdct" and bwe:
         raise NotImplementedError("bwe is a waveform-mode feature (run.py:127-131)")
     if arch not in ("mlp", "kan"):
         raise NotImplementedError(f"arch={arch!r}: the reference builds 'kan' or the MLP (run.py:92-96)")
+    if arch != "kan" and kan_grid_size != 5:
+        raise ValueError(f"kan_grid_size={kan_grid_size!r} is the KAN's grid size: it needs arch='kan'")
     if arch == "kan" and method == "mdct":
         raise NotImplementedError("arch='kan' takes 1-D coordinates (run.py:92 builds KAN([1, H, H, 1]))")
     spectral = loss_mode == "snr" or alpha != 0.0
@@ -167,7 +171,8 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     if seed is not None:
         torch.manual_seed(seed)
     if arch == "kan":  # run.py:92-93
-        model = KAN([1, num_hidden_features, num_hidden_features, 1])
+        model = KAN([1, num_hidden_features, num_hidden_features, 1], grid_size=kan_grid_size)
+        model.hip_check()  # a grid size or order the HIP path refuses, before any data is read further
     else:
         model = SirenWithSnakeTanh(in_features=input_dimension, out_features=1,
                                    hidden_features=num_hidden_features, num_sine=num_sine,
@@ -306,6 +311,8 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         }
         if stft_loss != "stft":
             params["stft_loss"] = stft_loss
+        if kan_grid_size != 5:
+            params["kan_grid_size"] = kan_grid_size
         if split_spectral:
             params["split_spectral"] = True
         if visualization:
