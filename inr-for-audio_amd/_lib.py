@@ -240,6 +240,12 @@ _SIGS = {
     "siren_kan_grid_knots": (ctypes.c_int, [_p, _i32, ctypes.c_double, ctypes.c_double, _p, _p]),
     "siren_kan_grid_gram": (ctypes.c_int, [_p, _i64, _i32, _p, _p, _i32, _p, _p, _p]),
     "siren_kan_grid_refit": (ctypes.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _p, _p]),
+    # KANLinear.regrid: the same three steps from a grid of g_old intervals onto one of g_new
+    "siren_kan_regrid_pass_rows": (_i64, [_i32, _i32, _i32]),
+    "siren_kan_regrid_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "siren_kan_regrid_knots": (ctypes.c_int, [_p, _i32, _i32, ctypes.c_double, ctypes.c_double, _p, _p]),
+    "siren_kan_regrid_gram": (ctypes.c_int, [_p, _i64, _i32, _i32, _i32, _p, _p, _i32, _p, _p, _p]),
+    "siren_kan_regrid_refit": (ctypes.c_int, [_p, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
     "siren_profile_enable": (ctypes.c_int, [_i32]),
     "siren_profile_reset": (ctypes.c_int, []),
     "siren_profile_mask": (ctypes.c_int, [ctypes.c_uint32]),

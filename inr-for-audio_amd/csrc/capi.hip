@@ -1603,4 +1603,49 @@ int siren_kan_grid_refit(const double* gram, int32_t in, int32_t out, const floa
   return SIREN_OK;
 }
 
+// ---- KAN refit onto a grid of another size (KANLinear.regrid) ----
+static bool kan_regrid_g_ok(int32_t g_old, int32_t g_new) {
+  return g_old >= 1 && g_old <= SIREN_KAN_MAX_GRID && g_new >= 1 && g_new <= SIREN_KAN_MAX_GRID;
+}
+
+int64_t siren_kan_regrid_pass_rows(int32_t in, int32_t g_old, int32_t g_new) {
+  return kan_grid_in_ok(in) && kan_regrid_g_ok(g_old, g_new) ? kan_regrid_pass_rows(in, g_old, g_new) : -1;
+}
+
+int64_t siren_kan_regrid_workspace_bytes(int64_t rows, int32_t in, int32_t g_old, int32_t g_new) {
+  if (rows < 1 || !kan_grid_in_ok(in) || !kan_regrid_g_ok(g_old, g_new)) return -1;
+  return (int64_t)sizeof(double) * kan_regrid_part_doubles(rows, in, g_old, g_new);
+}
+
+int siren_kan_regrid_knots(const float* q, int32_t in, int32_t g_new, double margin, double grid_eps, float* grid_new,
+                           void* stream) {
+  if (g_new < 1 || g_new > SIREN_KAN_MAX_GRID) return SIREN_ERR_CONFIG;
+  if (!q || !grid_new) return SIREN_ERR_NULL;
+  if (!kan_grid_in_ok(in)) return SIREN_ERR_SHAPE;
+  SIREN_TRY(kan_regrid_knots(q, in, g_new, (float)margin, (float)(2 * margin), (float)grid_eps, (float)(1 - grid_eps),
+                             grid_new, S(stream)));
+  return SIREN_OK;
+}
+
+int siren_kan_regrid_gram(const float* x, int64_t rows, int32_t in, int32_t g_old, int32_t g_new,
+                          const float* grid_old, const float* grid_new, int32_t accumulate, double* gram, void* ws,
+                          void* stream) {
+  if (!kan_regrid_g_ok(g_old, g_new)) return SIREN_ERR_CONFIG;
+  if (!x || !grid_old || !grid_new || !gram || !ws) return SIREN_ERR_NULL;
+  if (rows < 1 || !kan_grid_in_ok(in)) return SIREN_ERR_SHAPE;
+  SIREN_TRY(kan_regrid_gram(x, grid_old, grid_new, rows, in, g_old, g_new, accumulate != 0, (double*)ws, gram,
+                            S(stream)));
+  return SIREN_OK;
+}
+
+int siren_kan_regrid_refit(const double* gram, int32_t in, int32_t out, int32_t g_old, int32_t g_new,
+                           const float* spline_w, const float* scaler, float* spline_w_new, int32_t* status,
+                           void* stream) {
+  if (!kan_regrid_g_ok(g_old, g_new)) return SIREN_ERR_CONFIG;
+  if (!gram || !spline_w || !spline_w_new || !status) return SIREN_ERR_NULL;  // scaler NULL: all ones
+  if (!kan_grid_in_ok(in) || out < 1 || out > 4096) return SIREN_ERR_SHAPE;
+  SIREN_TRY(kan_regrid_refit(gram, in, out, g_old, g_new, spline_w, scaler, spline_w_new, status, S(stream)));
+  return SIREN_OK;
+}
+
 }  // extern "C"

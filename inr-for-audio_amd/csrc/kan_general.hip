@@ -667,4 +667,325 @@ hipError_t kang_param_grads(const float* dW, const float* spline_w, const float*
   return hipGetLastError();
 }
 
+// ---- refit onto a grid of another size (KANLinear.regrid) ---------------------------------------
+// kan.hip's grid update with the old and the new basis each at its own size: per input i
+//   c_new[i] = G_nn[i]^-1 G_no[i] c_old[i],  G_nn (Gn+3) x (Gn+3),  G_no (Gn+3) x (Go+3)
+// (Go = Gn = 5 is kan_grid_*'s case).  A row touches 10 entries of G_nn's upper band and one 4 x 4
+// block of G_no, the block of its new span s and old span r.  G_no is a staircase: two pairs of
+// overlapping half-open spans never share s + r.  (Take (s, r) and (s', r') with s < s' and r > r':
+// an x in the first pair and a y in the second give y >= gn[s'] >= gn[s+1] > x >= go[r] >= go[r'+1]
+// > y.)  So slot t = s + r addresses a compact accumulator without collisions, of
+//   E = 4 (Gn+3) + 16 (Gn + Go + 11) doubles per input: G_nn's band [c][d - c], then [t][p][k]
+// (2492 at 64 -> 64, where the dense pair of matrices has 8978), and the per-slice partials have
+// that size too.
+//   kan_regrid_knots  the new knots from Gn + 1 order statistics of each input
+//   kan_regrid_gram   row slices into compact fp64 partials, then a fixed-order sum into dense Grams
+//   kan_regrid_refit  banded Cholesky of G_nn, M = G_nn^-1 G_no, spline_w_new = fp32(M c_old)
+constexpr int KR_ROWS = 8;                                             // rows a lane loads before it evaluates them
+constexpr int KR_MAX_SLICES = 256, KR_MIN_SLICES = 8, KR_BLOCKS = 1024;
+constexpr size_t kKrLdsMax = 160 * 1024;
+
+struct KrDims {
+  KgDims o, n;  // the old and the new grid
+  int nn, e;    // doubles of G_nn's band; of one input's compact accumulator
+};
+__host__ __device__ constexpr KrDims kr_dims(int Go, int Gn) {
+  return KrDims{kg_dims(Go), kg_dims(Gn), 4 * (Gn + 3), 4 * (Gn + 3) + 16 * (Gn + Go + 11)};
+}
+// LDS of one input: its accumulator, both knot rows and both reciprocal tables
+__host__ __device__ constexpr size_t kr_lds_per_input(const KrDims& d) {
+  return sizeof(double) * d.e + sizeof(float) * (d.o.gst + d.n.gst + d.o.vst + d.n.vst);
+}
+// inputs of a block (one wave, lane = input): what fits the CU's LDS, 64 at the most
+__host__ __device__ constexpr int kr_ic(const KrDims& d) {
+  return (int)(kKrLdsMax / kr_lds_per_input(d) < 64 ? kKrLdsMax / kr_lds_per_input(d) : 64);
+}
+static_assert(kr_ic(kr_dims(KG_MAX_GRID, KG_MAX_GRID)) >= 1, "one input's accumulator outgrows the LDS");
+
+// kan.py:183-212 op for op in fp32 as kan_grid_knots_kernel, with Gn for 5:
+//   step = (x_last - x_first + 2 margin) / Gn
+//   knot_k = eps ((k step + x_first) - margin) + (1 - eps) q_k,  k = 0..Gn
+// extended by three steps on either side.  q[k][i]: the k-th of the Gn + 1 order statistics of input i.
+__global__ __launch_bounds__(256) void kan_regrid_knots_kernel(const float* __restrict__ q, int in, int Gn, float margin,
+                                                               float margin2, float eps, float one_eps,
+                                                               float* __restrict__ grid) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= in) return;
+  const float x0 = q[i], xl = q[Gn * (int64_t)in + i];
+  const float step = ((xl - x0) + margin2) / (float)Gn;
+  float* out = grid + (int64_t)i * (Gn + 7);
+  float g0 = 0.f, gl = 0.f;
+  for (int k = 0; k <= Gn; ++k) {
+    const float gu = ((float)k * step + x0) - margin;
+    const float g = eps * gu + one_eps * q[k * (int64_t)in + i];
+    out[3 + k] = g;
+    g0 = k == 0 ? g : g0;
+    gl = g;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) out[k] = g0 - step * (float)(3 - k);
+#pragma unroll
+  for (int k = 1; k <= 3; ++k) out[Gn + 3 + k] = gl + step * (float)k;
+}
+
+// kan_grid_gram_kernel with run-time sizes: one wave per block, lane = input i0 + lane of the
+// block's ic = kr_ic inputs (X rows are read along the lanes, each element once).  Dynamic LDS:
+//   acc [E][ic] doubles (lane-consecutive: no bank conflicts whatever the spans), then
+//   gk_o [ic][gst_o]  gk_n [ic][gst_n]  inv_o [ic][vst_o]  inv_n [ic][vst_n] floats.
+// Block (cg, z) takes the 8-row tiles z, z + Z, ... and writes part[z][e][i] for every e.
+__global__ __launch_bounds__(64) void kan_regrid_gram_kernel(const float* __restrict__ X,
+                                                             const float* __restrict__ grid_old,
+                                                             const float* __restrict__ grid_new, int64_t N, int in,
+                                                             int Go, int Gn, int icb, double* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) double kr_smem[];
+  const KrDims d = kr_dims(Go, Gn);
+  const int lane = threadIdx.x, i0 = blockIdx.x * icb;
+  const int ic = in - i0 < icb ? in - i0 : icb;
+  double* acc = kr_smem;
+  float* gko = reinterpret_cast<float*>(acc + (size_t)d.e * icb);
+  float* gkn = gko + icb * d.o.gst;
+  float* ivo = gkn + icb * d.n.gst;
+  float* ivn = ivo + icb * d.o.vst;
+  kg_fill_knots(gko, grid_old, i0, ic, d.o);
+  kg_fill_knots(gkn, grid_new, i0, ic, d.n);
+  kg_fill_inv(ivo, grid_old, i0, ic, d.o);
+  kg_fill_inv(ivn, grid_new, i0, ic, d.n);
+  for (int e = lane; e < d.e * icb; e += 64) acc[e] = 0.0;
+  __syncthreads();
+  const bool on = lane < ic;
+  double* a = acc + lane;  // a[e * icb]
+  const int nbn = d.n.nb, nbo = d.o.nb;
+  const int64_t ntile = (N + KR_ROWS - 1) / KR_ROWS;
+  for (int64_t t = blockIdx.y; t < ntile; t += gridDim.y) {
+    float x[KR_ROWS];
+#pragma unroll
+    for (int r = 0; r < KR_ROWS; ++r) {
+      const int64_t n = t * KR_ROWS + r;
+      x[r] = (on && n < N) ? X[n * in + i0 + lane] : 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < KR_ROWS; ++r) {
+      if (!on || t * KR_ROWS + r >= N) continue;
+      float wn[4], wo[4], unused[4];
+      const int sn = kg_bases_window<false, false>(x[r], gkn + lane * d.n.gst, d.n.ng, wn, unused, ivn + lane * d.n.vst);
+      if (sn < 0) continue;
+      const int so = kg_bases_window<false, false>(x[r], gko + lane * d.o.gst, d.o.ng, wo, unused, ivo + lane * d.o.vst);
+      double* blk = a + (int64_t)(d.nn + 16 * (sn + (so < 0 ? 0 : so))) * icb;
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int c = sn - 3 + p;
+        if (c < 0 || c >= nbn) continue;
+        const double bp = (double)wn[p];
+#pragma unroll
+        for (int k = p; k < 4; ++k)
+          if (sn - 3 + k < nbn) a[(4 * c + (k - p)) * icb] += bp * (double)wn[k];
+        if (so >= 0) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int dd = so - 3 + k;
+            if (dd >= 0 && dd < nbo) blk[(4 * p + k) * icb] += bp * (double)wo[k];
+          }
+        }
+      }
+    }
+  }
+  if (!on) return;
+  double* out = part + (int64_t)blockIdx.y * d.e * in + i0 + lane;
+  for (int e = 0; e < d.e; ++e) out[(int64_t)e * in] = a[e * icb];
+}
+
+// gram[i] = {G_nn [NBn][NBn], G_no [NBn][NBo]} = (accumulate ? gram[i] : 0) + the slices in order.
+// One thread per dense entry.  G_nn (c, d): the band entry (min, |c - d|), an exact zero outside the
+// band.  G_no (c, d): the blocks of the spans s = c + 3 - p, r = d + 3 - k that overlap on this
+// input's knots (the only ones a row can have hit; each has its own slot s + r), in (p, k) order.
+__global__ __launch_bounds__(256) void kan_regrid_gram_reduce_kernel(const double* __restrict__ part, int slices, int in,
+                                                                     int Go, int Gn, const float* __restrict__ grid_old,
+                                                                     const float* __restrict__ grid_new, int accumulate,
+                                                                     double* __restrict__ gram) {
+  const KrDims d = kr_dims(Go, Gn);
+  const int nbn = d.n.nb, nbo = d.o.nb, per = nbn * (nbn + nbo);
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)per * in) return;
+  const int e = (int)(idx / in), i = (int)(idx - (int64_t)e * in);
+  double* dst = gram + (int64_t)i * per + e;
+  double v = accumulate ? *dst : 0.0;
+  const int64_t zs = (int64_t)d.e * in;
+  if (e < nbn * nbn) {
+    const int c = e / nbn, dd = e - c * nbn, lo = c < dd ? c : dd, w = c < dd ? dd - c : c - dd;
+    if (w <= 3) {
+      const double* p = part + (int64_t)(4 * lo + w) * in + i;
+      for (int z = 0; z < slices; ++z) v += p[z * zs];
+    }
+  } else {
+    const int f = e - nbn * nbn, c = f / nbo, dd = f - c * nbo;
+    const float* go = grid_old + (int64_t)i * d.o.ng;
+    const float* gn = grid_new + (int64_t)i * d.n.ng;
+    for (int p = 0; p < 4; ++p) {
+      const int s = c + 3 - p;
+      if (s > d.n.ng - 2) continue;
+      for (int k = 0; k < 4; ++k) {
+        const int r = dd + 3 - k;
+        if (r > d.o.ng - 2) continue;
+        const float lo = gn[s] > go[r] ? gn[s] : go[r], hi = gn[s + 1] < go[r + 1] ? gn[s + 1] : go[r + 1];
+        if (!(lo < hi)) continue;
+        const double* q = part + (int64_t)(d.nn + 16 * (s + r) + 4 * p + k) * in + i;
+        for (int z = 0; z < slices; ++z) v += q[z * zs];
+      }
+    }
+  }
+  *dst = v;
+}
+
+// One block per input.  Dynamic LDS: Lb [NBn + 3][4] doubles, the banded Cholesky factor
+// Lb[r][r - j] = L[r][j] (j = r-3 .. r; entries off the matrix and three rows past it are zeros, so
+// the substitutions need no edge cases), Ab [NBn][4], G_nn's lower band in the same layout, then
+// M [NBn][NBo], G_no solved in place.
+//   thread 0      G_nn = L L^T with kan_grid_solve_kernel's pivot rule and order of operations
+//   thread c      column c of G_no: L y = b, L^T x = y, three values of y (x) back in registers
+//   thread o, ..  spline_w_new[o][i][:] = fp32(M (spline_w[o][i][:] * scaler[o][i]))
+// A rank-deficient input counts in status[0], lowers status[1] to its index and writes nothing.
+__global__ __launch_bounds__(256) void kan_regrid_refit_kernel(const double* __restrict__ gram, int in, int out, int Go,
+                                                               int Gn, const float* __restrict__ spline_w,
+                                                               const float* __restrict__ scaler,
+                                                               float* __restrict__ spline_w_new,
+                                                               int* __restrict__ status) {
+  extern __shared__ __attribute__((aligned(16))) double kr_smem[];
+  __shared__ int ok_s;
+  const int nbn = Gn + 3, nbo = Go + 3, i = blockIdx.x, tid = threadIdx.x;
+  const double* Gnn = gram + (int64_t)i * nbn * (nbn + nbo);
+  const double* Gno = Gnn + nbn * nbn;
+  double* Lb = kr_smem;
+  double* Ab = Lb + 4 * (nbn + 3);  // Ab[r][r - j] = G_nn[r][j], its lower band
+  double* M = Ab + 4 * nbn;
+  for (int e = tid; e < 4 * (nbn + 3); e += blockDim.x) Lb[e] = 0.0;
+  for (int e = tid; e < 4 * nbn; e += blockDim.x) {
+    const int r = e >> 2, j = r - (e & 3);
+    Ab[e] = j >= 0 ? Gnn[r * nbn + j] : 0.0;
+  }
+  for (int e = tid; e < nbn * nbo; e += blockDim.x) M[e] = Gno[e];
+  __syncthreads();
+  if (tid == 0) {
+    double dmax = 0.0;
+    for (int c = 0; c < nbn; ++c) dmax = Ab[4 * c] > dmax ? Ab[4 * c] : dmax;
+    const double thr = dmax * 0x1p-40;
+    bool ok = dmax > 0.0;
+    for (int j = 0; j < nbn && ok; ++j) {
+      double p = Ab[4 * j];
+      for (int k = j < 3 ? 0 : j - 3; k < j; ++k) p -= Lb[4 * j + (j - k)] * Lb[4 * j + (j - k)];
+      if (!(p > thr)) {
+        ok = false;
+        break;
+      }
+      const double l = sqrt(p);
+      Lb[4 * j] = l;
+      for (int r = j + 1; r < nbn && r <= j + 3; ++r) {
+        double v = Ab[4 * r + (r - j)];
+        for (int k = r < 3 ? 0 : r - 3; k < j; ++k) v -= Lb[4 * r + (r - k)] * Lb[4 * j + (j - k)];
+        Lb[4 * r + (r - j)] = v / l;
+      }
+    }
+    if (!ok) {
+      atomicAdd(&status[0], 1);
+      atomicMin(&status[1], i);
+    }
+    ok_s = ok ? 1 : 0;
+  }
+  __syncthreads();
+  if (!ok_s) return;  // the whole block
+  for (int c = tid; c < nbo; c += blockDim.x) {
+    double y1 = 0.0, y2 = 0.0, y3 = 0.0;  // y[r-1], y[r-2], y[r-3]
+    for (int r = 0; r < nbn; ++r) {
+      const double* l = Lb + 4 * r;
+      double v = M[r * nbo + c];
+      v -= l[3] * y3;
+      v -= l[2] * y2;
+      v -= l[1] * y1;
+      v /= l[0];
+      M[r * nbo + c] = v;
+      y3 = y2, y2 = y1, y1 = v;
+    }
+    double x1 = 0.0, x2 = 0.0, x3 = 0.0;  // x[r+1], x[r+2], x[r+3]
+    for (int r = nbn - 1; r >= 0; --r) {
+      double v = M[r * nbo + c];
+      v -= Lb[4 * (r + 1) + 1] * x1;
+      v -= Lb[4 * (r + 2) + 2] * x2;
+      v -= Lb[4 * (r + 3) + 3] * x3;
+      v /= Lb[4 * r];
+      M[r * nbo + c] = v;
+      x3 = x2, x2 = x1, x1 = v;
+    }
+  }
+  __syncthreads();
+  for (int o = tid; o < out; o += blockDim.x) {
+    const int64_t idx = (int64_t)o * in + i;
+    const float s = scaler ? scaler[idx] : 1.0f;
+    const float* w = spline_w + idx * nbo;
+    float* wn = spline_w_new + idx * nbn;
+    for (int r = 0; r < nbn; ++r) {
+      const double* m = M + r * nbo;
+      double a = 0.0;
+      for (int c = 0; c < nbo; ++c) a += m[c] * (double)(w[c] * s);
+      wn[r] = (float)a;
+    }
+  }
+}
+
+static bool kr_grids_ok(int Go, int Gn) { return kg_grid_ok(Go) && kg_grid_ok(Gn); }
+
+hipError_t kan_regrid_knots(const float* q, int in, int Gn, float margin, float margin2, float eps, float one_eps,
+                            float* grid, hipStream_t s) {
+  if (in <= 0 || !kg_grid_ok(Gn)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kan_regrid_knots_kernel, dim3((in + 255) / 256), dim3(256), 0, s, q, in, Gn, margin, margin2, eps,
+                     one_eps, grid);
+  return hipGetLastError();
+}
+
+// inputs per block: kr_ic, and no more than the layer has (a narrow layer asks for less LDS)
+static int kr_block_inputs(int in, const KrDims& d) { return in < kr_ic(d) ? in : kr_ic(d); }
+
+// row slices of the Gram kernel: about KR_BLOCKS one-wave blocks over the column groups
+int kan_regrid_slices(int64_t N, int in, int Go, int Gn) {
+  const int icb = kr_block_inputs(in, kr_dims(Go, Gn)), ncg = (in + icb - 1) / icb;
+  int z = KR_BLOCKS / ncg;
+  z = z < KR_MIN_SLICES ? KR_MIN_SLICES : (z > KR_MAX_SLICES ? KR_MAX_SLICES : z);
+  const int64_t ntile = (N + KR_ROWS - 1) / KR_ROWS;
+  return ntile < z ? (int)(ntile < 1 ? 1 : ntile) : z;
+}
+int64_t kan_regrid_pass_rows(int in, int Go, int Gn) {
+  return (int64_t)KR_ROWS * kan_regrid_slices(INT64_MAX / 2, in, Go, Gn);
+}
+int64_t kan_regrid_part_doubles(int64_t N, int in, int Go, int Gn) {
+  return (int64_t)kan_regrid_slices(N, in, Go, Gn) * kr_dims(Go, Gn).e * in;
+}
+
+hipError_t kan_regrid_gram(const float* X, const float* grid_old, const float* grid_new, int64_t N, int in, int Go,
+                           int Gn, int accumulate, double* part, double* gram, hipStream_t s) {
+  if (N <= 0 || in <= 0 || !kr_grids_ok(Go, Gn)) return hipErrorInvalidValue;
+  const KrDims d = kr_dims(Go, Gn);
+  const int icb = kr_block_inputs(in, d), z = kan_regrid_slices(N, in, Go, Gn);
+  const size_t lds = kr_lds_per_input(d) * icb;
+  static bool raised = false;
+  const hipError_t e = kg_head_lds(kan_regrid_gram_kernel, lds, raised);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kan_regrid_gram_kernel, dim3((in + icb - 1) / icb, z), dim3(64), lds, s, X, grid_old, grid_new, N,
+                     in, Go, Gn, icb, part);
+  const int64_t total = (int64_t)d.n.nb * (d.n.nb + d.o.nb) * in;
+  hipLaunchKernelGGL(kan_regrid_gram_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, part, z, in,
+                     Go, Gn, grid_old, grid_new, accumulate, gram);
+  return hipGetLastError();
+}
+
+hipError_t kan_regrid_refit(const double* gram, int in, int out, int Go, int Gn, const float* spline_w,
+                            const float* scaler, float* spline_w_new, int* status, hipStream_t s) {
+  if (in <= 0 || out <= 0 || !kr_grids_ok(Go, Gn)) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(status, 0, sizeof(int), s);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(status + 1, 0x7f, sizeof(int), s);  // above every index
+  if (e != hipSuccess) return e;
+  const size_t lds = sizeof(double) * (4 * (Gn + 6) + 4 * (Gn + 3) + (size_t)(Gn + 3) * (Go + 3));  // 40 KB at 64 -> 64
+  hipLaunchKernelGGL(kan_regrid_refit_kernel, dim3(in), dim3(256), lds, s, gram, in, out, Go, Gn, spline_w, scaler,
+                     spline_w_new, status);
+  return hipGetLastError();
+}
+
 }  // namespace siren

@@ -353,6 +353,19 @@ hipError_t kan_grid_gram(const float* X, const float* grid_old, const float* gri
 // status[0] = rank-deficient inputs (pivot <= 2^-40 max diagonal), status[1] = the first of them
 hipError_t kan_grid_refit(const double* gram, int in, int out, const float* spline_w, const float* scaler, double* M,
                           float* spline_w_new, int* status, hipStream_t s);
+// The refit onto a grid of another size (kan_general.hip, "refit onto a grid of another size"): old
+// knots [in][Go + 7], new knots [in][Gn + 7], both sizes 1 .. KG_MAX_GRID.  q [Gn + 1][in];
+// gram [in]{G_nn [Gn+3][Gn+3], G_no [Gn+3][Go+3]} fp64; part: kan_regrid_part_doubles doubles of
+// scratch (compact: what can be non-zero); scaler may be null (all ones); refit needs no scratch
+hipError_t kan_regrid_knots(const float* q, int in, int Gn, float margin, float margin2, float eps, float one_eps,
+                            float* grid, hipStream_t s);
+int kan_regrid_slices(int64_t N, int in, int Go, int Gn);
+int64_t kan_regrid_pass_rows(int in, int Go, int Gn);
+int64_t kan_regrid_part_doubles(int64_t N, int in, int Go, int Gn);
+hipError_t kan_regrid_gram(const float* X, const float* grid_old, const float* grid_new, int64_t N, int in, int Go,
+                           int Gn, int accumulate, double* part, double* gram, hipStream_t s);
+hipError_t kan_regrid_refit(const double* gram, int in, int out, int Go, int Gn, const float* spline_w,
+                            const float* scaler, float* spline_w_new, int* status, hipStream_t s);
 
 struct OptState {      // device-resident optimizer + ReduceLROnPlateau state (run.py:116-117)
   double lr;           // current learning rate (param_groups[0]['lr'])

@@ -18,6 +18,12 @@ fused fit goes through ``KanEngine`` / ``run.train(arch='kan')``.  ``KANLinear.u
 (siren_kan_grid_*: knots, per-input Gram sums in fp64, Cholesky refit) at grid_size 5, whose 8 x 8
 Gram matrices those kernels are written for; ``regularization_loss``
 (kan.py:217-237, :281-285) is the reference's torch expression on the parameters.
+
+``KANLinear.regrid`` / ``KAN.regrid`` (no counterpart in the reference) return a new layer / model on a
+grid of another size, 1 to 64, fitted to this one over a batch (siren_kan_regrid_*: the same three
+steps with Gram matrices of (Gn+3)^2 and (Gn+3) x (Go+3)): the step of a coarse-to-fine grid
+curriculum, ``run.train(kan_prev_grid_size=...)``.  They refit the unscaled coefficients and keep the
+layer's function, unlike update_grid, which stores a scaled fit undivided.
 """
 from __future__ import annotations
 
@@ -142,6 +148,60 @@ class KANLinear(torch.nn.Module):
         self.grid.copy_(grid_new)
         self.spline_weight.data.copy_(sw_new)
 
+    @torch.no_grad()
+    def regrid(self, x: torch.Tensor, grid_size: int, margin=0.01, chunk: int = 1 << 20) -> "KANLinear":
+        """A new layer at `grid_size` (1 to 64, the layer's own size included) that computes this
+        layer's function on knots taken from x (batch, in): the knots are update_grid's (kan.py:183-212
+        with `grid_size` for the grid size), and the curves are refitted on them by least squares over
+        the batch through the Gram matrices of the new and the old bases (siren_kan_regrid_*).
+        ``base_weight`` and ``spline_scaler`` are copied and ``spline_weight`` is refitted from the
+        UNSCALED coefficients; by linearity the new layer's scaled curves are then the least-squares
+        fit of this layer's scaled curves, so the layer's function is kept up to that fit.  This is
+        deliberately not update_grid's quirk (kan.py:175, :215), which fits the scaled curves and
+        stores the result undivided, scaling the curves by spline_scaler once more.  `self` is never
+        modified; a rank-deficient input (a constant input, fewer than grid_size + 3 distinct useful
+        samples) raises SirenError and returns nothing.  Not differentiable."""
+        _hip_check_layer(self)
+        _hip_check_grid(grid_size, self.spline_order)
+        if not x.is_cuda:
+            raise RuntimeError("KANLinear.regrid runs on the HIP path only (CUDA tensors)")
+        if x.dim() != 2 or x.size(1) != self.in_features:
+            raise ValueError(f"regrid: x must be (batch, {self.in_features})")
+        lib, dev = _lib.load(), x.device
+        s = torch.cuda.current_stream(dev).cuda_stream
+        n_in, n_out, rows, g_old, g_new = self.in_features, self.out_features, x.size(0), self.grid_size, int(grid_size)
+        xs = x.detach().float().contiguous()
+        idx = torch.linspace(0, rows - 1, g_new + 1, dtype=torch.int64)
+        q = torch.sort(xs, dim=0)[0][idx.to(dev)].contiguous()
+        grid_old = self.grid.detach().to(dev, torch.float32).contiguous()
+        grid_new = torch.empty(n_in, g_new + 7, dtype=torch.float32, device=dev)
+        check(lib.siren_kan_regrid_knots(ptr(q), n_in, g_new, float(margin), float(self.grid_eps), ptr(grid_new), s),
+              "siren_kan_regrid_knots")
+        rows_c = max(1, min(int(chunk), rows))
+        ws = torch.empty(int(lib.siren_kan_regrid_workspace_bytes(rows_c, n_in, g_old, g_new)), dtype=torch.uint8,
+                         device=dev)
+        gram = torch.empty(n_in * (g_new + 3) * (g_new + g_old + 6), dtype=torch.float64, device=dev)
+        for lo in range(0, rows, rows_c):
+            hi = min(rows, lo + rows_c)
+            check(lib.siren_kan_regrid_gram(ptr(xs[lo:hi]), hi - lo, n_in, g_old, g_new, ptr(grid_old), ptr(grid_new),
+                                            int(lo > 0), ptr(gram), ptr(ws), s), "siren_kan_regrid_gram")
+        sw = self.spline_weight.detach().to(dev, torch.float32).contiguous()
+        sw_new = torch.empty(n_out, n_in, g_new + 3, dtype=torch.float32, device=dev)
+        status = torch.empty(2, dtype=torch.int32, device=dev)
+        check(lib.siren_kan_regrid_refit(ptr(gram), n_in, n_out, g_old, g_new, ptr(sw), None, ptr(sw_new), ptr(status),
+                                         s), "siren_kan_regrid_refit")
+        bad, first = status.tolist()  # the one host synchronisation
+        if bad:
+            raise _lib.SirenError(
+                f"regrid: the refit of input {first} is rank deficient ({bad} input(s) in all: a constant input, or "
+                f"fewer than {g_new + 3} distinct useful samples); no layer is returned")
+        new = _blank_layer(self, g_new).to(dev)
+        new.grid.copy_(grid_new)
+        new.base_weight.data.copy_(self.base_weight.detach())
+        new.spline_scaler.data.copy_(self.spline_scaler.detach())
+        new.spline_weight.data.copy_(sw_new)
+        return new
+
     def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0):
         """kan.py:217-237: the L1 / entropy surrogate on the spline weights (differentiable torch ops)."""
         mean_abs = self.spline_weight.abs().mean(-1)
@@ -156,6 +216,15 @@ def _hip_check_grid(grid_size, spline_order):
         raise NotImplementedError(f"HIP KAN path: spline_order=3 only (got {spline_order})")
     if not 1 <= int(grid_size) <= _lib.KAN_MAX_GRID or int(grid_size) != grid_size:
         raise NotImplementedError(f"HIP KAN path: grid_size from 1 to {_lib.KAN_MAX_GRID} (got {grid_size})")
+
+
+def _blank_layer(src: "KANLinear", grid_size: int) -> "KANLinear":
+    """A KANLinear with src's shape and settings at another grid size, for regrid to fill; its
+    constructor's random init is drawn from a forked generator, so the caller's stream is untouched."""
+    with torch.random.fork_rng(devices=[]):
+        return KANLinear(src.in_features, src.out_features, grid_size=grid_size, spline_order=src.spline_order,
+                         scale_noise=src.scale_noise, scale_base=src.scale_base, scale_spline=src.scale_spline,
+                         grid_eps=src.grid_eps)
 
 
 def _update_grid_check(grid_size):
@@ -319,6 +388,27 @@ class KAN(torch.nn.Module):
         with torch.no_grad():
             out = kan_forward(self, x.reshape(-1, self.widths[0]), x.device)
         return out.reshape(*lead, 1)
+
+    @torch.no_grad()
+    def regrid(self, x: torch.Tensor, grid_size: int, margin=0.01, chunk: int = 1 << 20) -> "KAN":
+        """A new model at `grid_size` fitted to this one over the coordinates x (..., in), in the order
+        of kan.py:274-279: per layer ``KANLinear.regrid`` on the layer's input h, then h = new_layer(h),
+        so a later layer's knots come from the activations of the already refitted layers before it.
+        This model is not modified and nothing is differentiable; a ``KanEngine`` is sized by the
+        grid, so build a new engine from the returned model."""
+        _hip_check_grid(grid_size, self.spline_order)
+        if not x.is_cuda:
+            raise RuntimeError("KAN.regrid runs on the HIP path only (CUDA tensors)")
+        h = x.detach().reshape(-1, self.widths[0]).float().contiguous()
+        layers = []
+        for lay in self.layers:
+            layers.append(lay.regrid(h, grid_size, margin=margin, chunk=chunk))
+            h = layer_forward(layers[-1], h)
+        new = KAN.__new__(KAN)  # the constructor would draw and fit an init for every layer
+        torch.nn.Module.__init__(new)
+        new.grid_size, new.spline_order, new.widths = int(grid_size), self.spline_order, list(self.widths)
+        new.layers = torch.nn.ModuleList(layers)
+        return new
 
     def regularization_loss(self, regularize_activation=1.0, regularize_entropy=1.0):
         """kan.py:281-285: the layers' regularisation losses summed."""

@@ -39,7 +39,7 @@ import torch
 
 from .encoding import GaussianEncoding
 from .engine import KanEngine, SirenEngine
-from .kan import KAN
+from .kan import KAN, _hip_check_grid
 from .models import SirenWithSnakeTanh
 from .utils import (MDCTFitting, MultiWaveformFitting, WaveformFitting, calculate_snr, get_coord,
                     load_mono_like_librosa, reported_snr)
@@ -87,7 +87,8 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
           min_learning_rate=1e-6, alpha=0.0, prev_ckpt_path=None, visualization=False, *,
           filename=None, data_dir="data", seed=None, micro_batch=1 << 20, use_graph=True,
           device=None, verbose=False, multichannel=False, patience=200, restated_losses=False,
-          stft_loss="stft", split_spectral=False, kan_grid_size=5):
+          stft_loss="stft", split_spectral=False, kan_grid_size=5, kan_prev_grid_size=None,
+          kan_regrid_margin=0.01):
     """Fit one clip; returns the checkpoint path (run.py:400).  Extra keyword-only knobs:
     ``filename`` (default ``{data_dir}/{inst}.wav`` as run.py:33), ``seed`` (torch.manual_seed
     before model construction), ``micro_batch`` (rows per fused micro-batch), ``use_graph``
@@ -106,7 +107,15 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     ``micro_batch``, or more than one GPU, and the only way arch='kan' fits with them; recorded in
     parameters.json only when true), ``kan_grid_size`` (arch='kan': the ``grid_size`` of KAN(...), 1 to 64;
     run.py:93 leaves it at kan.py's default 5; recorded in parameters.json only when it is not 5;
-    ``prev_ckpt_path`` resumes a checkpoint of the same grid size)."""
+    ``prev_ckpt_path`` resumes a checkpoint of the same grid size), ``kan_prev_grid_size`` (arch='kan' with
+    ``prev_ckpt_path``: the grid size the checkpoint was fitted at, for a coarse-to-fine grid curriculum such
+    as 5 -> 10 -> 20: the KAN is built at that size, loaded, and refitted onto ``kan_grid_size`` over the run's
+    coordinates by ``KAN.regrid``; Adam starts afresh, the checkpoint's moments having the old shapes; one
+    process; both sizes are recorded in parameters.json when it is given.  None: the checkpoint is loaded
+    into a model of ``kan_grid_size`` as before), ``kan_regrid_margin`` (that refit's ``margin``, kan.py:169's
+    0.01 by default: an absolute pad of the knot range, which leaves a hidden input whose activations span
+    less than about ``kan_grid_size`` x margin with an empty last knot span, and the refit then refuses it as
+    rank deficient -- pass a smaller one, 0 included, for such a model; recorded when it is not 0.01)."""
     if method not in ("wave", "mdct"):
         raise ValueError("specify the correct fitting method as wave or mdct (run.py:77-78)")
     if method == "mdct" and bwe:
@@ -115,6 +124,9 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         raise NotImplementedError(f"arch={arch!r}: the reference builds 'kan' or the MLP (run.py:92-96)")
     if arch != "kan" and kan_grid_size != 5:
         raise ValueError(f"kan_grid_size={kan_grid_size!r} is the KAN's grid size: it needs arch='kan'")
+    if kan_prev_grid_size is not None and (arch != "kan" or prev_ckpt_path is None):
+        raise ValueError(f"kan_prev_grid_size={kan_prev_grid_size!r} is the grid size of the KAN checkpoint to refit: "
+                         "it needs arch='kan' and prev_ckpt_path")
     if arch == "kan" and method == "mdct":
         raise NotImplementedError("arch='kan' takes 1-D coordinates (run.py:92 builds KAN([1, H, H, 1]))")
     spectral = loss_mode == "snr" or alpha != 0.0
@@ -171,7 +183,10 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     if seed is not None:
         torch.manual_seed(seed)
     if arch == "kan":  # run.py:92-93
-        model = KAN([1, num_hidden_features, num_hidden_features, 1], grid_size=kan_grid_size)
+        if kan_prev_grid_size is not None:
+            _hip_check_grid(kan_grid_size, 3)  # the size to refit onto; the model below is the checkpoint's
+        model = KAN([1, num_hidden_features, num_hidden_features, 1],
+                    grid_size=kan_grid_size if kan_prev_grid_size is None else kan_prev_grid_size)
         model.hip_check()  # a grid size or order the HIP path refuses, before any data is read further
     else:
         model = SirenWithSnakeTanh(in_features=input_dimension, out_features=1,
@@ -195,6 +210,14 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
             raise ValueError(f"checkpoint encoding has {encoding.encoded_size} frequencies, num_freq={num_freq}")
 
     dev = torch.device(device or "cuda")
+    if kan_prev_grid_size is not None:
+        # the checkpoint's curves refitted onto the new grid over the run's own coordinates; the
+        # optimizer state has the old grid's shapes, so Adam starts afresh
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            raise NotImplementedError("kan_prev_grid_size: the refit takes the order statistics of all coordinates "
+                                      "in one process")
+        model = model.to(dev).regrid(model_input.to(dev), kan_grid_size, margin=kan_regrid_margin)
+        ckpt = None
     Engine = KanEngine if arch == "kan" else SirenEngine
     kw = {"loss_mode": loss_mode, "alpha": alpha}
     if arch != "kan":
@@ -311,8 +334,12 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         }
         if stft_loss != "stft":
             params["stft_loss"] = stft_loss
-        if kan_grid_size != 5:
+        if kan_grid_size != 5 or kan_prev_grid_size is not None:
             params["kan_grid_size"] = kan_grid_size
+        if kan_prev_grid_size is not None:
+            params["kan_prev_grid_size"] = kan_prev_grid_size
+            if kan_regrid_margin != 0.01:
+                params["kan_regrid_margin"] = kan_regrid_margin
         if split_spectral:
             params["split_spectral"] = True
         if visualization:
