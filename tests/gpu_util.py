@@ -1,6 +1,7 @@
 """Helpers shared by the GPU test modules that call the C-ABI directly (a plain module like
 errlog.py: no fixtures, nothing collected)."""
 import contextlib
+import math
 
 import numpy as np
 import torch
@@ -55,6 +56,15 @@ def rel(a, b):
 def rel_np(a, b):
     """Relative L2 error of array a against the fp64 array b."""
     return float(np.linalg.norm(np.asarray(a, np.float64) - b) / max(np.linalg.norm(b), 1e-30))
+
+
+def col_reduce_chain(nrows):
+    """Longest fp32 add chain of col_reduce's documented order: rows r0 + rg, r0 + rg + 4, ... per
+    thread, then the four row groups, then the accumulate; two passes above 256 rows (64 row chunks,
+    then the 64 chunk sums)."""
+    if nrows <= 256:
+        return math.ceil(nrows / 4) + 3
+    return math.ceil(math.ceil(nrows / 64) / 4) + 3 + 19
 
 
 def grads(eng, lib):

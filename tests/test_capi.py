@@ -122,6 +122,38 @@ def test_validation_without_device(lib):
     DA = lambda act, e: lib.siren_inner_bwd_dx_act(1, 1, 1, e, act, f(30), 1024, 256, 1, 1, 1, None)  # noqa: E731
     assert DA(3, 1) == 1003
     assert DA(SNAKE, None) == 1002                                          # a Snake needs its Eprev
+    # the unfused fp32 layers (layer_fp32.hip): NULL operands, then shapes
+    BIG = (1 << 31)                                                          # rows above INT32_MAX
+    L = lambda x=1, rows=8, fin=4, out=4, W=1, pre=1: lib.siren_fp32_linear(  # noqa: E731
+        x, rows, fin, out, W, None, f(30), pre, None)
+    assert L(x=None) == 1002 and L(W=None) == 1002 and L(pre=None) == 1002
+    assert L(rows=0) == 1001 and L(rows=BIG) == 1001 and L(fin=0) == 1001 and L(out=0) == 1001
+    LB = lambda x=1, rows=8, fin=4, out=4, W=1, gpre=1, gW=1, gb=None, slab=None, splits=1, tmp=None: (  # noqa: E731
+        lib.siren_fp32_linear_bwd(x, rows, fin, out, W, f(30), gpre, None, gW, gb, slab, splits, tmp, None))
+    assert LB(x=None) == 1002 and LB(W=None) == 1002 and LB(gpre=None) == 1002 and LB(gW=None) == 1002
+    assert LB(splits=2) == 1002                                             # splits > 1 needs its slab
+    assert LB(gb=1) == 1002                                                 # gb needs tmp
+    assert LB(rows=0) == 1001 and LB(rows=BIG) == 1001 and LB(fin=0) == 1001 and LB(out=0) == 1001
+    assert LB(splits=0) == 1001 and LB(splits=0, slab=1) == 1001
+    IDENT, FSNAKE = 0, 3                                                    # enum siren_fp32_act
+    AC = lambda act=IDENT, x=1, rows=8, cols=4, a=None, y=1: lib.siren_fp32_act(  # noqa: E731
+        act, x, rows, cols, a, y, None)
+    assert AC(act=4, x=None) == 1003 and AC(act=-1, x=None) == 1003         # CONFIG is tested before NULL
+    assert AC(x=None) == 1002 and AC(y=None) == 1002
+    assert AC(act=FSNAKE) == 1002                                           # a Snake needs its a
+    assert AC(cols=0) == 1001 and AC(rows=-1) == 1001
+    AB = lambda act=IDENT, x=1, rows=8, cols=4, a=None, gy=1, gx=1, da=None, prod=None, tmp=None: (  # noqa: E731
+        lib.siren_fp32_act_bwd(act, x, rows, cols, a, gy, gx, da, prod, tmp, None))
+    assert AB(act=4, x=None) == 1003 and AB(act=-1, gx=None) == 1003
+    assert AB(x=None) == 1002 and AB(gy=None) == 1002 and AB(gx=None) == 1002
+    assert AB(act=FSNAKE) == 1002
+    assert AB(act=FSNAKE, a=1, da=1, tmp=1) == 1002                         # da needs da_prod ...
+    assert AB(act=FSNAKE, a=1, da=1, prod=1) == 1002                        # ... and tmp
+    assert AB(rows=BIG) == 1001 and AB(cols=0) == 1001
+    # As the code stands, siren_fp32_act takes rows = 0 (an empty array: it launches a kernel that has
+    # nothing to do) while siren_fp32_act_bwd refuses it.  Only the refusal returns before a launch;
+    # the acceptance is pinned on the device (test_gpu_layer_kernels.py::test_act_rows_zero).
+    assert AB(rows=0) == 1001
     # CONFIG is tested before SHAPE
     assert lib.siren_first_bwd_dx(1, 1, 1, 1, 3, f(30), 100, 256, 1, 1, None) == 1003
     b = SirenBatch()

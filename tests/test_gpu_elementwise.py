@@ -8,7 +8,6 @@ output with NaN and compares the whole buffer.  References: torch.optim.Adam(fus
 with fp64 sin / cos, int64 and fp64 column sums, torch's ReduceLROnPlateau."""
 import ctypes
 import functools
-import math
 
 import numpy as np
 import pytest
@@ -18,7 +17,7 @@ import adam_ref
 from inr_for_audio_amd._lib import SirenOptState
 from inr_for_audio_amd.engine import _opt_state_tensor
 from oracle import siren_oracle as orc
-from gpu_util import ok, ptr, release, stream as S, to_dev, within_f16
+from gpu_util import col_reduce_chain as _chain, ok, ptr, release, stream as S, to_dev, within_f16
 
 pytestmark = pytest.mark.gpu
 
@@ -150,15 +149,6 @@ def test_first_fwd_second_pass(lib, dev, H, R, in_dim):
 NROWS = [1, 3, 4, 5, 31, 32, 33, 255, 256, 257, 258, 4097, 8199]
 NCOLS = [1, 63, 64, 65, 259]
 U = 2.0 ** -24
-
-
-def _chain(nrows):
-    """Longest fp32 add chain of col_reduce's documented order: rows r0 + rg, r0 + rg + 4, ... per
-    thread, then the four row groups, then the accumulate; two passes above 256 rows (64 row chunks,
-    then the 64 chunk sums)."""
-    if nrows <= 256:
-        return math.ceil(nrows / 4) + 3
-    return math.ceil(math.ceil(nrows / 64) / 4) + 3 + 19
 
 
 @pytest.mark.parametrize("accumulate", [0, 1])
