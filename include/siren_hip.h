@@ -576,8 +576,8 @@ int siren_fp32_linear_bwd(const float* x, int64_t rows, int32_t in, int32_t out,
  * G = siren_kan_net.grid_size of 1 .. SIREN_KAN_MAX_GRID in every layer (0 means the default 5, so a
  * zero-initialised struct is a grid-5 net: 8 bases on 12 knots).  A value outside 0 .. 64 is
  * SIREN_ERR_CONFIG before any launch.  Grid 5 runs kernels with its sizes fixed at compile time,
- * every other size the any-grid-size set (kan_general.hip); the siren_kan_grid_* refit below is grid 5
- * only, and siren_kan_regrid_* after it refits from any of these sizes onto any other (or the same).
+ * every other size the any-grid-size set (kan_general.hip); siren_kan_regrid_* below refits from any
+ * of these sizes onto any other (or the same).
  * fp32 throughout.
  * siren_kan_forward / _backward take any last width (out is then [rows][last width]); the fused
  * fit step (siren_kan_train_step) needs last width 1.  Workspace: one caller-owned fp32 buffer of
@@ -641,63 +641,53 @@ int siren_kan_train_step_loss(const siren_kan_net* net, const siren_kan_grads* g
 int siren_kan_step_backward(const siren_kan_net* net, const siren_kan_grads* grads, siren_kan_batch* batch,
                             void* stream);
 
-/* ---- KAN grid update: KANLinear.update_grid of kan.py:168-215 for one layer ----------------
- * The reference refits the layer's curves on new knots by a least-squares fit over the batch.  Per
- * input i that fit is c_new[i] = G_nn[i]^-1 G_no[i] (spline_w[:, i, :] * scaler[:, i])^T with the
- * 8 x 8 Gram matrices G_nn = sum_r b_new(x_ri) b_new(x_ri)^T and G_no = sum_r b_new(x_ri) b_old(x_ri)^T
- * of the fp32 bases on the new and the old knots, summed in fp64 in a fixed order (two calls on the
- * same data agree bit for bit).  The three steps are separate calls; none allocates or synchronises,
- * and none writes a live parameter: the caller copies grid_new and spline_w_new over the layer's
- * buffers once status reads {0, *}.  All pointers are device pointers. */
-/* rows that one pass of the Gram kernel's grid covers (more rows loop); -1: in < 1 */
-int64_t siren_kan_grid_pass_rows(int32_t in);
-/* bytes of the scratch `ws` of siren_kan_grid_gram over `rows` rows and of siren_kan_grid_refit
- * (the larger of the two); -1 on a bad shape */
-int64_t siren_kan_grid_workspace_bytes(int64_t rows, int32_t in);
-/* kan.py:190-212 op for op in fp32: q [6][in] holds, per input, x_sorted at
- * torch.linspace(0, rows - 1, 6, dtype=int64) (any exact selection); grid_new [in][12] */
-int siren_kan_grid_knots(const float* q, int32_t in, double margin, double grid_eps, float* grid_new, void* stream);
-/* gram [in][2][8][8] fp64 (G_nn, then G_no; [new basis][new / old basis]) over x [rows][in];
- * accumulate != 0 adds to gram's contents (micro-batches of one update); x is read once */
-int siren_kan_grid_gram(const float* x, int64_t rows, int32_t in, const float* grid_old, const float* grid_new,
-                        int32_t accumulate, double* gram, void* ws, void* stream);
-/* kan.py:173-177, :215: spline_w_new [out][in][8] = fp32(G_nn^-1 G_no (spline_w * scaler)), by an
- * fp64 Cholesky factorisation per input.  status [2]: the number of rank-deficient inputs (a pivot at
- * or below 2^-40 x the largest diagonal entry of G_nn) and the lowest such index; their rows of
- * spline_w_new are left unwritten */
-int siren_kan_grid_refit(const double* gram, int32_t in, int32_t out, const float* spline_w, const float* scaler,
-                         float* spline_w_new, int32_t* status, void* ws, void* stream);
-
-/* ---- KAN refit onto a grid of another size: KANLinear.regrid (no counterpart in kan.py) -------
- * The siren_kan_grid_* steps with the old and the new basis each at its own size: a layer fitted on
- * g_old intervals (grid_old [in][g_old + 7], spline_w [out][in][g_old + 3]) is refitted by least
- * squares over the rows of x onto g_new intervals: c_new[i] = G_nn[i]^-1 G_no[i] c_old[i] with G_nn
- * (g_new + 3)^2 and G_no (g_new + 3) x (g_old + 3); g_old = g_new = 5 is siren_kan_grid_*'s case (not
- * the same summation order).  Both sizes are 1 .. SIREN_KAN_MAX_GRID, anything else is
- * SIREN_ERR_CONFIG (-1 from the two size queries) before any launch; `in` and `out` as above.  The
- * same rules: no allocation, no synchronisation, no live parameter written, fp64 sums in a fixed
- * order. */
-/* rows that one pass of the Gram kernel's grid covers (more rows loop) */
+/* ---- KAN refit: KANLinear.update_grid of kan.py:168-215 and KANLinear.regrid, for one layer ----
+ * The reference refits the layer's curves on new knots by a least-squares fit over the batch; regrid
+ * (no counterpart in kan.py) does so onto a grid of another size.  A layer fitted on g_old intervals
+ * (grid_old [in][g_old + 7], spline_w [out][in][g_old + 3]) is refitted over the rows of x onto g_new
+ * intervals: per input i, c_new[i] = G_nn[i]^-1 G_no[i] (spline_w[:, i, :] * scaler[:, i])^T with the
+ * Gram matrices G_nn = sum_r b_new(x_ri) b_new(x_ri)^T, (g_new + 3)^2, and G_no = sum_r b_new(x_ri)
+ * b_old(x_ri)^T, (g_new + 3) x (g_old + 3), of the fp32 bases on the new and the old knots, summed in
+ * fp64 in a fixed order (two calls on the same data agree bit for bit).  update_grid is g_old = g_new
+ * with the layer's scaler.  Both sizes are 1 .. SIREN_KAN_MAX_GRID, anything else is SIREN_ERR_CONFIG
+ * (-1 from the two size queries) before any launch; 1 <= in, out <= 4096.  The three steps are
+ * separate calls; none allocates or synchronises, and none writes a live parameter: the caller copies
+ * grid_new and spline_w_new over the layer's buffers once status reads {0, *}.  All pointers are
+ * device pointers. */
+/* rows that one pass of the Gram kernel's grid covers (more rows loop); -1 on a bad shape */
 int64_t siren_kan_regrid_pass_rows(int32_t in, int32_t g_old, int32_t g_new);
 /* bytes of the scratch `ws` of siren_kan_regrid_gram over `rows` rows: per row slice and input only
- * the entries that can be non-zero (G_nn's band, G_no's staircase of 4 x 4 blocks) */
+ * the entries that can be non-zero (G_nn's band, G_no's staircase of 4 x 4 blocks), or at 5 -> 5 the
+ * dense pair of 8 x 8 matrices, which is smaller; -1 on a bad shape */
 int64_t siren_kan_regrid_workspace_bytes(int64_t rows, int32_t in, int32_t g_old, int32_t g_new);
 /* kan.py:183-212 op for op in fp32 with g_new for its grid_size: q [g_new + 1][in] holds, per input,
- * x_sorted at torch.linspace(0, rows - 1, g_new + 1, dtype=int64); grid_new [in][g_new + 7] */
+ * x_sorted at torch.linspace(0, rows - 1, g_new + 1, dtype=int64) (any exact selection); grid_new
+ * [in][g_new + 7] */
 int siren_kan_regrid_knots(const float* q, int32_t in, int32_t g_new, double margin, double grid_eps, float* grid_new,
                            void* stream);
 /* gram [in]{G_nn [g_new+3][g_new+3], G_no [g_new+3][g_old+3]} fp64, dense (G_nn symmetric, exact zeros
- * off its band of half-width 3) over x [rows][in]; accumulate != 0 adds to gram's contents; x is
- * read once */
+ * off its band of half-width 3) over x [rows][in]; accumulate != 0 adds to gram's contents
+ * (micro-batches of one refit); x is read once */
 int siren_kan_regrid_gram(const float* x, int64_t rows, int32_t in, int32_t g_old, int32_t g_new,
                           const float* grid_old, const float* grid_new, int32_t accumulate, double* gram, void* ws,
                           void* stream);
-/* spline_w_new [out][in][g_new+3] = fp32(G_nn^-1 G_no (spline_w * scaler)) by a banded fp64 Cholesky
- * factorisation per input; scaler NULL: all ones (the unscaled coefficients).  status [2] and the
- * rank rule as siren_kan_grid_refit; needs no scratch */
+/* kan.py:173-177, :215: spline_w_new [out][in][g_new+3] = fp32(G_nn^-1 G_no (spline_w * scaler)) by a
+ * banded fp64 Cholesky factorisation per input; scaler NULL: all ones (the unscaled coefficients).
+ * status [2]: the number of rank-deficient inputs (a pivot at or below 2^-40 x the largest diagonal
+ * entry of G_nn) and the lowest such index; their rows of spline_w_new are left unwritten.  Needs no
+ * scratch */
 int siren_kan_regrid_refit(const double* gram, int32_t in, int32_t out, int32_t g_old, int32_t g_new,
                            const float* spline_w, const float* scaler, float* spline_w_new, int32_t* status,
                            void* stream);
+/* The (5, 5) case of siren_kan_regrid_* (same kernels, same bits), kept for existing callers: scaler
+ * and ws must not be NULL, and siren_kan_grid_refit does not use ws. */
+int64_t siren_kan_grid_pass_rows(int32_t in);
+int64_t siren_kan_grid_workspace_bytes(int64_t rows, int32_t in);
+int siren_kan_grid_knots(const float* q, int32_t in, double margin, double grid_eps, float* grid_new, void* stream);
+int siren_kan_grid_gram(const float* x, int64_t rows, int32_t in, const float* grid_old, const float* grid_new,
+                        int32_t accumulate, double* gram, void* ws, void* stream);
+int siren_kan_grid_refit(const double* gram, int32_t in, int32_t out, const float* spline_w, const float* scaler,
+                         float* spline_w_new, int32_t* status, void* ws, void* stream);
 
 /* ---- per-launch HIP-event profiling of the fused path (bench.py) --------------------
  * siren_profile_enable(n) creates 2n hipEvents; while enabled every launch made by

@@ -234,13 +234,14 @@ _SIGS = {
                                                  ctypes.POINTER(SirenKanBatch), _i32, _p]),
     "siren_kan_step_backward": (ctypes.c_int, [ctypes.POINTER(SirenKanNet), ctypes.POINTER(SirenKanGrads),
                                                ctypes.POINTER(SirenKanBatch), _p]),
-    # KANLinear.update_grid (kan.py:168-215): knots, Gram sums, refit
+    # the (5, 5) case of siren_kan_regrid_* under its earlier names, kept for existing callers
     "siren_kan_grid_pass_rows": (_i64, [_i32]),
     "siren_kan_grid_workspace_bytes": (_i64, [_i64, _i32]),
     "siren_kan_grid_knots": (ctypes.c_int, [_p, _i32, ctypes.c_double, ctypes.c_double, _p, _p]),
     "siren_kan_grid_gram": (ctypes.c_int, [_p, _i64, _i32, _p, _p, _i32, _p, _p, _p]),
     "siren_kan_grid_refit": (ctypes.c_int, [_p, _i32, _i32, _p, _p, _p, _p, _p, _p]),
-    # KANLinear.regrid: the same three steps from a grid of g_old intervals onto one of g_new
+    # KANLinear.update_grid (kan.py:168-215) and .regrid: knots, Gram sums, refit from a grid of g_old
+    # intervals onto one of g_new
     "siren_kan_regrid_pass_rows": (_i64, [_i32, _i32, _i32]),
     "siren_kan_regrid_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "siren_kan_regrid_knots": (ctypes.c_int, [_p, _i32, _i32, ctypes.c_double, ctypes.c_double, _p, _p]),

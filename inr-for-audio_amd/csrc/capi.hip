@@ -1567,43 +1567,31 @@ int siren_kan_backward(const siren_kan_net* net, const siren_kan_grads* gr, sire
   return SIREN_OK;
 }
 
-// ---- KAN grid update (kan.py:168-215) ----
+// ---- KAN refit (KANLinear.update_grid, kan.py:168-215, and KANLinear.regrid) ----
 static bool kan_grid_in_ok(int32_t in) { return in >= 1 && in <= 4096; }
 
-int64_t siren_kan_grid_pass_rows(int32_t in) { return kan_grid_in_ok(in) ? kan_grid_pass_rows(in) : -1; }
+// the (5, 5) case, kept for existing callers
+int64_t siren_kan_grid_pass_rows(int32_t in) { return siren_kan_regrid_pass_rows(in, 5, 5); }
 
 int64_t siren_kan_grid_workspace_bytes(int64_t rows, int32_t in) {
-  if (rows < 1 || !kan_grid_in_ok(in)) return -1;
-  const int64_t part = kan_grid_part_doubles(rows, in), m = (int64_t)in * KAN_NB * KAN_NB;
-  return (int64_t)sizeof(double) * (part > m ? part : m);
+  return siren_kan_regrid_workspace_bytes(rows, in, 5, 5);
 }
 
 int siren_kan_grid_knots(const float* q, int32_t in, double margin, double grid_eps, float* grid_new, void* stream) {
-  if (!q || !grid_new) return SIREN_ERR_NULL;
-  if (!kan_grid_in_ok(in)) return SIREN_ERR_SHAPE;
-  // the reference's host scalars, rounded to fp32 where torch rounds them (kan.py:190, :197, :200)
-  SIREN_TRY(kan_grid_knots(q, in, (float)margin, (float)(2 * margin), (float)grid_eps, (float)(1 - grid_eps), grid_new,
-                           S(stream)));
-  return SIREN_OK;
+  return siren_kan_regrid_knots(q, in, 5, margin, grid_eps, grid_new, stream);
 }
 
 int siren_kan_grid_gram(const float* x, int64_t rows, int32_t in, const float* grid_old, const float* grid_new,
                         int32_t accumulate, double* gram, void* ws, void* stream) {
-  if (!x || !grid_old || !grid_new || !gram || !ws) return SIREN_ERR_NULL;
-  if (rows < 1 || !kan_grid_in_ok(in)) return SIREN_ERR_SHAPE;
-  SIREN_TRY(kan_grid_gram(x, grid_old, grid_new, rows, in, accumulate != 0, (double*)ws, gram, S(stream)));
-  return SIREN_OK;
+  return siren_kan_regrid_gram(x, rows, in, 5, 5, grid_old, grid_new, accumulate, gram, ws, stream);
 }
 
 int siren_kan_grid_refit(const double* gram, int32_t in, int32_t out, const float* spline_w, const float* scaler,
                          float* spline_w_new, int32_t* status, void* ws, void* stream) {
-  if (!gram || !spline_w || !scaler || !spline_w_new || !status || !ws) return SIREN_ERR_NULL;
-  if (!kan_grid_in_ok(in) || out < 1 || out > 4096) return SIREN_ERR_SHAPE;
-  SIREN_TRY(kan_grid_refit(gram, in, out, spline_w, scaler, (double*)ws, spline_w_new, status, S(stream)));
-  return SIREN_OK;
+  if (!scaler || !ws) return SIREN_ERR_NULL;  // ws is not used
+  return siren_kan_regrid_refit(gram, in, out, 5, 5, spline_w, scaler, spline_w_new, status, stream);
 }
 
-// ---- KAN refit onto a grid of another size (KANLinear.regrid) ----
 static bool kan_regrid_g_ok(int32_t g_old, int32_t g_new) {
   return g_old >= 1 && g_old <= SIREN_KAN_MAX_GRID && g_new >= 1 && g_new <= SIREN_KAN_MAX_GRID;
 }
@@ -1622,6 +1610,7 @@ int siren_kan_regrid_knots(const float* q, int32_t in, int32_t g_new, double mar
   if (g_new < 1 || g_new > SIREN_KAN_MAX_GRID) return SIREN_ERR_CONFIG;
   if (!q || !grid_new) return SIREN_ERR_NULL;
   if (!kan_grid_in_ok(in)) return SIREN_ERR_SHAPE;
+  // the reference's host scalars, rounded to fp32 where torch rounds them (kan.py:190, :197, :200)
   SIREN_TRY(kan_regrid_knots(q, in, g_new, (float)margin, (float)(2 * margin), (float)grid_eps, (float)(1 - grid_eps),
                              grid_new, S(stream)));
   return SIREN_OK;

@@ -13,9 +13,9 @@
 //   kan_head_fwd / kan_head_train / kan_head_bwd  the last layer (out = 1): inference; forward,
 //                  MSE or L1 gradient and backward in one pass; the backward alone for a given
 //                  g (one row evaluation for all: kan_head_row)
-//   kan_grid_knots / kan_grid_gram / kan_grid_refit  update_grid (kan.py:168-215), at the end of the file
 // These kernels are grid_size 5's (KAN_NB = 8 at compile time).  Every other grid size runs their twins in
-// kan_general.hip, which takes its tool kit from this file ("shared with kan_general.hip" below).
+// kan_general.hip, which takes its tool kit from this file ("shared with kan_general.hip" below) and
+// holds the refit of update_grid and regrid (kan_regrid_*) for every size, 5 included.
 // The three backward kernels are put together from one set of tile helpers: kf_fill_a (A tile;
 // kan_bwd_fused keeps its own, with the derivatives in registers),
 // kf_g_load / kf_g_store / kf_g_scalar (G tile), kf_load_wt (W^T chunk), kf_da_to_gin (dA -> Gin),
@@ -1270,245 +1270,6 @@ hipError_t kan_gemm(const float* A, int64_t sam, int64_t sak, const float* B, in
   hipLaunchKernelGGL(kan_gemm_kernel, grid, dim3(256), 0, s, A, sam, sak, B, sbk, sbn, z > 1 ? C : out, M, N, K,
                      kchunk);
   if (z > 1) return slab_reduce(C, z, (int64_t)M * N, out, s);
-  return hipGetLastError();
-}
-
-// ---- grid update (kan.py:168-215 update_grid) -------------------------------------------------
-// The reference refits every curve on the new knots by least squares over the batch:
-// min || A_new c - B ||, B[r][o] = sum_c A_old[r][c] coeff_old[o][i][c].  A_new^T B =
-// (A_new^T A_old) coeff_old, so per input i
-//   c_new[i] (8 x out) = G_nn[i]^-1 G_no[i] coeff_old[i],
-//   G_nn[i] = sum_r b_new(x_ri) b_new(x_ri)^T,  G_no[i] = sum_r b_new(x_ri) b_old(x_ri)^T
-// two 8 x 8 matrices per input and nothing of size rows x out (the reference's (batch, in, out)
-// intermediate is 115 GB at 441 000 x 256 x 256).  The bases are the forward's fp32 values
-// (kan_bases_window on IEEE quotients); their products are exact in fp64 and are summed in fp64 in
-// a fixed order (no floating-point atomics), so two runs agree bit for bit.
-//   kan_grid_knots  the new knots from six order statistics of each input (kan.py:190-212)
-//   kan_grid_gram   G_nn, G_no: row slices into fp64 partials, then a fixed-order sum
-//   kan_grid_refit  Cholesky of G_nn, M = G_nn^-1 G_no, spline_w_new = fp32(M (spline_w * scaler))
-constexpr int KGU_ROWS = 8;                       // rows a wave loads before it evaluates them
-constexpr int KGU_E = 2 * KAN_NB * KAN_NB;        // fp64 entries per input: G_nn then G_no, [8][8] each
-constexpr int KGU_MAX_SLICES = 256, KGU_MIN_SLICES = 8, KGU_BLOCKS = 1024;
-
-// kan.py:190-212 op for op in fp32 (IEEE division; each product rounded before the sum):
-//   step = (x_last - x_first + 2 margin) / 5
-//   knot_k = eps ((k step + x_first) - margin) + (1 - eps) q_k,  k = 0..5
-// extended by three steps on either side.  q[k][i]: the k-th of the six order statistics of input i.
-__global__ __launch_bounds__(256) void kan_grid_knots_kernel(const float* __restrict__ q, int in, float margin,
-                                                             float margin2, float eps, float one_eps,
-                                                             float* __restrict__ grid) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= in) return;
-  const float x0 = q[i], x5 = q[5 * (int64_t)in + i];
-  const float step = ((x5 - x0) + margin2) / 5.0f;
-  float g[6];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const float gu = ((float)k * step + x0) - margin;
-    g[k] = eps * gu + one_eps * q[k * (int64_t)in + i];
-  }
-  float* out = grid + (int64_t)i * KAN_NG;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) out[k] = g[0] - step * (float)(3 - k);
-#pragma unroll
-  for (int k = 0; k < 6; ++k) out[3 + k] = g[k];
-#pragma unroll
-  for (int k = 1; k <= 3; ++k) out[8 + k] = g[5] + step * (float)k;
-}
-
-// One wave per block; lane = input i0 + lane (X rows are read along the lanes: coalesced, each
-// element once).  The lane's 128 fp64 sums live in LDS as acc[e][lane] (the entries a row touches
-// depend on its spans, so registers will not do; lane-consecutive doubles: no bank conflicts
-// whatever the spans).  Block (cg, z) takes the 8-row tiles z, z + Z, ... of its 64 inputs and
-// writes part[z][e][i]; G_nn is summed on its upper triangle and mirrored on the way out, and the
-// entries no row touches (|c - d| > 3) stay exact zeros.
-__global__ __launch_bounds__(64) void kan_grid_gram_kernel(const float* __restrict__ X,
-                                                           const float* __restrict__ grid_old,
-                                                           const float* __restrict__ grid_new, int64_t N, int in,
-                                                           double* __restrict__ part) {
-  __shared__ double acc[KGU_E][64];
-  __shared__ float gk[2][64][KF_GST];
-  __shared__ float inv[2][64][KF_VST];
-  const int lane = threadIdx.x, i0 = blockIdx.x * 64;
-  const int ic = in - i0 < 64 ? in - i0 : 64;
-  kf_fill_knots(gk[0], grid_old, i0, ic);
-  kf_fill_knots(gk[1], grid_new, i0, ic);
-  kf_fill_inv(inv[0], grid_old, i0, ic);
-  kf_fill_inv(inv[1], grid_new, i0, ic);
-#pragma unroll 8
-  for (int e = 0; e < KGU_E; ++e) acc[e][lane] = 0.0;
-  __syncthreads();
-  const bool on = lane < ic;
-  const int64_t ntile = (N + KGU_ROWS - 1) / KGU_ROWS;
-  for (int64_t t = blockIdx.y; t < ntile; t += gridDim.y) {
-    float x[KGU_ROWS];
-#pragma unroll
-    for (int r = 0; r < KGU_ROWS; ++r) {
-      const int64_t n = t * KGU_ROWS + r;
-      x[r] = (on && n < N) ? X[n * in + i0 + lane] : 0.f;
-    }
-#pragma unroll
-    for (int r = 0; r < KGU_ROWS; ++r) {
-      if (!on || t * KGU_ROWS + r >= N) continue;
-      float wn[4], wo[4], unused[4];
-      const int sn = kan_bases_window<false, false, false>(x[r], gk[1][lane], wn, unused, inv[1][lane]);
-      if (sn < 0) continue;
-      const int so = kan_bases_window<false, false, false>(x[r], gk[0][lane], wo, unused, inv[0][lane]);
-#pragma unroll
-      for (int p = 0; p < 4; ++p) {
-        const int c = sn - 3 + p;
-        if (c < 0 || c >= KAN_NB) continue;
-        const double bp = (double)wn[p];
-#pragma unroll
-        for (int k = p; k < 4; ++k) {
-          const int d = sn - 3 + k;
-          if (d < KAN_NB) acc[c * KAN_NB + d][lane] += bp * (double)wn[k];
-        }
-        if (so >= 0) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const int d = so - 3 + k;
-            if (d >= 0 && d < KAN_NB) acc[KAN_NB * KAN_NB + c * KAN_NB + d][lane] += bp * (double)wo[k];
-          }
-        }
-      }
-    }
-  }
-  if (!on) return;
-  double* out = part + (int64_t)blockIdx.y * KGU_E * in + i0 + lane;
-  for (int c = 0; c < KAN_NB; ++c)
-    for (int d = 0; d < KAN_NB; ++d) {
-      out[(int64_t)(c * KAN_NB + d) * in] = c <= d ? acc[c * KAN_NB + d][lane] : acc[d * KAN_NB + c][lane];
-      out[(int64_t)(KAN_NB * KAN_NB + c * KAN_NB + d) * in] = acc[KAN_NB * KAN_NB + c * KAN_NB + d][lane];
-    }
-}
-
-// gram[i][e] = (accumulate ? gram[i][e] : 0) + part[0][e][i] + part[1][e][i] + ... in slice order
-__global__ __launch_bounds__(256) void kan_grid_gram_reduce_kernel(const double* __restrict__ part, int slices, int in,
-                                                                   int accumulate, double* __restrict__ gram) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (int64_t)KGU_E * in) return;
-  const int e = (int)(idx / in), i = (int)(idx - (int64_t)e * in);
-  double v = accumulate ? gram[(int64_t)i * KGU_E + e] : 0.0;
-  for (int z = 0; z < slices; ++z) v += part[(int64_t)z * KGU_E * in + idx];
-  gram[(int64_t)i * KGU_E + e] = v;
-}
-
-// Per input: G_nn = L L^T (fp64), M = G_nn^-1 G_no as M[i][d][c].  A pivot at or below 2^-40 x the
-// largest diagonal entry (or a NaN) marks the input rank deficient: status[0] counts such inputs,
-// status[1] keeps the lowest index, and M[i] is NaN so that kan_grid_apply writes nothing for it.
-__global__ __launch_bounds__(64) void kan_grid_solve_kernel(const double* __restrict__ gram, int in,
-                                                            double* __restrict__ M, int* __restrict__ status) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= in) return;
-  const double* G = gram + (int64_t)i * KGU_E;
-  double* m = M + (int64_t)i * KAN_NB * KAN_NB;
-  double L[KAN_NB][KAN_NB];
-  double dmax = 0.0;
-  for (int c = 0; c < KAN_NB; ++c) dmax = G[c * KAN_NB + c] > dmax ? G[c * KAN_NB + c] : dmax;
-  const double thr = dmax * 0x1p-40;
-  bool ok = dmax > 0.0;
-  for (int j = 0; j < KAN_NB && ok; ++j) {
-    double p = G[j * KAN_NB + j];
-    for (int k = 0; k < j; ++k) p -= L[j][k] * L[j][k];
-    if (!(p > thr)) {
-      ok = false;
-      break;
-    }
-    const double l = sqrt(p);
-    L[j][j] = l;
-    for (int r = j + 1; r < KAN_NB; ++r) {
-      double v = G[r * KAN_NB + j];
-      for (int k = 0; k < j; ++k) v -= L[r][k] * L[j][k];
-      L[r][j] = v / l;
-    }
-  }
-  if (!ok) {
-    atomicAdd(&status[0], 1);
-    atomicMin(&status[1], i);
-    for (int e = 0; e < KAN_NB * KAN_NB; ++e) m[e] = __builtin_nan("");
-    return;
-  }
-  for (int c = 0; c < KAN_NB; ++c) {  // column c of G_no: L y = b, L^T x = y
-    double y[KAN_NB];
-    for (int r = 0; r < KAN_NB; ++r) {
-      double v = G[KAN_NB * KAN_NB + r * KAN_NB + c];
-      for (int k = 0; k < r; ++k) v -= L[r][k] * y[k];
-      y[r] = v / L[r][r];
-    }
-    for (int r = KAN_NB - 1; r >= 0; --r) {
-      double v = y[r];
-      for (int k = r + 1; k < KAN_NB; ++k) v -= L[k][r] * y[k];
-      y[r] = v / L[r][r];
-    }
-    for (int r = 0; r < KAN_NB; ++r) m[r * KAN_NB + c] = y[r];
-  }
-}
-
-// spline_w_new[o][i][:] = fp32(M[i] (spline_w[o][i][:] * scaler[o][i])): the refit targets the scaled
-// curves and the result is stored undivided (kan.py:175, :215)
-__global__ __launch_bounds__(256) void kan_grid_apply_kernel(const double* __restrict__ M,
-                                                             const float* __restrict__ spline_w,
-                                                             const float* __restrict__ scaler, int out, int in,
-                                                             float* __restrict__ spline_w_new) {
-  const int64_t total = (int64_t)out * in, stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += stride) {
-    const double* m = M + (idx % in) * KAN_NB * KAN_NB;
-    if (m[0] != m[0]) continue;
-    const float s = scaler[idx];
-    double v[KAN_NB];
-#pragma unroll
-    for (int c = 0; c < KAN_NB; ++c) v[c] = (double)(spline_w[idx * KAN_NB + c] * s);
-#pragma unroll
-    for (int d = 0; d < KAN_NB; ++d) {
-      double a = 0.0;
-#pragma unroll
-      for (int c = 0; c < KAN_NB; ++c) a += m[d * KAN_NB + c] * v[c];
-      spline_w_new[idx * KAN_NB + d] = (float)a;
-    }
-  }
-}
-
-hipError_t kan_grid_knots(const float* q, int in, float margin, float margin2, float eps, float one_eps, float* grid,
-                          hipStream_t s) {
-  if (in <= 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kan_grid_knots_kernel, dim3((in + 255) / 256), dim3(256), 0, s, q, in, margin, margin2, eps,
-                     one_eps, grid);
-  return hipGetLastError();
-}
-
-// row slices of the Gram kernel: about KGU_BLOCKS one-wave blocks over the 64-input column groups
-int kan_grid_slices(int64_t N, int in) {
-  const int ncg = (in + 63) / 64;
-  int z = KGU_BLOCKS / ncg;
-  z = z < KGU_MIN_SLICES ? KGU_MIN_SLICES : (z > KGU_MAX_SLICES ? KGU_MAX_SLICES : z);
-  const int64_t ntile = (N + KGU_ROWS - 1) / KGU_ROWS;
-  return ntile < z ? (int)(ntile < 1 ? 1 : ntile) : z;
-}
-int64_t kan_grid_pass_rows(int in) { return (int64_t)KGU_ROWS * kan_grid_slices(INT64_MAX / 2, in); }
-int64_t kan_grid_part_doubles(int64_t N, int in) { return (int64_t)kan_grid_slices(N, in) * KGU_E * in; }
-
-hipError_t kan_grid_gram(const float* X, const float* grid_old, const float* grid_new, int64_t N, int in,
-                         int accumulate, double* part, double* gram, hipStream_t s) {
-  if (N <= 0 || in <= 0) return hipErrorInvalidValue;
-  const int z = kan_grid_slices(N, in);
-  hipLaunchKernelGGL(kan_grid_gram_kernel, dim3((in + 63) / 64, z), dim3(64), 0, s, X, grid_old, grid_new, N, in,
-                     part);
-  hipLaunchKernelGGL(kan_grid_gram_reduce_kernel, dim3((unsigned)(((int64_t)KGU_E * in + 255) / 256)), dim3(256), 0, s,
-                     part, z, in, accumulate, gram);
-  return hipGetLastError();
-}
-
-hipError_t kan_grid_refit(const double* gram, int in, int out, const float* spline_w, const float* scaler, double* M,
-                          float* spline_w_new, int* status, hipStream_t s) {
-  if (in <= 0 || out <= 0) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(status, 0, sizeof(int), s);
-  if (e != hipSuccess) return e;
-  e = hipMemsetAsync(status + 1, 0x7f, sizeof(int), s);  // above every index
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(kan_grid_solve_kernel, dim3((in + 63) / 64), dim3(64), 0, s, gram, in, M, status);
-  hipLaunchKernelGGL(kan_grid_apply_kernel, dim3(ew_grid((int64_t)out * in)), dim3(256), 0, s, M, spline_w, scaler,
-                     out, in, spline_w_new);
   return hipGetLastError();
 }
 

@@ -667,23 +667,33 @@ hipError_t kang_param_grads(const float* dW, const float* spline_w, const float*
   return hipGetLastError();
 }
 
-// ---- refit onto a grid of another size (KANLinear.regrid) ---------------------------------------
-// kan.hip's grid update with the old and the new basis each at its own size: per input i
+// ---- the refit (KANLinear.update_grid, kan.py:168-215, and KANLinear.regrid) ----------------------
+// The reference refits every curve on the new knots by least squares over the batch:
+// min || A_new c - B ||, B[r][o] = sum_c A_old[r][c] coeff_old[o][i][c].  A_new^T B =
+// (A_new^T A_old) coeff_old, so per input i, with the old and the new basis each at its own size,
 //   c_new[i] = G_nn[i]^-1 G_no[i] c_old[i],  G_nn (Gn+3) x (Gn+3),  G_no (Gn+3) x (Go+3)
-// (Go = Gn = 5 is kan_grid_*'s case).  A row touches 10 entries of G_nn's upper band and one 4 x 4
+//   G_nn[i] = sum_r b_new(x_ri) b_new(x_ri)^T,  G_no[i] = sum_r b_new(x_ri) b_old(x_ri)^T
+// and nothing of size rows x out (the reference's (batch, in, out) intermediate is 115 GB at
+// 441 000 x 256 x 256).  The bases are the forward's fp32 values on IEEE quotients; their products
+// are exact in fp64 and are summed in fp64 in a fixed order (no floating-point atomics), so two runs
+// agree bit for bit.  update_grid is Go = Gn = grid_size with the scaler passed in.  A row touches
+// 10 entries of G_nn's upper band and one 4 x 4
 // block of G_no, the block of its new span s and old span r.  G_no is a staircase: two pairs of
 // overlapping half-open spans never share s + r.  (Take (s, r) and (s', r') with s < s' and r > r':
 // an x in the first pair and a y in the second give y >= gn[s'] >= gn[s+1] > x >= go[r] >= go[r'+1]
 // > y.)  So slot t = s + r addresses a compact accumulator without collisions, of
 //   E = 4 (Gn+3) + 16 (Gn + Go + 11) doubles per input: G_nn's band [c][d - c], then [t][p][k]
 // (2492 at 64 -> 64, where the dense pair of matrices has 8978), and the per-slice partials have
-// that size too.
+// that size too.  At 5 -> 5 (update_grid's case) the dense pair is the smaller one, 128 doubles
+// against 368, and 64 inputs fit a block where the compact accumulator lets 49 in: that pair alone
+// runs kan_regrid_gram_dense5_kernel (kr_gram_plan).
 //   kan_regrid_knots  the new knots from Gn + 1 order statistics of each input
-//   kan_regrid_gram   row slices into compact fp64 partials, then a fixed-order sum into dense Grams
+//   kan_regrid_gram   row slices into fp64 partials, then a fixed-order sum into dense Grams
 //   kan_regrid_refit  banded Cholesky of G_nn, M = G_nn^-1 G_no, spline_w_new = fp32(M c_old)
 constexpr int KR_ROWS = 8;                                             // rows a lane loads before it evaluates them
 constexpr int KR_MAX_SLICES = 256, KR_MIN_SLICES = 8, KR_BLOCKS = 1024;
 constexpr size_t kKrLdsMax = 160 * 1024;
+constexpr int KR_DENSE5_E = 2 * KAN_NB * KAN_NB;  // the 5 -> 5 Gram's fp64 entries per input: G_nn then G_no, [8][8] each
 
 struct KrDims {
   KgDims o, n;  // the old and the new grid
@@ -702,7 +712,7 @@ __host__ __device__ constexpr int kr_ic(const KrDims& d) {
 }
 static_assert(kr_ic(kr_dims(KG_MAX_GRID, KG_MAX_GRID)) >= 1, "one input's accumulator outgrows the LDS");
 
-// kan.py:183-212 op for op in fp32 as kan_grid_knots_kernel, with Gn for 5:
+// kan.py:183-212 op for op in fp32 (IEEE division; each product rounded before the sum), Gn for its 5:
 //   step = (x_last - x_first + 2 margin) / Gn
 //   knot_k = eps ((k step + x_first) - margin) + (1 - eps) q_k,  k = 0..Gn
 // extended by three steps on either side.  q[k][i]: the k-th of the Gn + 1 order statistics of input i.
@@ -728,7 +738,7 @@ __global__ __launch_bounds__(256) void kan_regrid_knots_kernel(const float* __re
   for (int k = 1; k <= 3; ++k) out[Gn + 3 + k] = gl + step * (float)k;
 }
 
-// kan_grid_gram_kernel with run-time sizes: one wave per block, lane = input i0 + lane of the
+// The compact Gram at run-time sizes: one wave per block, lane = input i0 + lane of the
 // block's ic = kr_ic inputs (X rows are read along the lanes, each element once).  Dynamic LDS:
 //   acc [E][ic] doubles (lane-consecutive: no bank conflicts whatever the spans), then
 //   gk_o [ic][gst_o]  gk_n [ic][gst_n]  inv_o [ic][vst_o]  inv_n [ic][vst_n] floats.
@@ -836,14 +846,97 @@ __global__ __launch_bounds__(256) void kan_regrid_gram_reduce_kernel(const doubl
   *dst = v;
 }
 
+// The dense case, Go = Gn = 5 (kan.hip's compile-time tables).  One wave per block; lane = input
+// i0 + lane (X rows are read along the lanes: coalesced, each element once).
+// The lane's 128 fp64 sums live in LDS as acc[e][lane] (the entries a row touches
+// depend on its spans, so registers will not do; lane-consecutive doubles: no bank conflicts
+// whatever the spans).  Block (cg, z) takes the 8-row tiles z, z + Z, ... of its 64 inputs and
+// writes part[z][e][i]; G_nn is summed on its upper triangle and mirrored on the way out, and the
+// entries no row touches (|c - d| > 3) stay exact zeros.
+__global__ __launch_bounds__(64) void kan_regrid_gram_dense5_kernel(const float* __restrict__ X,
+                                                                    const float* __restrict__ grid_old,
+                                                                    const float* __restrict__ grid_new, int64_t N,
+                                                                    int in, double* __restrict__ part) {
+  __shared__ double acc[KR_DENSE5_E][64];
+  __shared__ float gk[2][64][KF_GST];
+  __shared__ float inv[2][64][KF_VST];
+  const int lane = threadIdx.x, i0 = blockIdx.x * 64;
+  const int ic = in - i0 < 64 ? in - i0 : 64;
+  kf_fill_knots(gk[0], grid_old, i0, ic);
+  kf_fill_knots(gk[1], grid_new, i0, ic);
+  kf_fill_inv(inv[0], grid_old, i0, ic);
+  kf_fill_inv(inv[1], grid_new, i0, ic);
+#pragma unroll 8
+  for (int e = 0; e < KR_DENSE5_E; ++e) acc[e][lane] = 0.0;
+  __syncthreads();
+  const bool on = lane < ic;
+  const int64_t ntile = (N + KR_ROWS - 1) / KR_ROWS;
+  for (int64_t t = blockIdx.y; t < ntile; t += gridDim.y) {
+    float x[KR_ROWS];
+#pragma unroll
+    for (int r = 0; r < KR_ROWS; ++r) {
+      const int64_t n = t * KR_ROWS + r;
+      x[r] = (on && n < N) ? X[n * in + i0 + lane] : 0.f;
+    }
+#pragma unroll
+    for (int r = 0; r < KR_ROWS; ++r) {
+      if (!on || t * KR_ROWS + r >= N) continue;
+      float wn[4], wo[4], unused[4];
+      const int sn = kan_bases_window<false, false, false>(x[r], gk[1][lane], wn, unused, inv[1][lane]);
+      if (sn < 0) continue;
+      const int so = kan_bases_window<false, false, false>(x[r], gk[0][lane], wo, unused, inv[0][lane]);
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const int c = sn - 3 + p;
+        if (c < 0 || c >= KAN_NB) continue;
+        const double bp = (double)wn[p];
+#pragma unroll
+        for (int k = p; k < 4; ++k) {
+          const int d = sn - 3 + k;
+          if (d < KAN_NB) acc[c * KAN_NB + d][lane] += bp * (double)wn[k];
+        }
+        if (so >= 0) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            const int d = so - 3 + k;
+            if (d >= 0 && d < KAN_NB) acc[KAN_NB * KAN_NB + c * KAN_NB + d][lane] += bp * (double)wo[k];
+          }
+        }
+      }
+    }
+  }
+  if (!on) return;
+  double* out = part + (int64_t)blockIdx.y * KR_DENSE5_E * in + i0 + lane;
+  for (int c = 0; c < KAN_NB; ++c)
+    for (int d = 0; d < KAN_NB; ++d) {
+      out[(int64_t)(c * KAN_NB + d) * in] = c <= d ? acc[c * KAN_NB + d][lane] : acc[d * KAN_NB + c][lane];
+      out[(int64_t)(KAN_NB * KAN_NB + c * KAN_NB + d) * in] = acc[KAN_NB * KAN_NB + c * KAN_NB + d][lane];
+    }
+}
+
+// gram[i][e] = (accumulate ? gram[i][e] : 0) + part[0][e][i] + part[1][e][i] + ... in slice order
+__global__ __launch_bounds__(256) void kan_regrid_gram_dense5_reduce_kernel(const double* __restrict__ part, int slices,
+                                                                            int in, int accumulate,
+                                                                            double* __restrict__ gram) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)KR_DENSE5_E * in) return;
+  const int e = (int)(idx / in), i = (int)(idx - (int64_t)e * in);
+  double v = accumulate ? gram[(int64_t)i * KR_DENSE5_E + e] : 0.0;
+  for (int z = 0; z < slices; ++z) v += part[(int64_t)z * KR_DENSE5_E * in + idx];
+  gram[(int64_t)i * KR_DENSE5_E + e] = v;
+}
+
 // One block per input.  Dynamic LDS: Lb [NBn + 3][4] doubles, the banded Cholesky factor
 // Lb[r][r - j] = L[r][j] (j = r-3 .. r; entries off the matrix and three rows past it are zeros, so
 // the substitutions need no edge cases), Ab [NBn][4], G_nn's lower band in the same layout, then
 // M [NBn][NBo], G_no solved in place.
-//   thread 0      G_nn = L L^T with kan_grid_solve_kernel's pivot rule and order of operations
+//   thread 0      G_nn = L L^T in fp64, in the dense factorisation's order less its exact-zero terms
 //   thread c      column c of G_no: L y = b, L^T x = y, three values of y (x) back in registers
-//   thread o, ..  spline_w_new[o][i][:] = fp32(M (spline_w[o][i][:] * scaler[o][i]))
-// A rank-deficient input counts in status[0], lowers status[1] to its index and writes nothing.
+//   thread o, ..  spline_w_new[o][i][:] = fp32(M (spline_w[o][i][:] * scaler[o][i])); with a scaler
+//                 (update_grid) the refit targets the scaled curves and the result is stored
+//                 undivided (kan.py:175, :215)
+// A pivot at or below 2^-40 x the largest diagonal entry (or a NaN) marks the input rank deficient:
+// it counts in status[0], lowers status[1] to its index and writes nothing.
 __global__ __launch_bounds__(256) void kan_regrid_refit_kernel(const double* __restrict__ gram, int in, int out, int Go,
                                                                int Gn, const float* __restrict__ spline_w,
                                                                const float* __restrict__ scaler,
@@ -940,12 +1033,22 @@ hipError_t kan_regrid_knots(const float* q, int in, int Gn, float margin, float 
   return hipGetLastError();
 }
 
-// inputs per block: kr_ic, and no more than the layer has (a narrow layer asks for less LDS)
-static int kr_block_inputs(int in, const KrDims& d) { return in < kr_ic(d) ? in : kr_ic(d); }
+// Which Gram kernel a pair of sizes runs, and what follows from it: the inputs of a block and the
+// doubles per slice and input.  Compact: kr_ic inputs, and no more than the layer has (a narrow
+// layer asks for less LDS).
+struct KrGramPlan {
+  bool dense5;
+  int icb, e;
+};
+static KrGramPlan kr_gram_plan(int in, int Go, int Gn) {
+  if (Go == 5 && Gn == 5) return KrGramPlan{true, 64, KR_DENSE5_E};
+  const KrDims d = kr_dims(Go, Gn);
+  return KrGramPlan{false, in < kr_ic(d) ? in : kr_ic(d), d.e};
+}
 
 // row slices of the Gram kernel: about KR_BLOCKS one-wave blocks over the column groups
 int kan_regrid_slices(int64_t N, int in, int Go, int Gn) {
-  const int icb = kr_block_inputs(in, kr_dims(Go, Gn)), ncg = (in + icb - 1) / icb;
+  const int icb = kr_gram_plan(in, Go, Gn).icb, ncg = (in + icb - 1) / icb;
   int z = KR_BLOCKS / ncg;
   z = z < KR_MIN_SLICES ? KR_MIN_SLICES : (z > KR_MAX_SLICES ? KR_MAX_SLICES : z);
   const int64_t ntile = (N + KR_ROWS - 1) / KR_ROWS;
@@ -955,14 +1058,22 @@ int64_t kan_regrid_pass_rows(int in, int Go, int Gn) {
   return (int64_t)KR_ROWS * kan_regrid_slices(INT64_MAX / 2, in, Go, Gn);
 }
 int64_t kan_regrid_part_doubles(int64_t N, int in, int Go, int Gn) {
-  return (int64_t)kan_regrid_slices(N, in, Go, Gn) * kr_dims(Go, Gn).e * in;
+  return (int64_t)kan_regrid_slices(N, in, Go, Gn) * kr_gram_plan(in, Go, Gn).e * in;
 }
 
 hipError_t kan_regrid_gram(const float* X, const float* grid_old, const float* grid_new, int64_t N, int in, int Go,
                            int Gn, int accumulate, double* part, double* gram, hipStream_t s) {
   if (N <= 0 || in <= 0 || !kr_grids_ok(Go, Gn)) return hipErrorInvalidValue;
+  const KrGramPlan plan = kr_gram_plan(in, Go, Gn);
+  const int icb = plan.icb, z = kan_regrid_slices(N, in, Go, Gn);
+  if (plan.dense5) {
+    hipLaunchKernelGGL(kan_regrid_gram_dense5_kernel, dim3((in + 63) / 64, z), dim3(64), 0, s, X, grid_old, grid_new, N,
+                       in, part);
+    hipLaunchKernelGGL(kan_regrid_gram_dense5_reduce_kernel, dim3((unsigned)(((int64_t)KR_DENSE5_E * in + 255) / 256)),
+                       dim3(256), 0, s, part, z, in, accumulate, gram);
+    return hipGetLastError();
+  }
   const KrDims d = kr_dims(Go, Gn);
-  const int icb = kr_block_inputs(in, d), z = kan_regrid_slices(N, in, Go, Gn);
   const size_t lds = kr_lds_per_input(d) * icb;
   static bool raised = false;
   const hipError_t e = kg_head_lds(kan_regrid_gram_kernel, lds, raised);

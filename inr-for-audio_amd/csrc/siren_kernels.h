@@ -338,25 +338,15 @@ hipError_t kang_param_grads(const float* dW, const float* spline_w, const float*
                             int accumulate, float* g_base, float* g_spline, float* g_scaler, hipStream_t s);
 hipError_t kan_gemm(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, int M,
                     int N, int64_t K, int splits, float* C, float* out, hipStream_t s);
-// grid update (kan.py:168-215).  New knots [in][12] from the six order statistics q[6][in]
-// (margin2 = fp32(2 margin), one_eps = fp32(1 - grid_eps): the reference's host scalars)
-hipError_t kan_grid_knots(const float* q, int in, float margin, float margin2, float eps, float one_eps, float* grid,
-                          hipStream_t s);
-// gram[in][2][8][8] (fp64: G_nn = sum b_new b_new^T, G_no = sum b_new b_old^T over the N rows of X),
-// added to gram's contents when `accumulate`; part: kan_grid_part_doubles(N, in) doubles of scratch
-int kan_grid_slices(int64_t N, int in);
-int64_t kan_grid_pass_rows(int in);  // rows one pass of the Gram kernel's grid covers
-int64_t kan_grid_part_doubles(int64_t N, int in);
-hipError_t kan_grid_gram(const float* X, const float* grid_old, const float* grid_new, int64_t N, int in,
-                         int accumulate, double* part, double* gram, hipStream_t s);
-// spline_w_new = fp32(G_nn^-1 G_no (spline_w * scaler)) per input; M: in * 64 doubles of scratch;
-// status[0] = rank-deficient inputs (pivot <= 2^-40 max diagonal), status[1] = the first of them
-hipError_t kan_grid_refit(const double* gram, int in, int out, const float* spline_w, const float* scaler, double* M,
-                          float* spline_w_new, int* status, hipStream_t s);
-// The refit onto a grid of another size (kan_general.hip, "refit onto a grid of another size"): old
-// knots [in][Go + 7], new knots [in][Gn + 7], both sizes 1 .. KG_MAX_GRID.  q [Gn + 1][in];
-// gram [in]{G_nn [Gn+3][Gn+3], G_no [Gn+3][Go+3]} fp64; part: kan_regrid_part_doubles doubles of
-// scratch (compact: what can be non-zero); scaler may be null (all ones); refit needs no scratch
+// The refit of update_grid (kan.py:168-215, Go = Gn) and of regrid (kan_general.hip, "the refit"): old
+// knots [in][Go + 7], new knots [in][Gn + 7], both sizes 1 .. KG_MAX_GRID.  New knots from the order
+// statistics q [Gn + 1][in] (margin2 = fp32(2 margin), one_eps = fp32(1 - grid_eps): the reference's
+// host scalars).  gram [in]{G_nn [Gn+3][Gn+3], G_no [Gn+3][Go+3]} (fp64: G_nn = sum b_new b_new^T,
+// G_no = sum b_new b_old^T over the N rows of X), added to gram's contents when `accumulate`; part:
+// kan_regrid_part_doubles doubles of scratch (what can be non-zero; the dense pair at 5 -> 5);
+// pass_rows: the rows one pass of the Gram kernel's grid covers.  spline_w_new = fp32(G_nn^-1 G_no
+// (spline_w * scaler)) per input, scaler may be null (all ones), no scratch; status[0] = rank-deficient
+// inputs (pivot <= 2^-40 max diagonal), status[1] = the first of them
 hipError_t kan_regrid_knots(const float* q, int in, int Gn, float margin, float margin2, float eps, float one_eps,
                             float* grid, hipStream_t s);
 int kan_regrid_slices(int64_t N, int in, int Go, int Gn);

@@ -15,13 +15,13 @@ parameters and, when asked for, the input), so a user loop with ``loss.backward(
 ``torch.optim`` trains them as it trains the reference's modules (kan.py:153-166, 268-273); the
 fused fit goes through ``KanEngine`` / ``run.train(arch='kan')``.  ``KANLinear.update_grid`` /
 ``KAN.forward(x, update_grid=True)`` (kan.py:168-215, :274-279) run on the HIP path too
-(siren_kan_grid_*: knots, per-input Gram sums in fp64, Cholesky refit) at grid_size 5, whose 8 x 8
-Gram matrices those kernels are written for; ``regularization_loss``
+(siren_kan_regrid_*: knots, per-input Gram sums in fp64, Cholesky refit) at grid_size 5, the size at
+which they are checked against the reference; ``regularization_loss``
 (kan.py:217-237, :281-285) is the reference's torch expression on the parameters.
 
 ``KANLinear.regrid`` / ``KAN.regrid`` (no counterpart in the reference) return a new layer / model on a
-grid of another size, 1 to 64, fitted to this one over a batch (siren_kan_regrid_*: the same three
-steps with Gram matrices of (Gn+3)^2 and (Gn+3) x (Go+3)): the step of a coarse-to-fine grid
+grid of another size, 1 to 64, fitted to this one over a batch (the same three steps, ``_refit``, with
+Gram matrices of (Gn+3)^2 and (Gn+3) x (Go+3)): the step of a coarse-to-fine grid
 curriculum, ``run.train(kan_prev_grid_size=...)``.  They refit the unscaled coefficients and keep the
 layer's function, unlike update_grid, which stores a scaled fit undivided.
 """
@@ -103,74 +103,21 @@ class KANLinear(torch.nn.Module):
         return _kan_apply([self.in_features, self.out_features], [self], x,
                           [self.base_weight, self.spline_weight, self.spline_scaler])
 
-    @torch.no_grad()
-    def update_grid(self, x: torch.Tensor, margin=0.01, chunk: int = 1 << 20):
-        """kan.py:168-215 on the HIP path: new knots from the order statistics of x (batch, in), then
-        the curves refitted on them over the batch -- through the 8 x 8 Gram matrices of the bases
-        per input (siren_kan_grid_*), not the reference's (batch, in, out) intermediate and lstsq.
-        Like the reference the refit targets the scaled curves and stores the result in
-        spline_weight undivided.  `grid` and `spline_weight` are written in place, and only once the
-        refit succeeded: an input whose Gram matrix is rank deficient (a constant input, fewer than
-        8 distinct useful samples) raises SirenError and leaves the layer as it was."""
-        _hip_check_layer(self)
-        _update_grid_check(self.grid_size)
+    def _refit(self, x: torch.Tensor, g_new: int, margin, chunk, scaled: bool, who: str, outcome: str):
+        """The steps update_grid and regrid share (siren_kan_regrid_*): the order statistics of x
+        (batch, in), the knots of a grid of `g_new` intervals from them, the Gram sums of the new and
+        the old bases in row chunks, and the refit of spline_weight (times spline_scaler when `scaled`)
+        on the new knots.  Returns (grid_new, spline_weight_new) and writes nothing of the layer's; a
+        rank-deficient input raises SirenError in the caller's words `who` and `outcome`."""
         if not x.is_cuda:
-            raise RuntimeError("KANLinear.update_grid runs on the HIP path only (CUDA tensors)")
+            raise RuntimeError(f"KANLinear.{who} runs on the HIP path only (CUDA tensors)")
         if x.dim() != 2 or x.size(1) != self.in_features:
-            raise ValueError(f"update_grid: x must be (batch, {self.in_features})")
+            raise ValueError(f"{who}: x must be (batch, {self.in_features})")
         lib, dev = _lib.load(), x.device
         s = torch.cuda.current_stream(dev).cuda_stream
-        n_in, n_out, rows = self.in_features, self.out_features, x.size(0)
+        n_in, n_out, rows, g_old = self.in_features, self.out_features, x.size(0), self.grid_size
         xs = x.detach().float().contiguous()
         # order statistics: any exact selection will do; the indices are the reference's own call
-        idx = torch.linspace(0, rows - 1, self.grid_size + 1, dtype=torch.int64)
-        q = torch.sort(xs, dim=0)[0][idx.to(dev)].contiguous()
-        grid_new = torch.empty_like(self.grid)
-        check(lib.siren_kan_grid_knots(ptr(q), n_in, float(margin), float(self.grid_eps), ptr(grid_new), s),
-              "siren_kan_grid_knots")
-        rows_c = max(1, min(int(chunk), rows))
-        ws = torch.empty(int(lib.siren_kan_grid_workspace_bytes(rows_c, n_in)), dtype=torch.uint8, device=dev)
-        gram = torch.empty(n_in, 2, 8, 8, dtype=torch.float64, device=dev)
-        for lo in range(0, rows, rows_c):
-            hi = min(rows, lo + rows_c)
-            check(lib.siren_kan_grid_gram(ptr(xs[lo:hi]), hi - lo, n_in, ptr(self.grid), ptr(grid_new), int(lo > 0),
-                                          ptr(gram), ptr(ws), s), "siren_kan_grid_gram")
-        sw = self.spline_weight.detach()
-        sw_new = torch.empty_like(sw)
-        status = torch.empty(2, dtype=torch.int32, device=dev)
-        check(lib.siren_kan_grid_refit(ptr(gram), n_in, n_out, ptr(sw), ptr(self.spline_scaler.detach()),
-                                       ptr(sw_new), ptr(status), ptr(ws), s), "siren_kan_grid_refit")
-        bad, first = status.tolist()  # the one host synchronisation: this is not a per-step call
-        if bad:
-            raise _lib.SirenError(
-                f"update_grid: the refit of input {first} is rank deficient ({bad} input(s) in all: a constant "
-                "input, or fewer than 8 distinct useful samples); the layer is unchanged")
-        self.grid.copy_(grid_new)
-        self.spline_weight.data.copy_(sw_new)
-
-    @torch.no_grad()
-    def regrid(self, x: torch.Tensor, grid_size: int, margin=0.01, chunk: int = 1 << 20) -> "KANLinear":
-        """A new layer at `grid_size` (1 to 64, the layer's own size included) that computes this
-        layer's function on knots taken from x (batch, in): the knots are update_grid's (kan.py:183-212
-        with `grid_size` for the grid size), and the curves are refitted on them by least squares over
-        the batch through the Gram matrices of the new and the old bases (siren_kan_regrid_*).
-        ``base_weight`` and ``spline_scaler`` are copied and ``spline_weight`` is refitted from the
-        UNSCALED coefficients; by linearity the new layer's scaled curves are then the least-squares
-        fit of this layer's scaled curves, so the layer's function is kept up to that fit.  This is
-        deliberately not update_grid's quirk (kan.py:175, :215), which fits the scaled curves and
-        stores the result undivided, scaling the curves by spline_scaler once more.  `self` is never
-        modified; a rank-deficient input (a constant input, fewer than grid_size + 3 distinct useful
-        samples) raises SirenError and returns nothing.  Not differentiable."""
-        _hip_check_layer(self)
-        _hip_check_grid(grid_size, self.spline_order)
-        if not x.is_cuda:
-            raise RuntimeError("KANLinear.regrid runs on the HIP path only (CUDA tensors)")
-        if x.dim() != 2 or x.size(1) != self.in_features:
-            raise ValueError(f"regrid: x must be (batch, {self.in_features})")
-        lib, dev = _lib.load(), x.device
-        s = torch.cuda.current_stream(dev).cuda_stream
-        n_in, n_out, rows, g_old, g_new = self.in_features, self.out_features, x.size(0), self.grid_size, int(grid_size)
-        xs = x.detach().float().contiguous()
         idx = torch.linspace(0, rows - 1, g_new + 1, dtype=torch.int64)
         q = torch.sort(xs, dim=0)[0][idx.to(dev)].contiguous()
         grid_old = self.grid.detach().to(dev, torch.float32).contiguous()
@@ -186,16 +133,50 @@ class KANLinear(torch.nn.Module):
             check(lib.siren_kan_regrid_gram(ptr(xs[lo:hi]), hi - lo, n_in, g_old, g_new, ptr(grid_old), ptr(grid_new),
                                             int(lo > 0), ptr(gram), ptr(ws), s), "siren_kan_regrid_gram")
         sw = self.spline_weight.detach().to(dev, torch.float32).contiguous()
+        scaler = self.spline_scaler.detach().to(dev, torch.float32).contiguous() if scaled else None
         sw_new = torch.empty(n_out, n_in, g_new + 3, dtype=torch.float32, device=dev)
         status = torch.empty(2, dtype=torch.int32, device=dev)
-        check(lib.siren_kan_regrid_refit(ptr(gram), n_in, n_out, g_old, g_new, ptr(sw), None, ptr(sw_new), ptr(status),
-                                         s), "siren_kan_regrid_refit")
-        bad, first = status.tolist()  # the one host synchronisation
+        check(lib.siren_kan_regrid_refit(ptr(gram), n_in, n_out, g_old, g_new, ptr(sw), ptr(scaler), ptr(sw_new),
+                                         ptr(status), s), "siren_kan_regrid_refit")
+        bad, first = status.tolist()  # the one host synchronisation: this is not a per-step call
         if bad:
             raise _lib.SirenError(
-                f"regrid: the refit of input {first} is rank deficient ({bad} input(s) in all: a constant input, or "
-                f"fewer than {g_new + 3} distinct useful samples); no layer is returned")
-        new = _blank_layer(self, g_new).to(dev)
+                f"{who}: the refit of input {first} is rank deficient ({bad} input(s) in all: a constant input, or "
+                f"fewer than {g_new + 3} distinct useful samples); {outcome}")
+        return grid_new, sw_new
+
+    @torch.no_grad()
+    def update_grid(self, x: torch.Tensor, margin=0.01, chunk: int = 1 << 20):
+        """kan.py:168-215 on the HIP path: new knots from the order statistics of x (batch, in), then
+        the curves refitted on them over the batch -- through the Gram matrices of the bases per input
+        (``_refit`` at the layer's own grid size), not the reference's (batch, in, out) intermediate
+        and lstsq.  Like the reference the refit targets the scaled curves and stores the result in
+        spline_weight undivided.  `grid` and `spline_weight` are written in place, and only once the
+        refit succeeded: an input whose Gram matrix is rank deficient (a constant input, fewer than
+        8 distinct useful samples) raises SirenError and leaves the layer as it was."""
+        _hip_check_layer(self)
+        _update_grid_check(self.grid_size)
+        grid_new, sw_new = self._refit(x, self.grid_size, margin, chunk, True, "update_grid", "the layer is unchanged")
+        self.grid.copy_(grid_new)
+        self.spline_weight.data.copy_(sw_new)
+
+    @torch.no_grad()
+    def regrid(self, x: torch.Tensor, grid_size: int, margin=0.01, chunk: int = 1 << 20) -> "KANLinear":
+        """A new layer at `grid_size` (1 to 64, the layer's own size included) that computes this
+        layer's function on knots taken from x (batch, in): the knots are update_grid's (kan.py:183-212
+        with `grid_size` for the grid size), and the curves are refitted on them by least squares over
+        the batch through the Gram matrices of the new and the old bases (``_refit``).
+        ``base_weight`` and ``spline_scaler`` are copied and ``spline_weight`` is refitted from the
+        UNSCALED coefficients; by linearity the new layer's scaled curves are then the least-squares
+        fit of this layer's scaled curves, so the layer's function is kept up to that fit.  This is
+        deliberately not update_grid's quirk (kan.py:175, :215), which fits the scaled curves and
+        stores the result undivided, scaling the curves by spline_scaler once more.  `self` is never
+        modified; a rank-deficient input (a constant input, fewer than grid_size + 3 distinct useful
+        samples) raises SirenError and returns nothing.  Not differentiable."""
+        _hip_check_layer(self)
+        _hip_check_grid(grid_size, self.spline_order)
+        grid_new, sw_new = self._refit(x, int(grid_size), margin, chunk, False, "regrid", "no layer is returned")
+        new = _blank_layer(self, int(grid_size)).to(x.device)
         new.grid.copy_(grid_new)
         new.base_weight.data.copy_(self.base_weight.detach())
         new.spline_scaler.data.copy_(self.spline_scaler.detach())
@@ -230,8 +211,8 @@ def _blank_layer(src: "KANLinear", grid_size: int) -> "KANLinear":
 def _update_grid_check(grid_size):
     if grid_size != 5:
         raise NotImplementedError(
-            f"update_grid: the refit's Gram and Cholesky kernels are 8 x 8 (grid_size=5); grid_size={grid_size} "
-            "trains and infers on the HIP path but cannot refit its grid")
+            f"update_grid is checked against the reference at grid_size=5 only; grid_size={grid_size} trains, "
+            "infers and regrids on the HIP path but cannot update its grid in place")
 
 
 def _hip_check_layer(lay: "KANLinear"):

@@ -1,5 +1,5 @@
 """fp64 numpy restatement of efficient-KAN's ``KANLinear.update_grid`` (kan.py:168-215) and of the
-layer forward (kan.py:153-166), for judging the HIP grid update (csrc/kan.hip kan_grid_*).
+layer forward (kan.py:153-166), for judging the HIP grid update (csrc/kan_general.hip kan_regrid_* at 5 -> 5).
 
 Everything is fp64: the bases (the Cox-de Boor recursion of kan.py:94-104), the curves, the knots and
 the least-squares fit (``numpy.linalg.lstsq``, an SVD).  ``knots32`` is the one fp32 routine: the

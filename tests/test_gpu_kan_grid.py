@@ -1,4 +1,4 @@
-"""The KAN grid update (kan.py:168-215) on the HIP path: each kernel through the C-ABI
+"""The KAN grid update (kan.py:168-215) on the HIP path: each kernel through the C-ABI's (5, 5) forwards
 (siren_kan_grid_knots / _gram / _refit), KANLinear.update_grid, KAN.forward(x, update_grid=True),
 KanEngine.update_grid and regularization_loss, against tests/golden/kan_grid_update.npz (the
 reference's own results, tests/golden/make_golden_kan_grid.py) and the fp64 restatement
@@ -220,6 +220,30 @@ def test_layer_update_grid(lib, dev, fx, name):
     y = lay(_t(c["x"], dev)).detach().cpu().numpy()
     y64 = gr.layer_forward(c["x"], c["new_grid"], c["base_weight"], c64, c["spline_scaler"])
     assert np.abs(y - y64).max() <= 1e-5 * max(1.0, np.abs(y64).max())
+
+
+def test_layer_update_grid_in_small_chunks(lib, dev, fx):
+    """chunk smaller than the batch (257 rows in chunks of 100): the refit of the Gram sums accumulated
+    over the same row pieces in the same order, bit for bit, and inside the layer test's gate."""
+    from inr_for_audio_amd._lib import check, ptr
+    c = case(fx, "normal")
+    rows, fin = c["x"].shape
+    assert rows > 200 and rows % 100
+    lay = make_layer(c, dev)
+    lay.update_grid(_t(c["x"], dev), chunk=100)
+    assert np.array_equal(bits(lay.grid), c["new_grid"].view(np.int32))
+    xs, go, gn = _t(c["x"], dev), _t(c["grid"], dev), _t(c["new_grid"], dev)
+    gram = torch.full((fin, 2, 8, 8), NAN, dtype=torch.float64, device=dev)
+    ws = torch.full((int(lib.siren_kan_grid_workspace_bytes(100, fin)) // 8,), NAN, dtype=torch.float64, device=dev)
+    for lo in range(0, rows, 100):
+        hi = min(rows, lo + 100)
+        check(lib.siren_kan_grid_gram(ptr(xs[lo:hi]), hi - lo, fin, ptr(go), ptr(gn), int(lo > 0), ptr(gram), ptr(ws),
+                                      _s(dev)), "gram")
+    want, status = dev_refit(lib, dev, gram.cpu().numpy(), c["spline_weight"], c["spline_scaler"])
+    assert status[0] == 0
+    assert np.array_equal(bits(lay.spline_weight), want.view(np.int32))
+    _, c64 = gr.update_grid(c["x"], c["grid"], c["spline_weight"], c["spline_scaler"], grid_new=c["new_grid"])
+    assert gr.coeff_error(lay.spline_weight.detach().cpu().numpy(), c64) <= 4 * float(c["ref_err"])
 
 
 def test_layer_rank_deficiency_raises(lib, dev, fx):

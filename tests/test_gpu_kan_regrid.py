@@ -155,6 +155,8 @@ ALL_ROWS, ALL_FIN = [1, 63, 65, 2049, "pass+77"], [1, 5, 64, 65]
 GRAM_CASES = [(go, gn, rows, fin) for go, gn in ((5, 10), (64, 64)) for rows in ALL_ROWS for fin in ALL_FIN]
 GRAM_CASES += [(go, gn, rows, fin) for go, gn in rr.PAIRS if (go, gn) not in ((5, 10), (64, 64))
                for rows, fin in ((2049, 65), (1, 1))]
+# either side of the dense 5 -> 5 kernel, on the compact one: two column groups, row and input tails
+GRAM_CASES += [(5, 6, 65, 65), (6, 5, 65, 65)]
 
 
 @pytest.mark.parametrize("Go,Gn,rows,fin", GRAM_CASES)
@@ -182,7 +184,7 @@ def test_gram(lib, dev, Go, Gn, rows, fin):
     assert np.array_equal(got[0], got[0].transpose(0, 2, 1))
 
 
-# ---- at 5 -> 5 against the grid-5 entry points ---------------------------------------------------
+# ---- at 5 -> 5 against the grid-5 entry points, which forward here ------------------------------
 def grid5_gram(lib, dev, x, go, gn):
     from inr_for_audio_amd._lib import check, ptr
     rows, fin = x.shape
@@ -196,20 +198,22 @@ def grid5_gram(lib, dev, x, go, gn):
 
 @pytest.mark.parametrize("rows,fin", [(2049, 65), (63, 5)])
 def test_gram_5_to_5_equals_grid_gram(lib, dev, rows, fin):
+    """siren_kan_grid_* is siren_kan_regrid_* at (5, 5): the same sums bit for bit, the same sizes."""
     x, go, gn = gram_inputs(rows, fin, 5, 5)
-    _, terms = gram_reference(x, go, gn)
     g5 = grid5_gram(lib, dev, x, go, gn)[0].cpu().numpy()
     got = dev_gram(lib, dev, x, go, gn)
     for k in range(2):
-        assert (np.abs(got[k] - g5[:, k]) <= rows * 2.0 ** -52 * terms[k]).all()
-    print(f"5 -> 5 rows {rows} in {fin}: Gram sums bit-identical to siren_kan_grid_gram: "
-          f"{np.array_equal(bits(got[0]), bits(g5[:, 0])) and np.array_equal(bits(got[1]), bits(g5[:, 1]))}")
+        assert np.array_equal(bits(got[k]), bits(g5[:, k]))
+    for n_in in (1, 65, 256, 512, 4096):
+        assert lib.siren_kan_grid_pass_rows(n_in) == lib.siren_kan_regrid_pass_rows(n_in, 5, 5) > 0
+        for n in (1, rows, 441000):
+            assert lib.siren_kan_grid_workspace_bytes(n, n_in) == lib.siren_kan_regrid_workspace_bytes(n, n_in, 5, 5) > 0
 
 
 @pytest.mark.parametrize("name", GRID5_SOLVABLE)
 def test_refit_5_to_5_equals_grid_refit(lib, dev, fx5, name):
     """On the solvable cases of kan_grid_update.npz, with the scaler (siren_kan_grid_refit always has
-    one): within one fp32 ulp at the row's largest coefficient."""
+    one): bit for bit."""
     from inr_for_audio_amd._lib import check, ptr
     c = case(fx5, name)
     fout, fin = c["spline_scaler"].shape
@@ -220,14 +224,10 @@ def test_refit_5_to_5_equals_grid_refit(lib, dev, fx5, name):
     check(lib.siren_kan_grid_refit(ptr(g5), fin, fout, ptr(sw), ptr(sc), ptr(want), ptr(status), ptr(ws), _s(dev)),
           "grid refit")
     assert status.cpu().tolist()[0] == 0
-    want = want.cpu().numpy().astype(F64)
     g_nn, g_no = dev_gram(lib, dev, c["x"], c["grid"], c["new_grid"])
     got, st = dev_refit(lib, dev, g_nn, g_no, c["spline_weight"], c["spline_scaler"])
     assert st[0] == 0
-    bound = 2.0 ** -23 * np.abs(want).max(-1, keepdims=True)
-    print(f"refit 5 -> 5 {name}: worst difference {float((np.abs(got - want) / bound).max()):.3f} ulp; bit-identical: "
-          f"{np.array_equal(bits(got), bits(want.astype(F32)))}")
-    assert (np.abs(got - want) <= bound).all()
+    assert np.array_equal(bits(got), bits(want))
 
 
 # ---- refit ---------------------------------------------------------------------------------------

@@ -4,8 +4,8 @@
 
 Per layer of KAN([1, W, W, 1]) at `rows` coordinates and per pair of grid sizes (5 -> 5, 5 -> 10,
 10 -> 20, 64 -> 64): knots, Gram sums (with the achieved rate of the one read of the layer input) and
-refit, each the median of `reps` timed launches after one warm-up, by device events.  At 5 -> 5 the
-grid-5 entry points (siren_kan_grid_*) are timed beside them in the same process.  The layers' inputs
+refit, each the median of `reps` timed launches after one warm-up, by device events.  5 -> 5 is
+update_grid's case (tools/kan_grid_bench.py times it with its order statistics).  The layers' inputs
 are the old model's activations; an input the rank rule refuses is counted, its time stands.  One JSON
 line.
 """
@@ -36,9 +36,8 @@ def timed(fn, reps):
     return statistics.median(ms)
 
 
-def stages(lay, x, g_new, reps, grid5=False):
-    """Median ms of each stage of lay.regrid(x, g_new) (grid5: of lay.update_grid(x) through the
-    grid-5 entry points), without touching the layer."""
+def stages(lay, x, g_new, reps):
+    """Median ms of each stage of lay.regrid(x, g_new), without touching the layer."""
     from inr_for_audio_amd import _lib
     from inr_for_audio_amd._lib import check, ptr
     lib, dev = _lib.load(), x.device
@@ -48,25 +47,17 @@ def stages(lay, x, g_new, reps, grid5=False):
     q = torch.sort(x, dim=0)[0][idx].contiguous()
     grid_new = torch.empty(fin, g_new + 7, dtype=torch.float32, device=dev)
     gram = torch.empty(fin * (g_new + 3) * (g_new + g_old + 6), dtype=torch.float64, device=dev)
-    sw, sc = lay.spline_weight.detach(), lay.spline_scaler.detach()
+    sw = lay.spline_weight.detach()
     sw_new = torch.empty(fout, fin, g_new + 3, dtype=torch.float32, device=dev)
     status = torch.empty(2, dtype=torch.int32, device=dev)
     t = {}
-    if grid5:
-        ws = torch.empty(int(lib.siren_kan_grid_workspace_bytes(rows, fin)), dtype=torch.uint8, device=dev)
-        t["knots_ms"] = timed(lambda: check(lib.siren_kan_grid_knots(ptr(q), fin, 0.01, lay.grid_eps, ptr(grid_new), s)), reps)
-        t["gram_ms"] = timed(lambda: check(lib.siren_kan_grid_gram(ptr(x), rows, fin, ptr(lay.grid), ptr(grid_new), 0,
-                                                                    ptr(gram), ptr(ws), s)), reps)
-        t["refit_ms"] = timed(lambda: check(lib.siren_kan_grid_refit(ptr(gram), fin, fout, ptr(sw), ptr(sc), ptr(sw_new),
-                                                                      ptr(status), ptr(ws), s)), reps)
-    else:
-        ws = torch.empty(int(lib.siren_kan_regrid_workspace_bytes(rows, fin, g_old, g_new)), dtype=torch.uint8, device=dev)
-        t["knots_ms"] = timed(lambda: check(lib.siren_kan_regrid_knots(ptr(q), fin, g_new, 0.01, lay.grid_eps,
-                                                                        ptr(grid_new), s)), reps)
-        t["gram_ms"] = timed(lambda: check(lib.siren_kan_regrid_gram(ptr(x), rows, fin, g_old, g_new, ptr(lay.grid),
-                                                                      ptr(grid_new), 0, ptr(gram), ptr(ws), s)), reps)
-        t["refit_ms"] = timed(lambda: check(lib.siren_kan_regrid_refit(ptr(gram), fin, fout, g_old, g_new, ptr(sw), None,
-                                                                        ptr(sw_new), ptr(status), s)), reps)
+    ws = torch.empty(int(lib.siren_kan_regrid_workspace_bytes(rows, fin, g_old, g_new)), dtype=torch.uint8, device=dev)
+    t["knots_ms"] = timed(lambda: check(lib.siren_kan_regrid_knots(ptr(q), fin, g_new, 0.01, lay.grid_eps,
+                                                                    ptr(grid_new), s)), reps)
+    t["gram_ms"] = timed(lambda: check(lib.siren_kan_regrid_gram(ptr(x), rows, fin, g_old, g_new, ptr(lay.grid),
+                                                                  ptr(grid_new), 0, ptr(gram), ptr(ws), s)), reps)
+    t["refit_ms"] = timed(lambda: check(lib.siren_kan_regrid_refit(ptr(gram), fin, fout, g_old, g_new, ptr(sw), None,
+                                                                    ptr(sw_new), ptr(status), s)), reps)
     t["workspace_MB"] = ws.numel() / 1e6
     t["gram_read_GBps"] = rows * fin * 4 / (t["gram_ms"] * 1e-3) / 1e9
     t["rank_deficient_inputs"] = int(status[0].item())
@@ -93,10 +84,7 @@ def main():
             h = torch.linspace(-1, 1, a.rows, device=dev).reshape(-1, 1)
             layers = []
             for lay in model.layers:
-                t = {"in": lay.in_features, "out": lay.out_features, "regrid": stages(lay, h, g_new, a.reps)}
-                if (g_old, g_new) == (5, 5):
-                    t["grid5_entry_points"] = stages(lay, h, 5, a.reps, grid5=True)
-                layers.append(t)
+                layers.append({"in": lay.in_features, "out": lay.out_features, "regrid": stages(lay, h, g_new, a.reps)})
                 h = layer_forward(lay, h)
             res["pairs"][f"{g_old}->{g_new}"] = layers
     line = json.dumps(res)
