@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG, "csrc")
 HEADER = os.path.join(os.path.dirname(PKG), "include", "siren_hip.h")
 SOURCES = ["capi.hip", "gemm_nt.hip", "gemm_nt1.hip", "gemm_nt2.hip", "gemm_tn.hip", "elementwise.hip", "kan.hip", "kan_general.hip", "layer_fp32.hip",
            "rff.hip", "stft.hip", "plane.hip"]
-HEADERS = ["siren_common.h", "siren_kernels.h", "gemm_pipeline.h"]
+HEADERS = ["siren_common.h", "siren_kernels.h", "gemm_pipeline.h", "kan_tiles.h"]
 ARCH = "gfx950"
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall",
          "-Wno-unused-variable", "-Wno-unused-function"]

@@ -38,20 +38,25 @@ struct ProfState {
 };
 ProfState g_prof;
 
-inline void prof_begin(int kind, hipStream_t s) {
+}  // namespace
+
+// declared in siren_kernels.h: kan_hidden_bwd brackets its own launches
+void siren::prof_begin(int kind, hipStream_t s) {
   g_prof.open = false;
   if (!g_prof.on || g_prof.used >= (int)g_prof.kind.size() || !((g_prof.mask >> kind) & 1u)) return;
   (void)hipEventRecord(g_prof.ev[2 * g_prof.used], s);
   g_prof.kind[g_prof.used] = kind;
   g_prof.open = true;
 }
-inline void prof_end(hipStream_t s, int launches = 1) {
+void siren::prof_end(hipStream_t s, int launches) {
   if (!g_prof.open) return;
   (void)hipEventRecord(g_prof.ev[2 * g_prof.used + 1], s);
   g_prof.nl[g_prof.used] = launches;
   g_prof.used++;
   g_prof.open = false;
 }
+
+namespace {
 
 #define SIREN_PROF(kind, s, expr)            \
   do {                                       \
@@ -1287,29 +1292,15 @@ int siren_profile_read(int32_t kind, double* total_ms, int64_t* count) {
 namespace {
 
 static_assert(SIREN_KAN_MAX_GRID == KG_MAX_GRID, "the header's grid-size limit is the kernels'");
+static_assert(SIREN_PROF_KAN_DW == KAN_PROF_DW && SIREN_PROF_KAN_DX == KAN_PROF_DX, "kan_hidden_bwd's profile kinds");
 
 // The net's grid size (0 = the default 5) and which kernel set runs it: grid_size 5 keeps its own
 // kernels (KAN_NB = 8 at compile time) unless SIREN_OPT_KAN_GENERAL sends it through the
 // any-grid-size set, which runs every other size.
-struct KanSel {
-  int G, k1;
-  bool general;
-};
 KanSel kan_sel(const siren_kan_net* n) {
   const int G = n->grid_size == 0 ? 5 : n->grid_size;
   return KanSel{G, G + 4, G != 5 || tuning().kan_general != 0};
 }
-hipError_t sel_combine(const KanSel& k, const float* base_w, const float* spline_w, const float* scaler, int out, int in,
-                       float* W, float* WT, hipStream_t s) {
-  return k.general ? kang_combine(base_w, spline_w, scaler, out, in, k.G, W, WT, s)
-                   : kan_combine(base_w, spline_w, scaler, out, in, W, WT, s);
-}
-hipError_t sel_param_grads(const KanSel& k, const float* dW, const float* spline_w, const float* scaler, int out, int in,
-                           float* g_base, float* g_spline, float* g_scaler, hipStream_t s) {
-  return k.general ? kang_param_grads(dW, spline_w, scaler, out, in, k.G, 1, g_base, g_spline, g_scaler, s)
-                   : kan_param_grads(dW, spline_w, scaler, out, in, 1, g_base, g_spline, g_scaler, s);
-}
-
 int check_kan(const siren_kan_net* n) {
   if (!n) return SIREN_ERR_NULL;
   if (n->n_layers < 1 || n->n_layers > SIREN_KAN_MAX_LAYERS) return SIREN_ERR_CONFIG;
@@ -1381,14 +1372,12 @@ hipError_t kan_run_forward(const siren_kan_net* n, const siren_kan_batch* b, con
   const KanSel k = kan_sel(n);
   for (int l = 0; l < nl; ++l) {
     const int in = n->width[l], out = n->width[l + 1];
-    SIREN_PROF(SIREN_PROF_KAN_MISC, s, sel_combine(k, n->base_w[l], n->spline_w[l], n->scaler[l], out, in, w.W[l], w.WT[l], s));
+    SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_combine(k, n->base_w[l], n->spline_w[l], n->scaler[l], out, in, w.W[l], w.WT[l], s));
     // X[l+1][r][o] = sum_k A[r][k] W[o][k], A = [SiLU(x) | bases(x)] recomputed in LDS
     if (out == 1 && in <= 64)
-      SIREN_PROF(SIREN_PROF_KAN_FWD, s, k.general ? kang_head_fwd(x, n->grid[l], w.W[l], R, in, k.G, w.X[l + 1], s)
-                                                  : kan_head_fwd(x, n->grid[l], w.W[l], R, in, w.X[l + 1], s));
+      SIREN_PROF(SIREN_PROF_KAN_FWD, s, kan_head_fwd(k, x, n->grid[l], w.W[l], R, in, w.X[l + 1], s));
     else
-      SIREN_PROF(SIREN_PROF_KAN_FWD, s, k.general ? kang_fwd_fused(x, n->grid[l], w.W[l], R, in, out, k.G, w.X[l + 1], s)
-                                                  : kan_fwd_fused(x, n->grid[l], w.W[l], R, in, out, w.X[l + 1], s));
+      SIREN_PROF(SIREN_PROF_KAN_FWD, s, kan_fwd_fused(k, x, n->grid[l], w.W[l], R, in, out, w.X[l + 1], s));
     x = w.X[l + 1];
   }
   return hipSuccess;
@@ -1406,25 +1395,14 @@ hipError_t kan_run_backward(const siren_kan_net* net, const siren_kan_grads* gr,
     const float* xl = l == 0 ? b->coords : w.X[l];
     const int64_t max_splits = w.slab_floats / ((int64_t)out * k.k1 * in);
     float* gin = l > 0 ? w.G[cur] : grad_coords;
-    if (out <= 64 && gin && !k.general) {  // the any-grid-size set has no one-pass backward
-      // dW and dX = SiLU' dA_base + sum_c B'_c dA_c in one pass (bases and G read once)
-      SIREN_PROF(SIREN_PROF_KAN_DX, s, kan_bwd_fused(xl, net->grid[l], G, w.WT[l], R, in, out, max_splits, w.slab,
-                                                     w.dW, gin, s));
-      SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_param_grads(w.dW, net->spline_w[l], net->scaler[l], out, in, 1,
-                                                         gr->base_w[l], gr->spline_w[l], gr->scaler[l], s));
-      G = gin;
-      cur ^= 1;
-      continue;
-    }
-    // dW[o][k] = sum_r G[r][o] A[r][k]  (split-K over the coordinates, bases recomputed)
-    SIREN_PROF(SIREN_PROF_KAN_DW, s, k.general ? kang_dw_fused(xl, net->grid[l], G, R, in, out, k.G, max_splits, w.slab, w.dW, s)
-                                               : kan_dw_fused(xl, net->grid[l], G, R, in, out, max_splits, w.slab, w.dW, s));
-    SIREN_PROF(SIREN_PROF_KAN_MISC, s, sel_param_grads(k, w.dW, net->spline_w[l], net->scaler[l], out, in,
+    // dW[o][k] = sum_r G[r][o] A[r][k] (split-K over the coordinates) and, where the layer has an
+    // input gradient, dX = SiLU' dA_base + sum_c B'_c dA_c with dA = G W formed per chunk in LDS:
+    // one pass or two (kan_hidden_bwd), bases recomputed
+    const hipError_t e = kan_hidden_bwd(k, xl, net->grid[l], G, w.WT[l], R, in, out, max_splits, w.slab, w.dW, gin, s);
+    if (e != hipSuccess) return e;
+    SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_param_grads(k, w.dW, net->spline_w[l], net->scaler[l], out, in, 1,
                                                        gr->base_w[l], gr->spline_w[l], gr->scaler[l], s));
     if (!gin) break;  // layer 0 without a coordinate gradient
-    // dX = SiLU' dA_base + sum_c B'_c dA_spline_c with dA = G W formed per chunk in LDS
-    SIREN_PROF(SIREN_PROF_KAN_DX, s, k.general ? kang_dx_fused(xl, net->grid[l], G, w.WT[l], R, in, out, k.G, gin, s)
-                                               : kan_dx_fused(xl, net->grid[l], G, w.WT[l], R, in, out, gin, s));
     G = gin;
     cur ^= 1;
   }
@@ -1487,19 +1465,15 @@ int siren_kan_train_step_loss(const siren_kan_net* net, const siren_kan_grads* g
     const int in = net->width[L - 1];
     const KanSel k = kan_sel(net);
     SIREN_TRY(kan_run_forward(net, b, w, s, L - 1));
-    SIREN_PROF(SIREN_PROF_KAN_MISC, s, sel_combine(k, net->base_w[L - 1], net->spline_w[L - 1], net->scaler[L - 1], 1, in,
+    SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_combine(k, net->base_w[L - 1], net->spline_w[L - 1], net->scaler[L - 1], 1, in,
                                                    w.W[L - 1], w.WT[L - 1], s));
     int nparts = 0;
     const int64_t slots = w.slab_floats / (k.k1 * in), max_parts = (R + 255) / 256;
     SIREN_PROF(SIREN_PROF_KAN_DW, s,
-               k.general ? kang_head_train(w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->target, R, in, k.G, b->n_valid,
-                                           gfac, slots, max_parts, b->out, b->g, w.sse_part, w.slab, w.dW, w.G[cur],
-                                           &nparts, s, loss_mode)
-                         : kan_head_train(w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->target, R, in, b->n_valid, gfac,
-                                          slots, max_parts, b->out, b->g, w.sse_part, w.slab, w.dW, w.G[cur], &nparts,
-                                          s, loss_mode));
+               kan_head_train(k, w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->target, R, in, b->n_valid, gfac, slots,
+                              max_parts, b->out, b->g, w.sse_part, w.slab, w.dW, w.G[cur], &nparts, s, loss_mode));
     SIREN_PROF(SIREN_PROF_KAN_MISC, s, sum_to(w.sse_part, nparts, gr->sse, 1, s));
-    SIREN_PROF(SIREN_PROF_KAN_MISC, s, sel_param_grads(k, w.dW, net->spline_w[L - 1], net->scaler[L - 1], 1, in,
+    SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_param_grads(k, w.dW, net->spline_w[L - 1], net->scaler[L - 1], 1, in, 1,
                                                        gr->base_w[L - 1], gr->spline_w[L - 1], gr->scaler[L - 1], s));
     G = w.G[cur];
     cur ^= 1;
@@ -1541,11 +1515,9 @@ int siren_kan_step_backward(const siren_kan_net* net, const siren_kan_grads* gr,
   // partition, then the hidden layers as in that step
   const KanSel k = kan_sel(net);
   const int64_t slots = w.slab_floats / (k.k1 * in), max_parts = (R + 255) / 256;
-  SIREN_PROF(SIREN_PROF_KAN_DW, s, k.general ? kang_head_bwd(w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->g, R, in, k.G,
-                                                             slots, max_parts, w.slab, w.dW, w.G[0], s)
-                                             : kan_head_bwd(w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->g, R, in, slots,
-                                                            max_parts, w.slab, w.dW, w.G[0], s));
-  SIREN_PROF(SIREN_PROF_KAN_MISC, s, sel_param_grads(k, w.dW, net->spline_w[L - 1], net->scaler[L - 1], 1, in,
+  SIREN_PROF(SIREN_PROF_KAN_DW, s, kan_head_bwd(k, w.X[L - 1], net->grid[L - 1], w.W[L - 1], b->g, R, in, slots,
+                                                max_parts, w.slab, w.dW, w.G[0], s));
+  SIREN_PROF(SIREN_PROF_KAN_MISC, s, kan_param_grads(k, w.dW, net->spline_w[L - 1], net->scaler[L - 1], 1, in, 1,
                                                      gr->base_w[L - 1], gr->spline_w[L - 1], gr->scaler[L - 1], s));
   SIREN_TRY(kan_run_backward(net, gr, b, w, s, w.G[0], L - 2, 1, nullptr));
   return SIREN_OK;

@@ -1,8 +1,9 @@
 // KAN kernels for any grid size (kan.py KANLinear(grid_size=G), spline_order 3): the twins of kan.hip's
-// grid-5 kernels with G as a launch argument.  kan.hip supplies the basis division, the tile
-// loaders, the MFMA loop, the split plan and the slab reduction (its part above KAN_TILES_ONLY).
-#define KAN_TILES_ONLY
-#include "kan.hip"
+// grid-5 kernels with G as a launch argument, the refit (kan_regrid_*) for every size, and the one
+// family of KAN entry points (siren_kernels.h), which picks the set.  kan_tiles.h supplies the basis
+// recursion, the tile loaders, the MFMA loop, the head pass's row steps, the partitions and the slab
+// reduction to both sets.
+#include "kan_tiles.h"
 
 namespace siren {
 
@@ -11,13 +12,13 @@ namespace siren {
 // and K1 = G + 4 A-columns per input are run-time values, one code object per kernel.  grid_size 5
 // keeps kan.hip's kernels; these run every other size (and 5 under SIREN_OPT_KAN_GENERAL).
 // What a (row, input) pair costs does not grow with G: one span s, four non-zero bases B[s-3 .. s]
-// (kg_bases_window: the recursion of kan_bases_window on run-time table strides, the span found by
-// bisection instead of a count over the knots).  The pair's thread keeps that window and never
+// (kan_bases_window<.., KAN_SPAN_BISECT>: the one recursion on run-time table strides, the span found
+// by bisection instead of a count over the knots).  The pair's thread keeps that window and never
 // b[NB]: it writes the four values into a zero-filled A tile at columns ic + NB ii + (s - 3 + q),
-// and the dA tile is read back the same way.  The LDS tiles and the MFMA loop are kan.hip's;
+// and the dA tile is read back the same way.  The LDS tiles and the MFMA loop are kan_tiles.h's;
 // a chunk takes IC = min(16, 144 / K1) inputs so that its K1 IC columns fit the 144-column tiles
 // (G = 5: 16 inputs, G = 11: 9, G = 64: 2).  The backward always runs as kang_dw_fused +
-// kang_dx_fused (no one-pass twin of kan_bwd_fused).
+// kang_dx_fused (no one-pass twin of kan_bwd_fused: kan_hidden_bwd).
 // The skipped columns of a row hold exact zeros in kan.hip's kernels too, where they enter the
 // k-ordered sums as +-0 terms, so at G = 5 both sets add the same non-zero terms in the same order.
 struct KgDims {
@@ -39,6 +40,8 @@ constexpr bool kg_tables_fit() {
 }
 static_assert(kg_tables_fit(), "a chunk's columns, knots or reciprocals outgrow their LDS arrays");
 
+// (Not KfChunk with an nb field: filled with the literal 8 it did not fold away in kan_dx_fused_kernel
+// and kan_bwd_fused_kernel, which then compiled to other instructions.)
 struct KgChunk {
   int i0, ic, kc, kpad, nkt, nb;  // KfChunk's fields, and the bases per input
   __device__ __forceinline__ int col(int kk, int in) const { return kk < ic ? i0 + kk : in + nb * i0 + (kk - ic); }
@@ -46,67 +49,6 @@ struct KgChunk {
 __device__ __forceinline__ KgChunk kg_chunk(int i0, int in, const KgDims& d) {
   const int ic = in - i0 < d.ic ? in - i0 : d.ic, kc = d.k1 * ic, kpad = (kc + 15) & ~15;
   return KgChunk{i0, ic, kc, kpad, kpad >> 4, d.nb};
-}
-
-// kan_bases_window for ng knots: s (-1 outside the grid), w[q] = B[s-3+q] and, with DERIV,
-// d[q] = B'[s-3+q].  The same operations in the same order, so the same bits; inv is the input's
-// table inv[(k-1)(ng-1) + j] = RN(1 / (g[j+k] - g[j])) (kg_fill_inv).  The span: for non-decreasing
-// knots #{j : g[j] <= x} is where the predicate x >= g[j] turns false, found by bisection (a NaN
-// fails every comparison: count 0, no span).  Slots whose basis index s-3+q falls outside 0 .. NB-1
-// hold values of discarded terms: the callers skip them.
-template <bool DERIV, bool RCP>
-__device__ __forceinline__ int kg_bases_window(float x, const float* __restrict__ g, int ng, float* w, float* d,
-                                               const float* __restrict__ inv) {
-  int lo = 0, hi = ng;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (x >= g[mid]) lo = mid + 1;
-    else hi = mid;
-  }
-  const int s = (lo >= 1 && lo <= ng - 1) ? lo - 1 : -1;
-  const int s0 = s < 0 ? 0 : s;
-  float kw[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    int t = s0 - 3 + e;
-    t = t < 0 ? 0 : (t > ng - 1 ? ng - 1 : t);
-    kw[e] = g[t];
-  }
-  float ww[5] = {0.0f, 0.0f, 0.0f, 1.0f, 0.0f}, dd[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-  for (int k = 1; k <= 3; ++k) {
-#pragma unroll
-    for (int q = 3 - k; q < 4; ++q) {
-      const int j = s - 3 + q;
-      const bool ok = j >= 0 && j <= ng - 2 - k;  // inside the support and the array
-      const float gj = kw[q], gjk = kw[q + k], gj1 = kw[q + 1], gjk1 = kw[q + k + 1];
-      float il, ir, l, r;
-      if constexpr (RCP) {
-        il = __builtin_amdgcn_rcpf(gjk - gj);
-        ir = __builtin_amdgcn_rcpf(gjk1 - gj1);
-        l = (x - gj) * il;
-        r = (gjk1 - x) * ir;
-      } else {
-        const int jt = j < 0 ? 0 : (j > ng - 2 - k ? ng - 2 - k : j);  // in-table for discarded terms
-        il = inv[(k - 1) * (ng - 1) + jt];
-        ir = inv[(k - 1) * (ng - 1) + jt + 1];
-        l = kan_div(x - gj, gjk - gj, il);
-        r = kan_div(gjk1 - x, gjk1 - gj1, ir);
-      }
-      if constexpr (DERIV) {
-        const float nd = il * ww[q] + l * dd[q] - ir * ww[q + 1] + r * dd[q + 1];
-        dd[q] = ok ? nd : dd[q];
-      }
-      const float nw = l * ww[q] + r * ww[q + 1];
-      ww[q] = ok ? nw : ww[q];
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    w[q] = ww[q];
-    if constexpr (DERIV) d[q] = dd[q];
-  }
-  return s;
 }
 
 // gk[ii * gst + j] = knot j of input i0 + ii;  inv[ii * vst + (k-1)(ng-1) + j] = RN(1 / (g[j+k] - g[j]))
@@ -162,7 +104,7 @@ __global__ __launch_bounds__(256) void kang_fwd_fused_kernel(const float* __rest
       if (r0 + r >= N) continue;
       const float x = X[(r0 + r) * in + i0 + ii];
       float w[4], unused[4];
-      const int s = kg_bases_window<false, false>(x, gk + ii * d.gst, d.ng, w, unused, inv + ii * d.vst);
+      const int s = kan_bases_window<false, false, KAN_SPAN_BISECT>(x, gk + ii * d.gst, d.ng, w, unused, inv + ii * d.vst);
       As[r][ii] = silu(x);
       if (s < 0) continue;
 #pragma unroll
@@ -230,7 +172,7 @@ __device__ __forceinline__ float kg_head_row(bool on, float x, int lane, const K
   float v = 0.f;
   s = -1;
   if (on) {
-    s = kg_bases_window<DERIV, false>(x, h.gk + lane * d.gst, d.ng, w, dw, h.inv + lane * d.vst);
+    s = kan_bases_window<DERIV, false, KAN_SPAN_BISECT>(x, h.gk + lane * d.gst, d.ng, w, dw, h.inv + lane * d.vst);
     if constexpr (DERIV) silu_and_grad(x, sl, dsl);
     else sl = silu(x);
     const float* wl = h.wl + lane * h.wst;
@@ -307,25 +249,12 @@ __global__ __launch_bounds__(256) void kang_head_train_kernel(const float* __res
     float sl = 0.f, dsl = 0.f, w[4], dw[4];
     int s;
     const float v = kg_head_row<true>(on, xc, lane, h, d, sl, dsl, s, w, dw);
-    float gn = 0.f;
-    if constexpr (GIVEN) {
-      gn = yc;
-    } else {
-      const float o = (0.f + v) + 0.f;  // head_loss's accumulation of the one partial and the zero bias
-      if (n < n_valid) {
-        const float err = o - yc;
-        if constexpr (SRC == KAN_HEAD_L1) {
-          sse += fabsf(err);
-          gn = (err > 0.f ? 1.0f : (err < 0.f ? -1.0f : 0.f)) * gfac;
-        } else {
-          sse += err * err;
-          gn = err * gfac;
-        }
-      }
-      if (lane == 0) {
-        out[n] = o;
-        g[n] = gn;
-      }
+    const KanHeadG hg = kan_head_g<SRC>(v, yc, n < n_valid, gfac, sse);
+    const float gn = hg.gn;
+    sse = hg.sse;
+    if (!GIVEN && lane == 0) {
+      out[n] = hg.o;
+      g[n] = gn;
     }
     if (on) {
       ab += gn * sl;
@@ -354,7 +283,7 @@ __global__ __launch_bounds__(256) void kang_head_train_kernel(const float* __res
         row[t == 0 ? lane : in + d.nb * lane + (t - 1)] = v;
       }
     }
-    if (!GIVEN && lane == 0) sse_part[blockIdx.x] = ((sse_w[0] + sse_w[1]) + sse_w[2]) + sse_w[3];
+    if (!GIVEN && lane == 0) sse_part[blockIdx.x] = kan_head_sse(sse_w);
   }
 }
 
@@ -373,7 +302,7 @@ __device__ __forceinline__ void kg_fill_a(float (*As)[KF_CST], const float (*Xs)
     if (r0 + r >= re) continue;
     const float x = Xs[r][ii];
     float w[4], unused[4];
-    const int s = kg_bases_window<false, true>(x, gk + ii * d.gst, d.ng, w, unused, nullptr);
+    const int s = kan_bases_window<false, true, KAN_SPAN_BISECT>(x, gk + ii * d.gst, d.ng, w, unused, nullptr);
     As[ii][r] = silu(x);
     if (s < 0) continue;
 #pragma unroll
@@ -381,23 +310,6 @@ __device__ __forceinline__ void kg_fill_a(float (*As)[KF_CST], const float (*Xs)
       const int c = s - 3 + q;
       if (c >= 0 && c < d.nb) As[ch.ic + d.nb * ii + c][r] = w[q];
     }
-  }
-}
-
-// kf_store_slab on a KgChunk: slab[z][o + q][col(kk)] = acc[j][q]
-template <int NA>
-__device__ __forceinline__ void kg_store_slab(float* __restrict__ slab, int z, const f32x4 (&acc)[NA], int nj, int kk0,
-                                              int o, const KgChunk& ch, int in, int out, int k1) {
-  const int64_t K = (int64_t)k1 * in;
-  float* out_slab = slab + (int64_t)z * out * K;
-#pragma unroll
-  for (int j = 0; j < NA; ++j) {
-    const int kk = kk0 + 16 * j;
-    if (j >= nj || kk >= ch.kc) continue;
-    const int64_t col = ch.col(kk, in);
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      if (o + q < out) out_slab[(int64_t)(o + q) * K + col] = acc[j][q];
   }
 }
 
@@ -439,7 +351,7 @@ __global__ __launch_bounds__(256) void kang_dw_fused_kernel(const float* __restr
     kf_mfma_groups_n(ch.nkt, &Gt[16 * wv + li][4 * lk], &As[li][4 * lk], 16 * KF_CST, KF_R / 16, acc);
     __syncthreads();
   }
-  kg_store_slab(slab, z, acc, ch.nkt, li, o0 + 16 * wv + 4 * lk, ch, in, out, d.k1);
+  kf_store_slab(slab, z, acc, ch.nkt, li, o0 + 16 * wv + 4 * lk, ch, in, out, d.k1);
 }
 
 // kan_dx_fused_kernel at any grid size.  The pair's contraction reads its window of the dA row:
@@ -494,7 +406,7 @@ __global__ __launch_bounds__(256) void kang_dx_fused_kernel(const float* __restr
       if (r0 + r >= N) continue;
       const float x = Xs[r][ii];
       float w[4], dw[4], sl, ds;
-      const int s = kg_bases_window<true, true>(x, gk + ii * d.gst, d.ng, w, dw, nullptr);
+      const int s = kan_bases_window<true, true, KAN_SPAN_BISECT>(x, gk + ii * d.gst, d.ng, w, dw, nullptr);
       silu_and_grad(x, sl, ds);
       const float* dA = WD + r * KF_DST;
       float v = ds * dA[ii];
@@ -514,10 +426,15 @@ __global__ __launch_bounds__(256) void kang_dx_fused_kernel(const float* __restr
   }
 }
 
-// kan_combine / kan_param_grads with nb bases per input (k1 = nb + 1 columns)
-__global__ void kang_combine_kernel(const float* __restrict__ base_w, const float* __restrict__ spline_w,
-                                    const float* __restrict__ scaler, int out, int in, int nb, float* __restrict__ W,
-                                    float* __restrict__ WT) {
+// W[o][i] = base_w[o][i];  W[o][in + nb i + c] = spline_w[o][i][c] * scaler[o][i]  (kan.py:145-151), and
+// (WT != null) its transpose; nb bases per input (k1 = nb + 1 columns).  One body for both kernel sets:
+// NB = 0 takes nb at run time, NB = KAN_NB is grid 5's instance with the loop unrolled (with the
+// run-time loop at grid 5, cfg5's kan_misc measured 0.0536 against 0.0503 ms per step)
+template <int NB>
+__global__ void kan_combine_kernel(const float* __restrict__ base_w, const float* __restrict__ spline_w,
+                                   const float* __restrict__ scaler, int out, int in, int nb_rt,
+                                   float* __restrict__ W, float* __restrict__ WT) {
+  const int nb = NB ? NB : nb_rt;
   const int total = out * in;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
     const int o = e / in, i = e - o * in;
@@ -525,6 +442,7 @@ __global__ void kang_combine_kernel(const float* __restrict__ base_w, const floa
     row[i] = base_w[e];
     if (WT) WT[(int64_t)i * out + o] = base_w[e];
     const float s = scaler[e];
+#pragma unroll NB ? NB : 1
     for (int c = 0; c < nb; ++c) {
       const float v = spline_w[(int64_t)e * nb + c] * s;
       row[in + nb * i + c] = v;
@@ -533,16 +451,21 @@ __global__ void kang_combine_kernel(const float* __restrict__ base_w, const floa
   }
 }
 
-__global__ void kang_param_grads_kernel(const float* __restrict__ dW, const float* __restrict__ spline_w,
-                                        const float* __restrict__ scaler, int out, int in, int nb, int accumulate,
-                                        float* __restrict__ g_base, float* __restrict__ g_spline,
-                                        float* __restrict__ g_scaler) {
+// Parameter gradients from dW = dLoss/dW_combined (the autograd of kan_combine):
+//   d base_w = dW_base;  d spline_w = dW_spline * scaler;  d scaler = sum_c dW_spline * spline_w
+template <int NB>
+__global__ void kan_param_grads_kernel(const float* __restrict__ dW, const float* __restrict__ spline_w,
+                                       const float* __restrict__ scaler, int out, int in, int nb_rt, int accumulate,
+                                       float* __restrict__ g_base, float* __restrict__ g_spline,
+                                       float* __restrict__ g_scaler) {
+  const int nb = NB ? NB : nb_rt;
   const int total = out * in;
   for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
     const int o = e / in, i = e - o * in;
     const float* row = dW + (int64_t)o * (nb + 1) * in;
     const float s = scaler[e];
     float gs = 0.f;
+#pragma unroll NB ? NB : 1
     for (int c = 0; c < nb; ++c) {
       const float dv = row[in + nb * i + c];
       const int64_t k = (int64_t)e * nb + c;
@@ -571,99 +494,139 @@ static hipError_t kg_head_lds(Kern kernel, size_t bytes, bool& raised) {  // rai
   return e;
 }
 
-hipError_t kang_fwd_fused(const float* X, const float* grid, const float* W, int64_t N, int in, int out, int G, float* Y,
-                          hipStream_t s) {
-  if (N <= 0 || in <= 0 || out <= 0 || !kg_grid_ok(G)) return hipErrorInvalidValue;
+// ---- the KAN entry points (siren_kernels.h): k says which set runs.  The shapes are checked here,
+// once for both sets; the grid-5 launchers are kan.hip's kan5_* -----------------------------------
+hipError_t kan_fwd_fused(const KanSel& k, const float* X, const float* grid, const float* W, int64_t N, int in, int out,
+                         float* Y, hipStream_t s) {
+  if (N <= 0 || in <= 0 || out <= 0 || !kg_grid_ok(k.G)) return hipErrorInvalidValue;
+  if (!k.general) return kan5_fwd_fused(X, grid, W, N, in, out, Y, s);
   hipLaunchKernelGGL(kang_fwd_fused_kernel, dim3((unsigned)((N + KF_R - 1) / KF_R), (out + KF_O - 1) / KF_O), dim3(256),
-                     0, s, X, grid, W, N, in, out, G, Y);
+                     0, s, X, grid, W, N, in, out, k.G, Y);
   return hipGetLastError();
 }
 
-hipError_t kang_head_fwd(const float* X, const float* grid, const float* W, int64_t N, int in, int G, float* Y,
-                         hipStream_t s) {
-  if (N <= 0 || in <= 0 || in > 64 || !kg_grid_ok(G)) return hipErrorInvalidValue;
-  const size_t lds = kg_head_lds_bytes(in, G, false);
+hipError_t kan_head_fwd(const KanSel& k, const float* X, const float* grid, const float* W, int64_t N, int in, float* Y,
+                        hipStream_t s) {
+  if (N <= 0 || in <= 0 || in > 64 || !kg_grid_ok(k.G)) return hipErrorInvalidValue;
+  if (!k.general) return kan5_head_fwd(X, grid, W, N, in, Y, s);
+  const size_t lds = kg_head_lds_bytes(in, k.G, false);
   static bool raised = false;
   const hipError_t e = kg_head_lds(kang_head_fwd_kernel, lds, raised);
   if (e != hipSuccess) return e;
   const int64_t blocks = (N + 3) / 4;
   hipLaunchKernelGGL(kang_head_fwd_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), lds, s, X, grid,
-                     W, N, in, G, Y);
+                     W, N, in, k.G, Y);
   return hipGetLastError();
 }
 
-// kan_head_pass at any grid size: the same block partition
 template <int SRC>
-static hipError_t kang_head_pass(const float* X, const float* grid, const float* W, const float* yg, int64_t N, int in,
-                                 int G, int64_t n_valid, float gfac, int64_t slots, int64_t max_parts, float* out,
-                                 float* g, float* sse_part, float* slab, float* dW, float* Gin, int* nparts,
-                                 hipStream_t s) {
-  if (N <= 0 || in <= 0 || in > 64 || slots < 1 || max_parts < 1 || !kg_grid_ok(G)) return hipErrorInvalidValue;
+static hipError_t kang_head_launch(const KanHeadPlan& p, const float* X, const float* grid, const float* W,
+                                   const float* yg, int64_t N, int in, int G, int64_t n_valid, float gfac, float* out,
+                                   float* g, float* sse_part, float* slab, float* Gin, hipStream_t s) {
   const size_t lds = kg_head_lds_bytes(in, G, true);
   static bool raised = false;  // one per SRC
   const hipError_t e = kg_head_lds(kang_head_train_kernel<SRC>, lds, raised);
   if (e != hipSuccess) return e;
-  int64_t blocks = (N + 255) / 256;
-  if (blocks > slots) blocks = slots;
-  if (blocks > max_parts) blocks = max_parts;
-  const int64_t rpb = (N + blocks - 1) / blocks;
-  blocks = (N + rpb - 1) / rpb;
-  hipLaunchKernelGGL(kang_head_train_kernel<SRC>, dim3((unsigned)blocks), dim3(256), lds, s, X, grid, W, yg, N, in, G,
-                     n_valid, gfac, rpb, out, g, sse_part, slab, Gin);
-  if (nparts) *nparts = (int)blocks;
-  return slab_reduce(slab, (int)blocks, (int64_t)kg_dims(G).k1 * in, dW, s);
+  hipLaunchKernelGGL(kang_head_train_kernel<SRC>, dim3(p.blocks), dim3(256), lds, s, X, grid, W, yg, N, in, G, n_valid,
+                     gfac, p.rows_per_block, out, g, sse_part, slab, Gin);
+  return hipGetLastError();
 }
 
-hipError_t kang_head_train(const float* X, const float* grid, const float* W, const float* y, int64_t N, int in, int G,
-                           int64_t n_valid, float gfac, int64_t slots, int64_t max_parts, float* out, float* g,
-                           float* sse_part, float* slab, float* dW, float* Gin, int* nparts, hipStream_t s,
-                           int loss_mode) {
+// The head pass for g from src (KAN_HEAD_*): kan_head_plan's blocks, then the fixed-order slab sum
+// into dW
+static hipError_t kan_head_pass(const KanSel& k, int src, const float* X, const float* grid, const float* W,
+                                const float* yg, int64_t N, int in, int64_t n_valid, float gfac, int64_t slots,
+                                int64_t max_parts, float* out, float* g, float* sse_part, float* slab, float* dW,
+                                float* Gin, int* nparts, hipStream_t s) {
+  if (N <= 0 || in <= 0 || in > 64 || slots < 1 || max_parts < 1 || !kg_grid_ok(k.G)) return hipErrorInvalidValue;
+  const KanHeadPlan p = kan_head_plan(N, slots, max_parts);
+  const hipError_t e =
+      !k.general ? kan5_head_pass(src, p, X, grid, W, yg, N, in, n_valid, gfac, out, g, sse_part, slab, Gin, s)
+      : (src == KAN_HEAD_GIVEN ? kang_head_launch<KAN_HEAD_GIVEN>
+         : src == KAN_HEAD_L1  ? kang_head_launch<KAN_HEAD_L1>
+                               : kang_head_launch<KAN_HEAD_MSE>)(p, X, grid, W, yg, N, in, k.G, n_valid, gfac, out, g,
+                                                                 sse_part, slab, Gin, s);
+  if (e != hipSuccess) return e;
+  if (nparts) *nparts = (int)p.blocks;
+  return slab_reduce(slab, (int)p.blocks, (int64_t)k.k1 * in, dW, s);
+}
+
+hipError_t kan_head_train(const KanSel& k, const float* X, const float* grid, const float* W, const float* y, int64_t N,
+                          int in, int64_t n_valid, float gfac, int64_t slots, int64_t max_parts, float* out, float* g,
+                          float* sse_part, float* slab, float* dW, float* Gin, int* nparts, hipStream_t s,
+                          int loss_mode) {
   if (!nparts || (loss_mode != 0 && loss_mode != 1)) return hipErrorInvalidValue;
-  return loss_mode == 1 ? kang_head_pass<KAN_HEAD_L1>(X, grid, W, y, N, in, G, n_valid, gfac, slots, max_parts, out, g,
-                                                      sse_part, slab, dW, Gin, nparts, s)
-                        : kang_head_pass<KAN_HEAD_MSE>(X, grid, W, y, N, in, G, n_valid, gfac, slots, max_parts, out, g,
-                                                       sse_part, slab, dW, Gin, nparts, s);
+  return kan_head_pass(k, loss_mode == 1 ? KAN_HEAD_L1 : KAN_HEAD_MSE, X, grid, W, y, N, in, n_valid, gfac, slots,
+                       max_parts, out, g, sse_part, slab, dW, Gin, nparts, s);
 }
 
-hipError_t kang_head_bwd(const float* X, const float* grid, const float* W, const float* g, int64_t N, int in, int G,
-                         int64_t slots, int64_t max_parts, float* slab, float* dW, float* Gin, hipStream_t s) {
-  return kang_head_pass<KAN_HEAD_GIVEN>(X, grid, W, g, N, in, G, N, 0.f, slots, max_parts, nullptr, nullptr, nullptr,
-                                        slab, dW, Gin, nullptr, s);
+hipError_t kan_head_bwd(const KanSel& k, const float* X, const float* grid, const float* W, const float* g, int64_t N,
+                        int in, int64_t slots, int64_t max_parts, float* slab, float* dW, float* Gin, hipStream_t s) {
+  return kan_head_pass(k, KAN_HEAD_GIVEN, X, grid, W, g, N, in, N, 0.f, slots, max_parts, nullptr, nullptr, nullptr,
+                       slab, dW, Gin, nullptr, s);
 }
 
-hipError_t kang_dw_fused(const float* X, const float* grid, const float* Gr, int64_t N, int in, int out, int G,
-                         int64_t max_splits, float* slab, float* dW, hipStream_t s) {
-  if (N <= 0 || in <= 0 || out <= 0 || max_splits < 1 || !kg_grid_ok(G)) return hipErrorInvalidValue;
-  const KgDims d = kg_dims(G);
-  const int nchunk = (in + d.ic - 1) / d.ic, nout = (out + KF_O - 1) / KF_O;
-  const KfSplitPlan p = kf_plan_splits(N, kKanResidentBlocks, (int64_t)nchunk * nout, max_splits);
-  if (!p.blocks) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kang_dw_fused_kernel, dim3(p.blocks), dim3(256), 0, s, X, grid, Gr, N, in, out, G,
-                     p.rows_per_split, nchunk, nout, p.z, slab);
-  return slab_reduce(slab, p.z, (int64_t)out * d.k1 * in, dW, s);
+// dW[o][k] = sum_n G[n][o] A[n][k]: row slices into slabs (kf_plan_dw), then the fixed-order slab sum
+hipError_t kan_dw_fused(const KanSel& k, const float* X, const float* grid, const float* G, int64_t N, int in, int out,
+                        int64_t max_splits, float* slab, float* dW, hipStream_t s) {
+  if (N <= 0 || in <= 0 || out <= 0 || max_splits < 1 || !kg_grid_ok(k.G)) return hipErrorInvalidValue;
+  const KfDwPlan p = kf_plan_dw(N, in, out, k.general ? kg_dims(k.G).ic : KF_IC, max_splits);
+  if (!p.split.blocks) return hipErrorInvalidValue;
+  hipError_t e;
+  if (k.general) {
+    hipLaunchKernelGGL(kang_dw_fused_kernel, dim3(p.split.blocks), dim3(256), 0, s, X, grid, G, N, in, out, k.G,
+                       p.split.rows_per_split, p.nchunk, p.nout, p.split.z, slab);
+    e = hipGetLastError();
+  } else {
+    e = kan5_dw_fused(p, X, grid, G, N, in, out, slab, s);
+  }
+  if (e != hipSuccess) return e;
+  return slab_reduce(slab, p.split.z, (int64_t)out * k.k1 * in, dW, s);
 }
 
-hipError_t kang_dx_fused(const float* X, const float* grid, const float* Gout, const float* WT, int64_t N, int in,
-                         int out, int G, float* Gin, hipStream_t s) {
-  if (N <= 0 || in <= 0 || out <= 0 || !kg_grid_ok(G)) return hipErrorInvalidValue;
+hipError_t kan_dx_fused(const KanSel& k, const float* X, const float* grid, const float* Gout, const float* WT,
+                        int64_t N, int in, int out, float* Gin, hipStream_t s) {
+  if (N <= 0 || in <= 0 || out <= 0 || !kg_grid_ok(k.G)) return hipErrorInvalidValue;
+  if (!k.general) return kan5_dx_fused(X, grid, Gout, WT, N, in, out, Gin, s);
   hipLaunchKernelGGL(kang_dx_fused_kernel, dim3((unsigned)((N + KF_R - 1) / KF_R)), dim3(256), 0, s, X, grid, Gout, WT,
-                     N, in, out, G, Gin);
+                     N, in, out, k.G, Gin);
   return hipGetLastError();
 }
 
-hipError_t kang_combine(const float* base_w, const float* spline_w, const float* scaler, int out, int in, int G,
-                        float* W, float* WT, hipStream_t s) {
-  if (!kg_grid_ok(G)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kang_combine_kernel, dim3(ew_grid((int64_t)out * in)), dim3(256), 0, s, base_w, spline_w, scaler,
-                     out, in, G + 3, W, WT);
+// A hidden layer's backward, dW and (Gin != null) Gin.  The grid-5 set runs both in one pass when
+// out <= 64; the any-grid-size set has no one-pass backward.  Profiled as the caller's launches
+// are: the one-pass backward and the input-gradient pass under KAN_PROF_DX, the weight-gradient
+// pass under KAN_PROF_DW.
+hipError_t kan_hidden_bwd(const KanSel& k, const float* X, const float* grid, const float* G, const float* WT,
+                          int64_t N, int in, int out, int64_t max_splits, float* slab, float* dW, float* Gin,
+                          hipStream_t s) {
+  if (N <= 0 || in <= 0 || out <= 0 || max_splits < 1 || !kg_grid_ok(k.G)) return hipErrorInvalidValue;
+  const bool one_pass = out <= KF_O && Gin && !k.general;
+  prof_begin(one_pass ? KAN_PROF_DX : KAN_PROF_DW, s);
+  hipError_t e = one_pass ? kan5_bwd_fused(X, grid, G, WT, N, in, out, max_splits, slab, dW, Gin, s)
+                          : kan_dw_fused(k, X, grid, G, N, in, out, max_splits, slab, dW, s);
+  prof_end(s);
+  if (e != hipSuccess || one_pass || !Gin) return e;
+  prof_begin(KAN_PROF_DX, s);
+  e = kan_dx_fused(k, X, grid, G, WT, N, in, out, Gin, s);
+  prof_end(s);
+  return e;
+}
+
+hipError_t kan_combine(const KanSel& k, const float* base_w, const float* spline_w, const float* scaler, int out, int in,
+                       float* W, float* WT, hipStream_t s) {
+  if (!kg_grid_ok(k.G)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k.general ? kan_combine_kernel<0> : kan_combine_kernel<KAN_NB>, dim3(ew_grid((int64_t)out * in)),
+                     dim3(256), 0, s, base_w, spline_w, scaler, out, in, k.k1 - 1, W, WT);
   return hipGetLastError();
 }
 
-hipError_t kang_param_grads(const float* dW, const float* spline_w, const float* scaler, int out, int in, int G,
-                            int accumulate, float* g_base, float* g_spline, float* g_scaler, hipStream_t s) {
-  if (!kg_grid_ok(G)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(kang_param_grads_kernel, dim3(ew_grid((int64_t)out * in)), dim3(256), 0, s, dW, spline_w, scaler,
-                     out, in, G + 3, accumulate, g_base, g_spline, g_scaler);
+hipError_t kan_param_grads(const KanSel& k, const float* dW, const float* spline_w, const float* scaler, int out, int in,
+                           int accumulate, float* g_base, float* g_spline, float* g_scaler, hipStream_t s) {
+  if (!kg_grid_ok(k.G)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k.general ? kan_param_grads_kernel<0> : kan_param_grads_kernel<KAN_NB>,
+                     dim3(ew_grid((int64_t)out * in)), dim3(256), 0, s, dW, spline_w, scaler, out, in, k.k1 - 1,
+                     accumulate, g_base, g_spline, g_scaler);
   return hipGetLastError();
 }
 
@@ -777,9 +740,9 @@ __global__ __launch_bounds__(64) void kan_regrid_gram_kernel(const float* __rest
     for (int r = 0; r < KR_ROWS; ++r) {
       if (!on || t * KR_ROWS + r >= N) continue;
       float wn[4], wo[4], unused[4];
-      const int sn = kg_bases_window<false, false>(x[r], gkn + lane * d.n.gst, d.n.ng, wn, unused, ivn + lane * d.n.vst);
+      const int sn = kan_bases_window<false, false, KAN_SPAN_BISECT>(x[r], gkn + lane * d.n.gst, d.n.ng, wn, unused, ivn + lane * d.n.vst);
       if (sn < 0) continue;
-      const int so = kg_bases_window<false, false>(x[r], gko + lane * d.o.gst, d.o.ng, wo, unused, ivo + lane * d.o.vst);
+      const int so = kan_bases_window<false, false, KAN_SPAN_BISECT>(x[r], gko + lane * d.o.gst, d.o.ng, wo, unused, ivo + lane * d.o.vst);
       double* blk = a + (int64_t)(d.nn + 16 * (sn + (so < 0 ? 0 : so))) * icb;
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
@@ -882,9 +845,9 @@ __global__ __launch_bounds__(64) void kan_regrid_gram_dense5_kernel(const float*
     for (int r = 0; r < KR_ROWS; ++r) {
       if (!on || t * KR_ROWS + r >= N) continue;
       float wn[4], wo[4], unused[4];
-      const int sn = kan_bases_window<false, false, false>(x[r], gk[1][lane], wn, unused, inv[1][lane]);
+      const int sn = kan_bases_window<false, false, KAN_SPAN_SELECT>(x[r], gk[1][lane], KAN_NG, wn, unused, inv[1][lane]);
       if (sn < 0) continue;
-      const int so = kan_bases_window<false, false, false>(x[r], gk[0][lane], wo, unused, inv[0][lane]);
+      const int so = kan_bases_window<false, false, KAN_SPAN_SELECT>(x[r], gk[0][lane], KAN_NG, wo, unused, inv[0][lane]);
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         const int c = sn - 3 + p;

@@ -283,59 +283,55 @@ hipError_t spec_gather(int n, const SpecWs& w, float* g, hipStream_t s);        
 hipError_t loss_mix(const float* out, const float* y, int n, int rows, const SpecWs& w, int loss_mode, double alpha,
                     float gfac, float* g, hipStream_t s, int lo = 0);
 
-// KAN (kan.hip): fp32, grid_size 5, spline_order 3
-constexpr int KAN_NB = 8;           // grid_size + spline_order bases per input
+// KAN (kan.hip, kan_general.hip): fp32, spline_order 3, any grid size G = 1 .. KG_MAX_GRID:
+// NB = G + 3 bases, NG = G + 7 knots, K1 = G + 4 A-columns per input.  grid [in][G + 7],
+// spline_w [out][in][G + 3], W [out][(G + 4) in]; slabs of out x (G + 4) in floats.
+constexpr int KAN_NB = 8;           // grid_size 5: grid_size + spline_order bases per input
 constexpr int KAN_K1 = 1 + KAN_NB;  // A-columns per input feature: SiLU + the bases
+constexpr int KG_MAX_GRID = 64;
+// A net's grid size and which kernel set runs it (chosen in one place, capi.hip's kan_sel): the
+// grid-5 kernels of kan.hip (sizes at compile time, a one-pass hidden backward) or the
+// any-grid-size kernels of kan_general.hip (G as a launch argument)
+struct KanSel {
+  int G, k1;  // k1 = G + 4
+  bool general;
+};
+// capi.hip's per-launch profiling brackets (SIREN_PROF), for kan_hidden_bwd, whose launches fall
+// under two kinds (SIREN_PROF_KAN_DW, SIREN_PROF_KAN_DX)
+void prof_begin(int kind, hipStream_t s);
+void prof_end(hipStream_t s, int launches = 1);
+constexpr int KAN_PROF_DW = 9, KAN_PROF_DX = 10;
 // fused layer kernels (the bases are recomputed in LDS; A and dA never reach HBM)
-hipError_t kan_fwd_fused(const float* X, const float* grid, const float* W, int64_t N, int in, int out, float* Y,
-                         hipStream_t s);
-// split-K over the rows: at most max_splits slabs of out x 9 in floats
-hipError_t kan_dw_fused(const float* X, const float* grid, const float* G, int64_t N, int in, int out,
+hipError_t kan_fwd_fused(const KanSel& k, const float* X, const float* grid, const float* W, int64_t N, int in, int out,
+                         float* Y, hipStream_t s);
+// split-K over the rows: at most max_splits slabs of out x K1 in floats
+hipError_t kan_dw_fused(const KanSel& k, const float* X, const float* grid, const float* G, int64_t N, int in, int out,
                         int64_t max_splits, float* slab, float* dW, hipStream_t s);
-hipError_t kan_dx_fused(const float* X, const float* grid, const float* Gout, const float* WT, int64_t N, int in,
-                        int out, float* Gin, hipStream_t s);
-// dW and Gin of a layer with out <= 64 in one pass (bases and G rows read once)
-hipError_t kan_bwd_fused(const float* X, const float* grid, const float* G, const float* WT, int64_t N, int in, int out,
-                         int64_t max_splits, float* slab, float* dW, float* Gin, hipStream_t s);
+hipError_t kan_dx_fused(const KanSel& k, const float* X, const float* grid, const float* Gout, const float* WT,
+                        int64_t N, int in, int out, float* Gin, hipStream_t s);
+// a hidden layer's backward: dW and (Gin != null) Gin, in one pass where the set has one (grid 5,
+// out <= 64: bases and G rows read once), else kan_dw_fused then kan_dx_fused
+hipError_t kan_hidden_bwd(const KanSel& k, const float* X, const float* grid, const float* G, const float* WT,
+                          int64_t N, int in, int out, int64_t max_splits, float* slab, float* dW, float* Gin,
+                          hipStream_t s);
 // the last layer (out = 1, in <= 64): wave-per-row forward (inference)
-hipError_t kan_head_fwd(const float* X, const float* grid, const float* W, int64_t N, int in, float* Y, hipStream_t s);
+hipError_t kan_head_fwd(const KanSel& k, const float* X, const float* grid, const float* W, int64_t N, int in, float* Y,
+                        hipStream_t s);
 // the last layer's forward + loss gradient + backward in one pass (out = 1, in <= 64); *nparts
 // loss partials (loss_mode 0: MSE, squared errors; 1: L1, absolute errors)
-hipError_t kan_head_train(const float* X, const float* grid, const float* W, const float* y, int64_t N, int in,
-                          int64_t n_valid, float gfac, int64_t slots, int64_t max_parts, float* out, float* g,
+hipError_t kan_head_train(const KanSel& k, const float* X, const float* grid, const float* W, const float* y, int64_t N,
+                          int in, int64_t n_valid, float gfac, int64_t slots, int64_t max_parts, float* out, float* g,
                           float* sse_part, float* slab, float* dW, float* Gin, int* nparts, hipStream_t s,
                           int loss_mode = 0);
 // its backward half for a given g [N] (zero on pad rows): Gin and dW in kan_head_train's block
 // partition and accumulation order for the same slots and max_parts
-hipError_t kan_head_bwd(const float* X, const float* grid, const float* W, const float* g, int64_t N, int in,
-                        int64_t slots, int64_t max_parts, float* slab, float* dW, float* Gin, hipStream_t s);
-// W = [base_w | spline_w * scaler] as [out][9 in], and (WT != null) its transpose [9 in][out]
-hipError_t kan_combine(const float* base_w, const float* spline_w, const float* scaler, int out, int in, float* W,
-                       float* WT, hipStream_t s);
-hipError_t kan_param_grads(const float* dW, const float* spline_w, const float* scaler, int out, int in,
+hipError_t kan_head_bwd(const KanSel& k, const float* X, const float* grid, const float* W, const float* g, int64_t N,
+                        int in, int64_t slots, int64_t max_parts, float* slab, float* dW, float* Gin, hipStream_t s);
+// W = [base_w | spline_w * scaler] as [out][K1 in], and (WT != null) its transpose [K1 in][out]
+hipError_t kan_combine(const KanSel& k, const float* base_w, const float* spline_w, const float* scaler, int out, int in,
+                       float* W, float* WT, hipStream_t s);
+hipError_t kan_param_grads(const KanSel& k, const float* dW, const float* spline_w, const float* scaler, int out, int in,
                            int accumulate, float* g_base, float* g_spline, float* g_scaler, hipStream_t s);
-// The same launches for any grid size G = 1 .. KG_MAX_GRID (spline_order 3): NB = G + 3 bases,
-// NG = G + 7 knots, K1 = G + 4 A-columns per input as run-time values (kan.hip, "any grid size").
-// grid [in][G + 7], spline_w [out][in][G + 3], W [out][(G + 4) in]; slabs of out x (G + 4) in floats.
-constexpr int KG_MAX_GRID = 64;
-hipError_t kang_fwd_fused(const float* X, const float* grid, const float* W, int64_t N, int in, int out, int G, float* Y,
-                          hipStream_t s);
-hipError_t kang_dw_fused(const float* X, const float* grid, const float* Gr, int64_t N, int in, int out, int G,
-                         int64_t max_splits, float* slab, float* dW, hipStream_t s);
-hipError_t kang_dx_fused(const float* X, const float* grid, const float* Gout, const float* WT, int64_t N, int in,
-                         int out, int G, float* Gin, hipStream_t s);
-hipError_t kang_head_fwd(const float* X, const float* grid, const float* W, int64_t N, int in, int G, float* Y,
-                         hipStream_t s);
-hipError_t kang_head_train(const float* X, const float* grid, const float* W, const float* y, int64_t N, int in, int G,
-                           int64_t n_valid, float gfac, int64_t slots, int64_t max_parts, float* out, float* g,
-                           float* sse_part, float* slab, float* dW, float* Gin, int* nparts, hipStream_t s,
-                           int loss_mode = 0);
-hipError_t kang_head_bwd(const float* X, const float* grid, const float* W, const float* g, int64_t N, int in, int G,
-                         int64_t slots, int64_t max_parts, float* slab, float* dW, float* Gin, hipStream_t s);
-hipError_t kang_combine(const float* base_w, const float* spline_w, const float* scaler, int out, int in, int G,
-                        float* W, float* WT, hipStream_t s);
-hipError_t kang_param_grads(const float* dW, const float* spline_w, const float* scaler, int out, int in, int G,
-                            int accumulate, float* g_base, float* g_spline, float* g_scaler, hipStream_t s);
 hipError_t kan_gemm(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn, int M,
                     int N, int64_t K, int splits, float* C, float* out, hipStream_t s);
 // The refit of update_grid (kan.py:168-215, Go = Gn) and of regrid (kan_general.hip, "the refit"): old

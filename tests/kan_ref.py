@@ -132,7 +132,7 @@ def _rn32(v):
 
 
 def kan_div_emulated(a, d):
-    """csrc/kan.hip kan_div on fp32 arrays a, d, emulated in fp64: y = RN(1/d), q = RN(a y),
+    """csrc/kan_tiles.h kan_div on fp32 arrays a, d, emulated in fp64: y = RN(1/d), q = RN(a y),
     r = fma(-q, d, a), q' = fma(r, y, q).  Products of two fp32 numbers and r are exact in fp64;
     the last sum is not always, so its fp64 rounding error (two-sum) nudges the sum one fp64 ulp
     towards the true value before the rounding to fp32 -- the result is the single rounding an

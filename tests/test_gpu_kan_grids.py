@@ -519,6 +519,65 @@ def test_knob_selects_the_kernel_set(lib, dev):
     assert general["kan_dw"] == 1 and general["kan_dx"] == 1, general
 
 
+@pytest.mark.parametrize("prefill", [False, True])
+def test_knob_combine_and_param_grads_bit_identical(lib, dev, prefill):
+    """One kan_combine and one kan_param_grads kernel (run-time NB) serve both sets: at grid 5 the
+    combined W and W^T in the workspace and siren_kan_backward's three parameter gradients of a
+    (17 -> 48) layer at 300 rows are bit-equal with the knob off and on -- from zeroed gradient
+    buffers and, with prefill, accumulated onto the same non-zero contents."""
+    G, fin, fout, rows = 5, 17, 48, 300
+    wlen = fout * (G + 4) * fin
+    pre = np.random.default_rng(5).normal(size=fout * fin * (G + 5) + 1).astype(F32)
+
+    def run():
+        _, _, _, up, net = _layer_case(lib, dev, G, fin, fout, rows, 1)
+        net.forward()
+        if prefill:
+            net.flat.copy_(torch.from_numpy(pre))
+        else:
+            net.b.zero_grads = 1
+        grads, _ = net.backward(up, True)
+        return net.ws_piece(0, (wlen,)), net.ws_piece((wlen + 63) // 64 * 64, (wlen,)), grads[0]
+
+    (w_a, wt_a, g_a), (w_b, wt_b, g_b) = _both_sets(lib, run)
+    assert not np.isnan(w_a).any() and not np.isnan(wt_a).any()
+    assert np.array_equal(w_a.reshape(fout, -1).T, wt_a.reshape(-1, fout))
+    assert np.array_equal(w_a, w_b) and np.array_equal(wt_a, wt_b)
+    for nm in g_a:
+        assert not np.isnan(g_a[nm]).any(), nm
+        assert np.array_equal(g_a[nm], g_b[nm]), nm
+
+
+@pytest.mark.parametrize("rows,splits,blocks", [(256, 1, 1), (500, 1, 2), (1100, 1, 4), (1100, 2, 5)])
+@pytest.mark.parametrize("G,general", [(5, 0), (5, 1), (11, 0)])
+def test_head_partition_reproduces_step(lib, dev, G, general, rows, splits, blocks):
+    """The head pass's block partition is one host function for both sets and the three sources of
+    g: on [1, 64, 1], siren_kan_step_backward fed the step's own g reproduces the step's gradients
+    bit for bit, at grid 5 (both sets) and 11, for 1, 2, 4 and 5 blocks (the count of loss partials
+    the step wrote).  Through the C-ABI a pass has 4 * splits slab rows and ceil(rows / 256) loss
+    partials, so at 1100 rows only 4 and 5 blocks can be had; 1 and 2 blocks take fewer rows."""
+    from inr_for_audio_amd._lib import Opt, options
+    h = 64
+    data, make = _two_layer(lib, dev, G, h, rows, splits, 11 + G)
+    with options(lib, {Opt.KAN_GENERAL: general}):
+        a = make().bind(data[4], splits, target=data[5], n_valid=rows - 7, n_total=float(rows))
+        a.flat.fill_(float("nan"))
+        a.b.zero_grads = 1
+        _, g = a.train_step()
+        grads = a.grads()
+        parts = a.ws_piece(a.G0_off + 2 * ((rows * h + 63) // 64 * 64), ((rows + 255) // 256,))
+        assert int(np.sum(~np.isnan(parts))) == blocks
+        b = make().bind(data[4], splits)
+        b.forward()
+        b.flat.fill_(float("nan"))
+        b.b.zero_grads = 1
+        again = b.step_backward(g)
+    for l in range(2):
+        for nm in grads[l]:
+            assert not np.isnan(grads[l][nm]).any(), (l, nm)
+            assert np.array_equal(grads[l][nm], again[l][nm]), (l, nm)
+
+
 @pytest.mark.parametrize("fin,fout,rows,splits", [(17, 48, 300, 1), (33, 70, 300, 2), (64, 1, 300, 2)])
 def test_knob_layer_within_gate(lib, dev, fin, fout, rows, splits):
     """Outputs and gradients of both sets at grid 5 within the gate of fp64; whether they are

@@ -1,5 +1,5 @@
-"""The unfused fp32 layers of csrc/layer_fp32.hip and the strided GEMM they run on (kan_gemm_kernel,
-kan_slab_reduce_kernel in csrc/kan.hip), through their four C entry points -- siren_fp32_linear,
+"""The unfused fp32 layers of csrc/layer_fp32.hip and the strided GEMM they run on (kan_gemm_kernel in
+csrc/kan.hip, kan_slab_reduce_kernel in csrc/kan_tiles.h), through their four C entry points -- siren_fp32_linear,
 siren_fp32_linear_bwd, siren_fp32_act, siren_fp32_act_bwd -- against tests/fp32_layer_ref.py: fp64,
 element by element.  `splits` is the test's choice here, not models._splits(rows).
 

@@ -57,7 +57,7 @@ def test_kan_div_is_the_ieee_quotient_on_these_grids(G):
 
 
 def test_span_by_bisection_equals_span_predicate():
-    """kg_bases_window's span: bisection for the first knot above x on non-decreasing knots gives
+    """kan_bases_window's KAN_SPAN_BISECT span: bisection for the first knot above x on non-decreasing knots gives
     #{j : g[j] <= x}, so s = count - 1 (count 1 .. NG - 1) is the span of the predicate
     g[j] <= x < g[j+1] -- on, beside and outside the knots, with repeated knots, +-inf and NaN."""
     rng = np.random.default_rng(0)

@@ -67,7 +67,7 @@ def test_kan_oracle_matches_reference():
 
 
 def test_span_by_count_equals_span_predicate():
-    """kan.hip kan_bases_window (KAN_WINDOW_GATHER): for non-decreasing knots the span found by
+    """kan_tiles.h kan_bases_window (KAN_WINDOW_GATHER): for non-decreasing knots the span found by
     counting, s = #{j : g[j] <= x} - 1 if that count is 1 .. 11 else -1, equals the span of the
     per-span predicate g[j] <= x < g[j+1] (kan.py:94-96's order-0 bases), for x on, between and
     outside the knots, +-inf and NaN, on uniform grids (efficient-KAN init) and on sorted grids
@@ -188,7 +188,7 @@ def test_kan_oracle_error_measured_and_zero_outside():
 
 
 def test_kan_div_emulated_is_the_ieee_quotient():
-    """kan.hip kan_div (a reciprocal, a product and two fmas; Markstein) equals the fp32 IEEE
+    """kan_tiles.h kan_div (a reciprocal, a product and two fmas; Markstein) equals the fp32 IEEE
     quotient a / D on every quotient the recursion forms for the kan_knots grids and probe inputs
     the GPU tests use, so the forward's bit-exactness claim holds on those non-default grids."""
     import kan_ref as kr

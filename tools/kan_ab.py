@@ -6,7 +6,10 @@ siren_kan_train_step cases of test_head_train_vs_unfused_route, and one whole st
 KAN([1, H, H, 1]), H = 64 and 128, at bench.py cfg5's 441 000 rows (the base library twice there:
 "differing_on_repeat" tells whether the step repeats at all).  Compared as bit patterns (NaN
 included): out, g, the flat gradient vector, dX and the whole workspace (W, W^T, X[l], dW, slabs,
-Gin).  Prints one JSON object; "differing" must be 0.
+Gin).  Prints one JSON object; "differing" must be 0.  --general runs the comparison through the
+any-grid-size kernel set instead: grid_size 1, 11, 64, and 5 under SIREN_OPT_KAN_GENERAL, on the layer
+cases of tests/test_gpu_kan_grids.py (_fwd_cases, _bwd_cases) and [1, 3, 1] and [1, 64, 1] steps under
+MSE and L1 (a few hundred rows each).
 
     python tools/kan_ab.py --libs parent=inr-for-audio_amd/libsiren_parent.so,this=inr-for-audio_amd/libsiren_hip.so
 """
@@ -38,7 +41,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--libs", required=True, help="base=path,other=path (paths relative to the repo root)")
     ap.add_argument("--step-rows", type=int, default=441_000, help="rows of the whole-step cases (bench.py cfg5's)")
+    ap.add_argument("--general", action="store_true", help="compare through the any-grid-size kernel set")
     args = ap.parse_args()
+    if args.general:
+        return general_main(args)
     import test_gpu_kan_kernels as T
     from inr_for_audio_amd import _lib
     libs = {}
@@ -109,6 +115,66 @@ def main():
             res["compared"] += sum(v.numel() for v in a.values())
             res["differing"] += sum(bad.values())
             res["cases"][f"{kind}{tuple(case)}"] = {k: v for k, v in bad.items() if v} or 0
+    print(json.dumps(res))
+    return 1 if res["differing"] else 0
+
+
+def general_main(args):
+    import test_gpu_kan_grids as T
+    from inr_for_audio_amd import _lib
+    from inr_for_audio_amd._lib import Opt, options
+    (base, lib_a), (other, lib_b) = [(nm, _lib.bind(os.path.join(ROOT, path), check_abi=False))
+                                     for nm, path in (i.split("=") for i in args.libs.split(","))]
+    dev = torch.device("cuda:0")
+
+    def layer_run(lib, case):
+        G, fin, fout, rows, splits = case
+        _, _, _, up, net = T._layer_case(lib, dev, G, fin, fout, rows, splits)
+        net.b.zero_grads = 1
+        got = {"out": _bits(torch.from_numpy(net.forward()))}
+        for want_dx in (True, False):
+            net.flat.fill_(float("nan"))
+            _, dx = net.backward(up, want_dx)
+            tag = "dx" if want_dx else "nodx"
+            got[f"grads_{tag}"] = _bits(net.flat)
+            got[f"ws_{tag}"] = _bits(net.ws)
+            if want_dx:
+                got["dX"] = _bits(torch.from_numpy(dx))
+        return got
+
+    def step_run(lib, case):
+        G, h, loss_mode = case
+        rows = 300
+        data, make = T._two_layer(lib, dev, G, h, rows, 3, h + G)
+        y = data[5].copy()
+        y[270:] = np.nan
+        net = make().bind(data[4], 3, target=y, n_valid=270, n_total=1234.0)
+        net.flat.fill_(float("nan"))
+        net.b.zero_grads = 1
+        out, g = net.train_step(loss_mode)
+        got = {"out": _bits(torch.from_numpy(out)), "g": _bits(torch.from_numpy(g)), "grads": _bits(net.flat),
+               "ws": _bits(net.ws)}
+        net.flat.fill_(float("nan"))
+        net.step_backward(g)
+        got["grads_step_backward"] = _bits(net.flat)
+        return got
+
+    res = {"libs": {base: None, other: None}, "set": "general", "cases": {}, "compared": 0, "differing": 0}
+    res["libs"] = {nm: p for nm, p in (i.split("=") for i in args.libs.split(","))}
+    for G in (1, 5, 11, 64):
+        layers = sorted({(G, fin, fout, rows, 1) for fin, fout, rows in T._fwd_cases(G)} | {(G, *c) for c in T._bwd_cases(G)})
+        steps = [(G, h, mode) for h in (3, 64) for mode in (0, 1)]
+        for kind, run, cases in (("layer", layer_run, layers), ("step", step_run, steps)):
+            for case in cases:
+                got = []
+                for lib in (lib_a, lib_b):
+                    with options(lib, {Opt.KAN_GENERAL: 1}):
+                        got.append(run(lib, case))
+                a, b = got
+                bad = {k: int((a[k] != b[k]).sum()) for k in a}
+                res["compared"] += sum(v.numel() for v in a.values())
+                res["differing"] += sum(bad.values())
+                res["cases"][f"{kind}{case}"] = {k: v for k, v in bad.items() if v} or 0
     print(json.dumps(res))
     return 1 if res["differing"] else 0
 
