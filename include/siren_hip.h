@@ -227,6 +227,25 @@ int siren_apply_update(const siren_net* net, float* params, const float* grads_f
 /* (siren_apply_update: `sse` is siren_grads.sse after any all-reduce -- sse[1] != 0 marks the guard
  * stalled, so every rank skips a step any rank's fused hand-off voided) */
 
+/* run.py:171-174 as the reference meant it: the weights of the best step so far.
+ * best: int32[4] = {float bits of best loss (+inf initially), best step (-1), snapshots taken, 0}
+ * Called on the step's stream BEFORE siren_apply_update / siren_adam_step (and after any all-reduce),
+ * while `params` still are the weights the loss in `sse` was computed with.  Two launches, no host
+ * synchronisation, capturable in a graph: a float4 copy best_params[0..n) = params[0..n), then one
+ * thread that sets best = {loss, state->last_epoch, taken + 1}; both iff
+ *   loss = (float)((double)sse[0] / n_total)  (the float siren_plateau_step records at
+ *          loss_hist[state->last_epoch])  <  the best loss     -- strict: NaN never wins, a tie keeps
+ *                                                                 the earlier step
+ *   and sse[1] == 0 and (guard given) guard->stalls == 0       -- a voided step has no loss.
+ * The guard's overflow flag is not consulted: the loss of a step whose fp16 backward overflowed is
+ * still the true loss of `params`, nothing advances on it, and the recomputed step (same loss, same
+ * last_epoch) is not taken again.  n: floats, n >= 4, n % 4 == 0, both vectors 16-B aligned (else
+ * SIREN_ERR_SHAPE); n_total > 0 and best_params != params (else SIREN_ERR_CONFIG); NULL params,
+ * best_params, state, sse or best: SIREN_ERR_NULL -- all before any launch. */
+int siren_best_keep(const float* params, float* best_params, int64_t n,
+                    const siren_opt_state* state, const float* sse, double n_total,
+                    const siren_guard* guard /* NULL ok */, int32_t* best, void* stream);
+
 /* ---- the loss-landscape plane ---------------------------------------------------------
  * run.py:192-198 (visualization=True): the MSE at steps x steps weight settings
  * theta_ij = theta + a_i d1 + b_j d2 around the fitted weights.

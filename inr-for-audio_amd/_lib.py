@@ -143,6 +143,8 @@ _SIGS = {
     "siren_apply_update": (ctypes.c_int, [ctypes.POINTER(SirenNet), _p, _p, _p, _p, _i64,
                                           ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_p),
                                           _p, _p, ctypes.c_double, _p, _p, _i64, _p, _p]),
+    # keep the best step's weights (run.py:171-174): params, best_params, n, state, sse, n_total, guard, best
+    "siren_best_keep": (ctypes.c_int, [_p, _p, _i64, _p, _p, ctypes.c_double, _p, _p, _p]),
     # the loss-landscape plane (run.py:192-198)
     "siren_plane_point": (ctypes.c_int, [_p, _p, _p, ctypes.c_float, ctypes.c_float, _p, _i64, _i32, _i32,
                                          ctypes.POINTER(_p), ctypes.POINTER(_p), ctypes.POINTER(_p), _p]),

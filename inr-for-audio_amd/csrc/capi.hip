@@ -605,6 +605,20 @@ int siren_apply_update(const siren_net* net, float* params, const float* grads_f
   return SIREN_OK;
 }
 
+static_assert(sizeof(BestState) == 4 * sizeof(int32_t), "siren_best_keep's best is a plain int32[4]");
+
+int siren_best_keep(const float* params, float* best_params, int64_t n, const siren_opt_state* state,
+                    const float* sse, double n_total, const siren_guard* guard, int32_t* best, void* stream) {
+  if (!params || !best_params || !state || !sse || !best) return SIREN_ERR_NULL;
+  // whole 16-B pieces
+  if (n < 4 || n % 4 || (((uintptr_t)params | (uintptr_t)best_params) & 15)) return SIREN_ERR_SHAPE;
+  if (!(n_total > 0.0) || best_params == params) return SIREN_ERR_CONFIG;
+  hipStream_t s = S(stream);
+  SIREN_PROF(SIREN_PROF_UPDATE, s, best_keep(params, best_params, n, (const OptState*)state, sse, n_total,
+                                             (const GuardState*)guard, (BestState*)best, s));
+  return SIREN_OK;
+}
+
 // ---- the loss-landscape plane (run.py:192-198) ------------------------------------------
 
 int siren_plane_point(const float* theta, const float* d1, const float* d2, float a, float b, float* out,

@@ -677,6 +677,63 @@ hipError_t plateau_step(OptState* st, const float* sse, double n_total, float* l
 }
 
 // ---------------------------------------------------------------------------------
+// Keep the best weights of the fit (run.py:171-174 as the reference meant it: best_loss, best_iter,
+// best_model), a pair of launches at the head of the update, before guard_check and Adam: the
+// parameters are still the ones this step's loss was computed with.
+// The predicate, the same in every block of the copy and in the commit:
+//   loss = (float)((double)sse[0] / n_total)      the float plateau_kernel records for this step
+//   take = loss < best->loss                      strict: a NaN never wins, an equal loss keeps the earlier step
+//          && sse[1] == 0 && !guard_stalled       a voided step (fused hand-off timeout) has no loss
+// The range guard's overflow flag is deliberately NOT part of it.  An overflow step's loss is the
+// true loss of the current weights (the forward is unaffected; only the fp16 dZ storage of the
+// backward overflowed), and nothing advances on such a step: the recomputed step sees the same
+// loss and the same last_epoch, and the strict < does not take again.  So the pair runs before
+// guard_check and the gradients are scanned once, not twice.
+// The copy reads best->loss and writes best_params only; the commit (one thread, the next launch on
+// the stream) writes best: no block writes anything another block reads.
+__device__ __forceinline__ bool best_take(const float* __restrict__ sse, double n_total,
+                                          const GuardState* __restrict__ guard, const BestState* __restrict__ best,
+                                          float* loss) {
+  *loss = (float)((double)sse[0] / n_total);
+  return *loss < __int_as_float(best->loss_bits) && sse[1] == 0.f && !guard_stalled(guard);
+}
+
+// best_params[i] = params[i] over n4 float4: 16 B per lane, so a wave moves eight whole 128-B lines
+// per pass; grid-stride over a capped grid (best_keep), plain vector loads and stores
+__global__ __launch_bounds__(256) void best_copy_kernel(const float4* __restrict__ p, float4* __restrict__ bp,
+                                                        int64_t n4, const float* __restrict__ sse, double n_total,
+                                                        const GuardState* __restrict__ guard,
+                                                        const BestState* __restrict__ best) {
+  float loss;
+  if (!best_take(sse, n_total, guard, best, &loss)) return;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x)
+    bp[i] = p[i];
+}
+
+__global__ void best_commit_kernel(const OptState* __restrict__ st, const float* __restrict__ sse, double n_total,
+                                   const GuardState* __restrict__ guard, BestState* best) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  float loss;
+  if (!best_take(sse, n_total, guard, best, &loss)) return;
+  best->loss_bits = __float_as_int(loss);
+  best->step = st->last_epoch;  // the index plateau_kernel is about to give this loss in loss_hist
+  best->taken += 1;
+}
+
+hipError_t best_keep(const float* params, float* best_params, int64_t n, const OptState* st, const float* sse,
+                     double n_total, const GuardState* guard, BestState* best, hipStream_t s) {
+  if (n < 4 || n % 4) return hipErrorInvalidValue;
+  // 2048 blocks = 8 per CU on 256 CUs: every CU streams, and the graph node has one size from
+  // 2 M floats up (a 5x1024 stack's 4.2 M floats take two passes)
+  hipLaunchKernelGGL(best_copy_kernel, dim3(grid_for(n / 4, 256, kBestKeepGridCap)), dim3(256), 0, s,
+                     (const float4*)params, (float4*)best_params, n / 4, sse, n_total, guard, best);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(best_commit_kernel, dim3(1), dim3(64), 0, s, st, sse, n_total, guard, best);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
 // h16 shadows of a hidden weight W[o][k] (fp32 master): Wb = W, WTb = W^T, through a
 // 64x64 LDS transpose so both stores are coalesced.
 // (the tile body is cast_tile64, siren_common.h: plane.hip's plane_point builds its shadows with it too)

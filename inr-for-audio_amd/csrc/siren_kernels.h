@@ -368,6 +368,18 @@ hipError_t adam_flat(float* p, const float* g, float* m, float* v, int64_t n, co
                      hipStream_t s, const GuardState* guard = nullptr, const float* sse = nullptr);
 hipError_t plateau_step(OptState* st, const float* sse, double n_total, float* loss_hist,
                         double* lr_hist, int64_t hist_cap, hipStream_t s, GuardState* guard = nullptr);
+// The best step so far (include/siren_hip.h siren_best_keep: a plain int32[4], no ABI struct)
+struct BestState {
+  int32_t loss_bits;  // float bits of the best loss (+inf initially)
+  int32_t step;       // its index in loss_hist (-1: none)
+  int32_t taken;      // snapshots taken
+  int32_t pad;
+};
+constexpr int kBestKeepGridCap = 2048;  // blocks of 256 threads x one float4: 2 M floats per pass
+// best_params[0..n) = params[0..n) (n % 4 == 0, 16-B aligned) and best = {loss, st->last_epoch, ++taken}
+// iff this step's loss < best's, sse[1] == 0 and the guard (nullable) is not stalled; two launches
+hipError_t best_keep(const float* params, float* best_params, int64_t n, const OptState* st, const float* sse,
+                     double n_total, const GuardState* guard, BestState* best, hipStream_t s);
 hipError_t cast_weight(const float* W, int H_out, int H_in, h16* Wb, h16* WTb, hipStream_t s);
 // cast_weight of n square H x H layers in one launch
 constexpr int kMaxInner = 16;  // == SIREN_MAX_INNER

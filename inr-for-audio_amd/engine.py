@@ -291,6 +291,9 @@ def shard_range(n_total: int, rank: int, world: int) -> tuple[int, int]:
     return n_total * rank // world, n_total * (rank + 1) // world
 
 
+_BEST_INIT = (0x7F800000, -1, 0, 0)   # siren_best_keep's state: +inf, no step, no snapshot
+
+
 def _opt_state_tensor(lr, min_lr, factor, patience, dev) -> torch.Tensor:
     """siren_opt_state for torch.optim.Adam(lr) + ReduceLROnPlateau(min, factor, patience,
     min_lr) with torch's defaults (run.py:116-117), as device bytes."""
@@ -316,6 +319,8 @@ class FitEngine:
     # ranks' parameters then drift apart -- timing passes after the measured run, never training)
     comm_enabled = True
     guard = None  # the fp16 backward range guard (SirenEngine; KAN is fp32 throughout)
+    keep_best = False   # keep_best=True: the best step's weights stay on the device (_setup_best)
+    best_params = None
 
     def __init__(self, device):
         self.lib = _lib.load()
@@ -351,6 +356,28 @@ class FitEngine:
         self.hist_cap = int(hist_cap)
         self.loss_hist = torch.zeros(max(self.hist_cap, 1), dtype=torch.float32, device=dev)
         self.lr_hist = torch.zeros(max(self.hist_cap, 1), dtype=torch.float64, device=dev)
+
+    def _setup_best(self, keep_best):
+        """keep_best=True (run.py:171-174 as the reference meant it): a second flat vector for the weights
+        of the best step so far and siren_best_keep's int32[4] {loss bits, step, taken, 0}, "best of this
+        run" like the reference's best_loss = float('inf') (a resumed run starts from +inf too).  Off (the
+        default): nothing is allocated and the update launches what it always did."""
+        self.keep_best = bool(keep_best)
+        if self.keep_best:
+            self.best_params = torch.zeros(self.layout.flat_len, dtype=torch.float32, device=self.device)
+            self._best_init = torch.tensor(_BEST_INIT, dtype=torch.int32).to(self.device)
+            self._best = self._best_init.clone()
+
+    def _launch_best(self, s):
+        """First thing in _launch_update, i.e. after the gradient all-reduce (the reduced sse slot is the
+        same on every rank, so every rank decides alike) and before Adam moves the weights the step's
+        loss belongs to.  n_total is the plateau call's: 1.0 when the sse slot holds a finished loss."""
+        if not self.keep_best:
+            return
+        check(self.lib.siren_best_keep(ptr(self.params), ptr(self.best_params), self.layout.n_params,
+                                       ptr(self.state), self.grads.data_ptr() + 4 * self.layout.sse_offset,
+                                       1.0 if self.spectral else float(self.n_total), ptr(self.guard),
+                                       ptr(self._best), s), "siren_best_keep")
 
     def _shard(self, coords, target, in_dim, n_total):
         """This rank's contiguous shard of the data as fp32 ([n][in_dim], [n]); sets n_total (the
@@ -625,6 +652,55 @@ class FitEngine:
             st.lr = float(sd["param_groups"][0]["lr"])
             self.state.copy_(torch.frombuffer(bytearray(bytes(st)), dtype=torch.uint8).to(self.device))
 
+    # ------------------------------------------------------------------ keep_best=True
+    def _need_best(self, what):
+        if not self.keep_best:
+            raise RuntimeError(f"{what}: the engine was built without keep_best=True")
+
+    def best_info(self):
+        """(loss, step, taken) of the best step so far (synchronises): the smallest loss of this run's
+        history, the first step that had it (its index in history(); -1 before any) and how many
+        snapshots were taken."""
+        self._need_best("best_info")
+        bits, step, taken, _ = self._best.cpu().tolist()
+        return float(torch.tensor([bits], dtype=torch.int32).view(torch.float32).item()), int(step), int(taken)
+
+    def best_state_dict(self) -> dict:
+        """The best step's weights as {parameter name: fp32 host tensor in its true shape} (synchronises)."""
+        self._need_best("best_state_dict")
+        if self.best_info()[1] < 0:
+            raise RuntimeError("best_state_dict: no snapshot was taken yet")
+        lay = self.layout
+        return {name: lay.true_view(self.best_params, i).detach().cpu().clone() for i, name in enumerate(lay.names)}
+
+    @torch.no_grad()
+    def load_best(self) -> None:
+        """The best step's weights become the live ones: best_params over params[:n_params] on the
+        current stream (SirenEngine then rebuilds every hidden layer's fp16 shadows from them).  Pointers
+        do not move; Adam state, scheduler, history and guard stay as they are, so a step() afterwards
+        goes on from the best weights with the final optimizer state.  An engine that replays a captured
+        step captures it again (_recapture), as loss_plane does after its eager launches.  Raises if no
+        snapshot was taken (synchronises)."""
+        self._need_best("load_best")
+        if self.best_info()[1] < 0:
+            raise RuntimeError("load_best: no snapshot was taken yet")
+        n = self.layout.n_params
+        self.params[:n].copy_(self.best_params[:n])
+        self._refresh_shadows()
+        if self.graph is not None:
+            self._recapture()
+
+    def _refresh_shadows(self):
+        """The weights' derived device copies, after the flat vector was written from outside a step."""
+
+    def _recapture(self):
+        """Capture the step again after eager launches ran between two replays of it.  Measured (DESIGN 6e):
+        the first replay of the old graph after a plane's launches left a stray word in the gradients' stall
+        slot, which voids the step; a graph captured after them replays as the first one did.  Capturing
+        runs nothing: parameters, optimizer state, history and guard stay as they are."""
+        self.graph = None
+        self.capture_graph()
+
 
 class SirenEngine(FitEngine):
     """Full-batch SIREN fit on one GPU (or one DP rank): run.py:108-190 minus the plots.
@@ -637,7 +713,8 @@ class SirenEngine(FitEngine):
                  min_lr: float = 1e-6, factor: float = 0.8, patience: int = 200,
                  n_total: int | None = None, micro_batch: int = 1 << 20, hist_cap: int = 20000,
                  splits: int | None = None, device=None, loss_mode: str = "mse", encoding=None,
-                 alpha: float = 0.0, stft_loss: str = "stft", split_spectral: bool = False):
+                 alpha: float = 0.0, stft_loss: str = "stft", split_spectral: bool = False,
+                 keep_best: bool = False):
         """`encoding` (encoding.GaussianEncoding, run.py:141-144): `coords` stay the raw [N][1]
         coordinates and model.in_features must be 2 * encoded_size -- the first layer's kernel
         builds the encoded input itself (training and infer()).
@@ -656,7 +733,12 @@ class SirenEngine(FitEngine):
         the frame blocks of its own samples), then every micro-batch runs its backward from its slice of
         g = dLoss/dout.  Only then does such an engine take more than one micro-batch or rank; each rank
         holds the whole target and a whole-signal loss workspace, so the caller passes the whole signal
-        (no n_total)."""
+        (no n_total).
+
+        `keep_best` (run.py:171-174 as the reference meant it): every step whose loss is below
+        all earlier ones of this run copies the weights it was computed with into `best_params`, on the
+        step's stream and inside a captured graph (siren_best_keep, first in the update); best_info(),
+        best_state_dict() and load_best() read and restore them.  False: nothing is added to the step."""
         self._spectral_args(target, n_total, micro_batch, round_up(int(micro_batch), 2 * ROW_TILE), loss_mode, alpha,
                             stft_loss, split_spectral)
         split = self.split_spectral
@@ -687,6 +769,7 @@ class SirenEngine(FitEngine):
                             pv(ix["wh"]), pv(ix["bh"]), [None if k is None else pv(k) for k in ix["a"]],
                             None if ix["a0"] is None else pv(ix["a0"]), rff_B=self.rff_B)
         self.grad_struct = make_grads(spec, lay, self.grads, ix)
+        self._setup_best(keep_best)
         self._Wp = (ctypes.c_void_p * L)(*[ptr(w) for w in self.W])
         self._Whp = (ctypes.c_void_p * L)(*[ptr(w) for w in self.Wh])
         self._WThp = (ctypes.c_void_p * L)(*[ptr(w) for w in self.WTh])
@@ -809,6 +892,7 @@ class SirenEngine(FitEngine):
                 b.head_scale_prev = 1
 
     def _launch_update(self):
+        self._launch_best(self._stream())
         check(self.lib.siren_apply_update(
             ctypes.byref(self.net), ptr(self.params), ptr(self.grads), ptr(self.exp_avg),
             ptr(self.exp_avg_sq), self.layout.n_params, self._Wp, self._Whp, self._WThp,
@@ -915,14 +999,6 @@ class SirenEngine(FitEngine):
             self._recapture()
         return plane
 
-    def _recapture(self):
-        """Capture the step again after eager launches ran between two replays of it.  Measured (DESIGN 6e):
-        the first replay of the old graph after a plane's launches left a stray word in the gradients' stall
-        slot, which voids the step; a graph captured after them replays as the first one did.  Capturing
-        runs nothing: parameters, optimizer state, history and guard stay as they are."""
-        self.graph = None
-        self.capture_graph()
-
     @torch.no_grad()
     def plane_state_dict(self, d1, d2, steps: int, i: int, j: int) -> dict:
         """theta_ij of loss_plane(d1, d2, steps) as {parameter name: fp32 host tensor in its true shape},
@@ -968,13 +1044,16 @@ class KanEngine(FitEngine):
     loss_mode='snr' and alpha != 0 (run.py:126-128, :160-169) run as FitEngine's phased step alone
     (`split_spectral=True`, the keyword of SirenEngine): siren_kan_forward per micro-batch
     into the signal-length out_sig, the loss once on the whole signal, siren_kan_step_backward from
-    each slice of g_sig."""
+    each slice of g_sig.
+
+    `keep_best` (SirenEngine's keyword): the best step's weights in `best_params`.  The knots are
+    buffers outside the flat vector and are not snapshotted: update_grid() forgets the snapshot."""
 
     def __init__(self, model, coords: torch.Tensor, target: torch.Tensor, *, lr: float = 1e-3,
                  min_lr: float = 1e-6, factor: float = 0.8, patience: int = 200,
                  n_total: int | None = None, micro_batch: int = 1 << 20, hist_cap: int = 20000,
                  splits: int | None = None, device=None, loss_mode: str = "mse", alpha: float = 0.0,
-                 stft_loss: str = "stft", split_spectral: bool = False):
+                 stft_loss: str = "stft", split_spectral: bool = False, keep_best: bool = False):
         from .kan import make_kan_grads
         if (loss_mode == "snr" or alpha != 0.0) and not split_spectral:
             raise NotImplementedError("KanEngine's one-pass step is fitted with a point loss (MSELoss only, or L1Loss "
@@ -994,6 +1073,7 @@ class KanEngine(FitEngine):
         self.net = model.make_net(views)
         self.grad_struct = make_kan_grads(model, gviews, self.grads.data_ptr() + 4 * lay.sse_offset,
                                           self.grads, lay.flat_len)
+        self._setup_best(keep_best)
         self._setup_opt(lr, min_lr, factor, patience, hist_cap)
 
         if split:
@@ -1046,6 +1126,7 @@ class KanEngine(FitEngine):
 
     def _launch_update(self):
         s = self._stream()
+        self._launch_best(s)
         check(self.lib.siren_adam_step(ptr(self.params), ptr(self.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq),
                                        self.layout.n_params, ptr(self.state), s), "siren_adam_step")
         check(self.lib.siren_plateau_step(ptr(self.state), self.grads.data_ptr() + 4 * self.layout.sse_offset,
@@ -1060,12 +1141,19 @@ class KanEngine(FitEngine):
         steps: every layer's knots move to its inputs' distribution and its curves are refitted, in
         place in the flat parameter vector and the grid buffers, so the net struct and a captured
         graph keep their pointers.  The Adam state, the scheduler and the history are untouched, as
-        in the reference, whose optimizer knows nothing of it.  Returns the updated model's output.
+        in the reference, whose optimizer knows nothing of it.  With keep_best the best state goes back to
+        (+inf, -1) -- a snapshot from before belongs to the old knots -- and `taken` keeps counting.  Returns
+        the updated model's output.
         Single process only: a rank sees only its shard, and the knots need global order statistics."""
         if _dist() is not None:
             raise NotImplementedError("KanEngine.update_grid: one process only (global order statistics across "
                                       "ranks are not implemented)")
-        return self.model(self.coords, update_grid=True)
+        out = self.model(self.coords, update_grid=True)
+        if self.keep_best:
+            # the knots are buffers outside the flat vector: a snapshot from before they moved belongs to
+            # other knots.  Back to (+inf, -1) on the stream; `taken` keeps counting
+            self._best[:2].copy_(self._best_init[:2])
+        return out
 
     @torch.no_grad()
     def infer(self, coords: torch.Tensor, chunk: int | None = None) -> torch.Tensor:

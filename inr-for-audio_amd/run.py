@@ -88,7 +88,7 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
           filename=None, data_dir="data", seed=None, micro_batch=1 << 20, use_graph=True,
           device=None, verbose=False, multichannel=False, patience=200, restated_losses=False,
           stft_loss="stft", split_spectral=False, kan_grid_size=5, kan_prev_grid_size=None,
-          kan_regrid_margin=0.01):
+          kan_regrid_margin=0.01, keep_best=False):
     """Fit one clip; returns the checkpoint path (run.py:400).  Extra keyword-only knobs:
     ``filename`` (default ``{data_dir}/{inst}.wav`` as run.py:33), ``seed`` (torch.manual_seed
     before model construction), ``micro_batch`` (rows per fused micro-batch), ``use_graph``
@@ -115,7 +115,18 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     into a model of ``kan_grid_size`` as before), ``kan_regrid_margin`` (that refit's ``margin``, kan.py:169's
     0.01 by default: an absolute pad of the knot range, which leaves a hidden input whose activations span
     less than about ``kan_grid_size`` x margin with an empty last knot span, and the refit then refuses it as
-    rank deficient -- pass a smaller one, 0 included, for such a model; recorded when it is not 0.01)."""
+    rank deficient -- pass a smaller one, 0 included, for such a model; recorded when it is not 0.01),
+    ``keep_best`` (run.py:171-174 as the reference meant it: its ``best_model = model`` is an alias, so the
+    reference and, by default, this port write the LAST step's weights.  True keeps the weights of the
+    step with the smallest loss of this run on the device, the first such step, decided and copied inside
+    the step itself with no host read-back (engine keep_best), and restores them after the fit
+    and its top-up: the landscape plane, output.wav, both SNRs and the checkpoint's model_state_dict are
+    then the best step's; optimizer_state_dict stays the final Adam state as run.py:359-362 saves it.  Every
+    arch, loss and data path the call otherwise takes; a resumed run starts from +inf, "best of this run".
+    A fit that took no snapshot -- no step, or every loss NaN -- keeps its final weights.  parameters.json
+    gains keep_best and best_loss only when it is set)."""
+    if not isinstance(keep_best, bool):
+        raise TypeError(f"keep_best={keep_best!r} must be a bool")
     if method not in ("wave", "mdct"):
         raise ValueError("specify the correct fitting method as wave or mdct (run.py:77-78)")
     if method == "mdct" and bwe:
@@ -228,6 +239,8 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         if not restated_losses:
             raise NotImplementedError("split_spectral is the restated_losses step across micro-batches and ranks")
         kw["split_spectral"] = True
+    if keep_best:
+        kw["keep_best"] = True
     engine = Engine(model, model_input, ground_truth, lr=learning_rate, min_lr=min_learning_rate,
                     patience=patience, micro_batch=micro_batch, hist_cap=total_steps, device=dev, **kw)
     if ckpt is not None:
@@ -252,6 +265,15 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
     end_time = time.time()
     total_time = (end_time - start_time) / 60
 
+    # run.py:171-174: the reference hands best_model to the plane and to the inference below
+    best_loss = None
+    if keep_best:
+        best_loss, best_step, _ = engine.best_info()
+        if best_step >= 0:
+            engine.load_best()
+        else:
+            best_loss = None
+
     # run.py:192-208: the loss-landscape plane around the fitted weights, after the timed fit.  The
     # directions are drawn on rank 0 (loss_plane broadcasts them) from the run's seed when it has one
     landscape_time = None
@@ -270,12 +292,15 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
         losses = 10 * np.log10(raw_losses.astype(np.float64) + 1e-10)   # run.py:180
     lrs = 10 * np.log10(raw_lrs)                                     # run.py:190
     best_iter = int(np.argmin(raw_losses)) if len(raw_losses) else -1
+    if best_loss is not None:
+        best_iter = best_step   # the same step: argmin and the device's strict < both pick the first minimum
 
     param_size = sum(p.nelement() * p.element_size() for p in model.parameters())
     buffer_size = sum(b.nelement() * b.element_size() for b in model.buffers())
     model_size = (param_size + buffer_size) / 1024
 
-    # inference (run.py:251-256); best_model aliases the final model (run.py:173)
+    # inference (run.py:251-256); best_model aliases the final model (run.py:173) unless keep_best
+    # restored the best step's weights above
     if bwe:
         coords = get_coord(input_data.original_sample_rate * duration, dim=1)
         recover_sample_rate = input_data.original_sample_rate
@@ -342,6 +367,9 @@ def train(experiment_path: str, tag: str, inst: str, duration: int, num_channels
                 params["kan_regrid_margin"] = kan_regrid_margin
         if split_spectral:
             params["split_spectral"] = True
+        if keep_best:
+            params["keep_best"] = True
+            params["best_loss"] = best_loss
         if visualization:
             params["landscape_time_s"] = landscape_time
         save_parameters(experiment_folder, **params)
